@@ -1,8 +1,14 @@
 """bench.py — users scored/sec + SVD build time of the PureSVD hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline only: it generates the matrix, builds twice (the first build of the process warms the
+path up, the second is `build_s`), warms the scoring loop up, times the K steps and prints the line.  `--dump-outputs DIR`
+writes the lists of the last timed step (DIR/recommendations.npy: external item ids, float64).  Everything below that
+is not `value`, `ms_per_step` or `build_s` — the first-pass and long-region figures, latency, per-kernel times and
+rooflines, the CPU baseline, the sub-blocks and bench_detail.json — is measured with `--full` only.
 
 HEADLINE (top-level `value`, `config`, `roofline`, `cpu_baseline`): the configuration BASELINE.json's `metric`
 is quoted on — "ML-20M rank-50 PureSVD" — as an ML-20M-shaped synthetic matrix (138 493 x 26 744, ~2e7 nnz, 10
@@ -18,7 +24,7 @@ The other half of the metric, `build_s`, is the WHOLE warm build as the model la
 CSR, relabelling into popularity order, CSC image, eigensolver, re-indexing of catalogue and test rows by factor
 norm, factor images — itemised in `build`, with the first (cold) build of the process next to it.
 
-Sub-blocks (N = 1 only, `--only-headline` skips them), each with its own ms_per_step / swept fraction / rows
+Sub-blocks (--full, N = 1 only, `--only-headline` skips them), each with its own ms_per_step / swept fraction / rows
 identical to the CPU path:
   configs2_ml20m_rank100_top20   BASELINE.json configs[2]
   configs1_s1m_rank50_top10      BASELINE.json configs[1] (1M x 100K, 1e8 nnz), pruned and --no-prune sweeps
@@ -112,10 +118,24 @@ def parse():
     ap.add_argument('--warm', default='code', choices=['code', 'pipeline', 'none'],
                     help="what HipOps() does once per process: load the library's code objects (default), also run the miniature pipeline, or nothing")
     ap.add_argument('--cpu-users', type=int, default=0, help='users in the CPU scoring sample (0 = auto)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything besides the headline figure: the first pass of the process, the long region and '
+                         'the un-pipelined latency, per-kernel times and rooflines, the CPU baseline, the rank-100 and adversarial '
+                         'sub-blocks and bench_detail.json.  Without it a run sets up, warms up, times the --steps passes and prints '
+                         'the line (--detail implies --full)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step returned to its caller — the top-k lists of every '
+                         'user as external item ids — to DIR/recommendations.npy (float64; above %d MB a fixed seeded sample of '
+                         'rows, their indices in DIR/recommendations_rows.npy)' % (DUMP_MAX_BYTES >> 20))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    args.full = args.full or args.detail
+    return args
 
 
 MAX_PASS_STREAMS = 6      # pass streams + copy stream + the solver's monitor stream stay within the 8 hardware queues asked for
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: larger results are sampled
 
 
 def ensure_world(args):
@@ -367,9 +387,10 @@ class Bench:
         return state, t
 
     # ---- scoring ---------------------------------------------------------------------------------------------
-    def score_passes(self, st, topk, steps, warmup, prune=True, batches=None):
+    def score_passes(self, st, topk, steps, warmup, prune=True, batches=None, full=True):
         """Timed region: `steps` full passes, result of every pass copied to a pinned host buffer (double-buffered on a
-        side stream).  Returns (seconds max over ranks, last host result, extras)."""
+        side stream).  Returns (seconds max over ranks, last host result, extras); `full` adds the long region and the
+        un-pipelined latency after it."""
         from polara_amd import scoring
         ops = self.ops
         F, A = st['F'], st['A']
@@ -564,29 +585,32 @@ class Bench:
         elapsed = time.perf_counter() - t0
         if gc_was:
             gc.enable()
-        # the same loop over a region 10x as long (not `value`): what a pass costs once the fill of the first passes and the
-        # drain of the last (its 0.8 ms latency + the 0.4 ms copy of its result) are spread over 200 instead of 20 steps
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        loop(10 * steps, use_cap)
-        torch.cuda.synchronize()
-        long_ms = 1e3 * (time.perf_counter() - t1) / max(10 * steps, 1)
-        # un-pipelined latency of one pass: compute + copy + sync
-        lat = []
-        for i in range(3):
+        # the lists of the LAST timed pass, taken before any later pass can rewrite their buffer
+        last = host[(steps - 1) % DEPTH]
+        if use_cap == 'recorded':
+            last = recorded[(steps - 1) % len(recorded)].host_out
+        last = last.clone()
+        long_ms, lat = None, []
+        if full:
+            # the same loop over a region 10x as long (not `value`): what a pass costs once the fill of the first passes and the
+            # drain of the last (its 0.8 ms latency + the 0.4 ms copy of its result) are spread over 200 instead of 20 steps
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-            one(i, use_cap)
+            loop(10 * steps, use_cap)
             torch.cuda.synchronize()
-            lat.append(time.perf_counter() - t1)
+            long_ms = 1e3 * (time.perf_counter() - t1) / max(10 * steps, 1)
+            # un-pipelined latency of one pass: compute + copy + sync
+            for i in range(3):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                one(i, use_cap)
+                torch.cuda.synchronize()
+                lat.append(time.perf_counter() - t1)
         if self.world > 1:
             tt = torch.tensor([elapsed], dtype=torch.float64, device='cpu' if self.debug_backend == 'gloo' else self.dev)
             torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
             elapsed = float(tt.item())
-        last = host[(steps - 1) % DEPTH if steps else 0]
-        if use_cap == 'recorded' and steps:
-            last = recorded[(steps - 1) % len(recorded)].host_out
-        extras = dict(latency_ms_per_pass=1e3 * float(np.median(lat)), d2h_bytes_per_pass=int(n_local * topk * 8),
+        extras = dict(latency_ms_per_pass=1e3 * float(np.median(lat)) if lat else None, d2h_bytes_per_pass=int(n_local * topk * 8),
                       host_result=last, launch=self.launch_mode)
         extras['serial_ms_per_step'] = serial_ms
         extras['long_region_ms_per_step'] = long_ms
@@ -665,21 +689,31 @@ class Bench:
 
     # ---- one complete measurement of (workload, rank, topk) -------------------------------------------------
     def measure(self, c, workload, rank, topk, steps, warmup, prune=True, norm_order=True, cpu=True, cpu_users=0,
-                cpu_build=True, catalogue='svd', cold_build=None, cpu_build_whole=False):
+                cpu_build=True, catalogue='svd', cold_build=None, cpu_build_whole=False, full=True, outputs=False):
+        """`full=False`: the build and the timed passes only (no long region, latency, kernel times, rooflines or CPU
+        baseline).  `outputs`: the lists of the last timed pass of every user, external item ids, go to out['outputs']."""
         ops, comm = self.ops, self.comm
         n_users, n_items = c['shape']
         nnz = int(c['indptr'][-1])
         st, tb = self.build(c, rank, norm_order, catalogue)           # warm (the process has built before) or cold
-        elapsed, recs, extra = self.score_passes(st, topk, steps, warmup, prune=prune, batches=self.args.batches or None)
-        ms, n_launch, stats = self.kernel_times(st, topk, prune=prune)
+        elapsed, recs, extra = self.score_passes(st, topk, steps, warmup, prune=prune, batches=self.args.batches or None,
+                                                 full=full)
+        ms, n_launch, stats = self.kernel_times(st, topk, prune=prune) if full else ({}, {}, {})
+        lists = None
+        if outputs:
+            lists = self.external_ids(st, extra['host_result'].numpy())
+            if comm.world > 1:
+                lists = comm.gather_rows(lists, n_users, topk)
         out = None
         if comm.rank == 0:
             lo, hi = st['lo'], st['hi']
             cand_ms = ms.get('score_candidates')
             flops = 2.0 * (hi - lo) * n_items * rank
-            swept = stats['tiles_scored'] / max(stats['tiles_total'], 1)
+            swept = stats['tiles_scored'] / max(stats['tiles_total'], 1) if stats else None
             tp = stats.get('two_phase')
-            if tp:      # head launch + the chunk launches of the seeded splits over the rest of the catalogue
+            if not full:
+                n_chunk = None
+            elif tp:    # head launch + the chunk launches of the seeded splits over the rest of the catalogue
                 n_chunk = 1 + int(ops.lib.pk_score_chunk_launches(n_items - 32 * tp['head_tiles'], rank, tp['splits'], 0, 1))
             else:
                 n_chunk = int(ops.lib.pk_score_chunk_launches(n_items, rank, stats.get('item_splits', 1), 0, 1 if prune else 0))
@@ -766,7 +800,7 @@ class Bench:
                                        'note': 'the same products on v_mfma_f32_32x32x2_f32 (round 1) are capped at 157.3 TFLOP/s'},
                     'dense_equivalent': {'flop_per_launch': flops, 'TFLOP/s': flops / (cand_ms * 1e-3) / 1e12,
                                          'of_f32_mfma_peak': flops / (cand_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS}}
-            if spmm_ms:
+            if spmm_ms and full:
                 gbps = float(sum(spmm_bytes) / (sum(spmm_ms) * 1e-3) / 1e9)
                 out['roofline_build'] = {
                     'kernel': 'spmm_csr_groups_kernel', 'bound': 'hbm', 'achieved': gbps, 'peak': PEAK_HBM_GBPS, 'unit': 'GB/s',
@@ -794,6 +828,8 @@ class Bench:
                     'refold_ms': (ms.get('spmm_rows_list') or ms.get('spmm_flagged') or ms.get('fold_rows') or 0.0) + (ms.get('rescore_topk_refolded') or 0.0)}
             if cold_build is not None:
                 out['build_cold'] = cold_build
+            if lists is not None:
+                out['outputs'] = {'recommendations': lists}
             if cpu and comm.world == 1:
                 n_score = cpu_users or min(n_users, 20000)
                 V_ext = self.external_V(st)
@@ -1089,6 +1125,22 @@ def write_detail(record):
             log('could not write %s/bench_detail.json: %s' % (d, exc))
 
 
+def dump_outputs(path, outputs):
+    """--dump-outputs: every array of `outputs` as <path>/<name>.npy in float64 (item ids are exact there), together at most
+    DUMP_MAX_BYTES; a larger result keeps a fixed, seeded sample of its rows, whose indices go to <path>/<name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(len(outputs), 1) - 4096       # (room for the .npy headers)
+    for name, a in outputs.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > budget:
+            row_bytes = max(a.nbytes // max(a.shape[0], 1), 1)
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], budget // (row_bytes + 8), replace=False))
+            np.save(os.path.join(path, name + '_rows.npy'), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + '.npy'), a)
+    log('outputs of the last timed step: %s/{%s}.npy' % (path, ','.join(outputs)))
+
+
 def main():
     args = parse()
     ensure_world(args)
@@ -1102,22 +1154,27 @@ def main():
     prune = not args.no_prune
     c = B.generate(args.workload, args.scale)
     gen_s = c['gen_s']
-    # cold build: the first heavy GPU work of the process (allocator growth, page tables, code objects), itemised
+    # cold build: the first heavy GPU work of the process (allocator growth, page tables, code objects), itemised; the
+    # build of the line (`build_s`) is the process's second
     st_cold, cold = B.build(c, headline_rank, not args.no_norm_order)
-    # ... and the first scoring pass of the process on it (host wall time, device idle before and after)
     from polara_amd import scoring as _scoring, runtime_info as _runtime_info
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    _scoring.recommend(B.ops, st_cold['F'], st_cold['A'], headline_topk, True, prune=prune)
-    torch.cuda.synchronize()
-    first_pass_ms = 1e3 * (time.perf_counter() - t0)
+    if args.full:
+        # ... and the first scoring pass of the process on it (host wall time, device idle before and after)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _scoring.recommend(B.ops, st_cold['F'], st_cold['A'], headline_topk, True, prune=prune)
+        torch.cuda.synchronize()
+        first_pass_ms = 1e3 * (time.perf_counter() - t0)
     del st_cold
     torch.cuda.empty_cache()
     full_size = comm.world == 1 and args.scale == 1.0
     head = B.measure(c, args.workload, headline_rank, headline_topk, args.steps, args.warmup, prune=prune,
-                     norm_order=not args.no_norm_order, cpu=not args.no_cpu_baseline, cpu_users=args.cpu_users,
-                     cold_build=cold, cpu_build_whole=full_size and args.workload in ('ml20m', 'ml1m'))
-    if comm.rank == 0:
+                     norm_order=not args.no_norm_order, cpu=args.full and not args.no_cpu_baseline, cpu_users=args.cpu_users,
+                     cold_build=cold, cpu_build_whole=full_size and args.workload in ('ml20m', 'ml1m'), full=args.full,
+                     outputs=bool(args.dump_outputs))
+    if comm.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, head.pop('outputs'))
+    if comm.rank == 0 and args.full:
         # what a process pays ONCE: creating the operator set (the library's code objects), its first build and its first
         # pass — next to the warm figures of the line (`build_s`, `ms_per_step`); `time_to_first_model_s` is their sum up to
         # the first model (the reference pays no warm-up, tools/timing.py:20-34)
@@ -1127,7 +1184,7 @@ def main():
                         'solver_cold_s': cold['solver_s'], 'first_pass_ms': first_pass_ms, 'gc_frozen_objects': gc_frozen, 'hw_queues': rt['hw_queues'],
                         'hw_queues_in_time': rt['in_time']}
     subs, adversarial = {}, {}
-    if args.scale == 1.0 and not args.only_headline and args.workload == 'ml20m' and not args.rank:
+    if args.full and args.scale == 1.0 and not args.only_headline and args.workload == 'ml20m' and not args.rank:
         # BASELINE.json configs[2] as written (rank 100, top-20) rides in the line at every N next to the metric's rank 50
         s = B.measure(c, 'ml20m', 100, 20, max(5, min(args.steps, 20)), 2, cpu=not args.no_cpu_baseline, cpu_users=5000,
                       cpu_build=False)
@@ -1137,7 +1194,7 @@ def main():
                                      'gramian_steps': s['build']['gramian_steps']}
             if 'cpu_baseline' in s:
                 head['rank100_top20']['identical_rows'] = s['cpu_baseline'].get('gpu_vs_cpu_identical_rows')
-    if full_size and not args.only_headline and args.workload == 'ml20m':
+    if args.full and full_size and not args.only_headline and args.workload == 'ml20m':
         # the headline depends on how fast the item-factor norms decay (the sweep is pruned by a norm bound): the same
         # matrix with three less friendly catalogues ALWAYS runs next to it and rides in the compact line
         sub_steps = max(5, min(args.steps, 20))
@@ -1176,6 +1233,9 @@ def main():
             torch.cuda.empty_cache()
     if comm.rank != 0:
         return
+    if not args.full:
+        print(compact_line(head, comm.world, args.steps, args.warmup, None, args.scale), flush=True)
+        return
     tag = {'ml20m': 'ml20m', 's1m': 's1m'}.get(args.workload)
     traffic = pmc_traffic(tag) if (tag and full_size and headline_rank == 50) else {}
     if 'roofline' in head and traffic:
@@ -1203,6 +1263,7 @@ def main():
                               'products; same source' % (2 * products))
     detail = dict(head)
     detail.pop('host_result', None)
+    detail.pop('outputs', None)
     detail.update(metric='users scored/sec + SVD build time, ML-20M rank-50 PureSVD', unit='users/s', n_gpus=comm.world,
                   steps=args.steps, warmup=args.warmup, gen_s=gen_s, scale=args.scale,
                   dtype_detail='candidate scoring on bf16 MFMA with every operand split into two bf16 (3 MFMAs per product, fp32 '

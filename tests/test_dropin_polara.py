@@ -1,7 +1,9 @@
 """Drop-in check against the REFERENCE ITSELF (build container only: skipped wherever /root/reference is absent,
 never part of -m gpu): Polara's own `RecommenderData` object drives Polara's `SVDModel` / `CoffeeModel` and ours
 (on the test-only NumPy double of the device ops) side by side — same data object, same events, same consumers
-(`recommendations`, `evaluate`, `show_recommendations`, rank truncation, data-change notifications)."""
+(`recommendations`, `evaluate`, `show_recommendations`, rank truncation, data-change notifications).  The two metric
+tests at the end compare with the reference's numbers recorded in tests/golden/dropin_metrics.npz
+(tests/golden/make_dropin_metrics.py) and run everywhere."""
 import contextlib
 import io
 import os
@@ -12,11 +14,12 @@ import pytest
 
 REF = '/root/reference'
 HERE = os.path.dirname(os.path.abspath(__file__))
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'polara')), reason='reference tree not present')
 
 
 @pytest.fixture(scope='module')
 def polara():
+    if not os.path.isdir(os.path.join(REF, 'polara')):
+        pytest.skip('reference tree not present')
     sys.path.insert(0, os.path.join(HERE, 'golden', '_numba_shim'))   # numba is not installed: pass-through shim
     sys.path.insert(0, REF)
     import warnings
@@ -409,53 +412,56 @@ def test_data_events_reach_both_models_alike(polara, kind):
     assert len(our_m.training_time) == len(ref_m.training_time)            # rebuilt exactly as often
 
 
-@pytest.mark.parametrize('cfg', [dict(warm_start=True, holdout_size=3, test_ratio=0.2),
-                                 dict(test_fold=4, warm_start=False, holdout_size=2, test_ratio=0.25, random_holdout=True),
-                                 dict(warm_start=True, holdout_size=1, test_ratio=0.2)],
-                         ids=['warm_h3', 'known_h2', 'warm_h1'])
-def test_native_metrics_equal_the_reference_evaluate(polara, cfg):
+METRIC_CFGS = [dict(warm_start=True, holdout_size=3, test_ratio=0.2),
+               dict(test_fold=4, warm_start=False, holdout_size=2, test_ratio=0.25, random_holdout=True),
+               dict(warm_start=True, holdout_size=1, test_ratio=0.2)]
+METRIC_CFG_IDS = ['warm_h3', 'known_h2', 'warm_h1']
+METRIC_TOPKS = (12, 5, 1)
+METRIC_SWITCH = (None, 4)
+
+
+def golden_metrics():
+    return np.load(os.path.join(HERE, 'golden', 'dropin_metrics.npz'))
+
+
+def same_hits(got, want):
+    """a Hits tuple against the recorded one (NaN where the reference returned None)"""
+    assert len(got) == len(want), (got, want)
+    for a, b in zip(got, want):
+        assert (a is None and np.isnan(b)) or a == b, (got, want)
+
+
+@pytest.mark.parametrize('cid', METRIC_CFG_IDS)
+def test_native_metrics_equal_the_reference_evaluate(cid):
     """polara_amd.evaluation (what `evaluate()` runs on ArrayData / without Polara) against the reference's
     `evaluate()` on the SAME lists and holdout, over topk, switch_positive and the metric families — every number
-    that does not pass through the reference's uninitialised-memory division (see evaluation.py's header)."""
+    that does not pass through the reference's uninitialised-memory division (see evaluation.py's header).  The lists
+    (the reference's SVDModel, rank 6, top-12, on Polara's own data object split as METRIC_CFGS says), the holdout and the
+    reference's numbers are recorded in tests/golden/dropin_metrics.npz."""
     from polara_amd import evaluation as ev
-    data = make_data(polara, **cfg)
-    ref_m = polara.SVDModel(data)
-    ref_m.verbose = False
-    ref_m.rank, ref_m.topk = 6, 12
-    np.random.seed(0)
-    quiet(ref_m.build)
-    recs = ref_m.recommendations
-    f = data.fields
-    h = data.test.holdout
-    hu, hi_, hf = h[f.userid].values, h[f.itemid].values, h[f.feedback].values.astype(np.float64)
-    hu = np.unique(hu, return_inverse=True)[1]                       # rows of the lists = the sorted holdout users
-    n_items = data.get_test_shape()[1] if hasattr(data, 'get_test_shape') else recs.max() + 1
-    for topk in (12, 5, 1):
-        for switch_positive in (None, 4):
+    g = golden_metrics()
+    p = cid + '/'
+    recs, hu, hi_, hf = g[p + 'recs'], g[p + 'hu'], g[p + 'hi'], g[p + 'hf']
+    n_items, holdout_size = int(g[p + 'n_items']), int(g[p + 'holdout_size'])
+    for topk in METRIC_TOPKS:
+        for switch_positive in METRIC_SWITCH:
             kw = dict(topk=topk, switch_positive=switch_positive)
-            want = dict((type(s).__name__, s) for s in quiet(ref_m.evaluate, 'all', **kw))
+            q = '%s%d_%s/' % (p, topk, switch_positive)
             got = dict((type(s).__name__, s) for s in ev.evaluate(recs, hu, hi_, hf, n_items, metric_type='all',
-                                                                    holdout_size=data.holdout_size, **kw))
-            assert got.keys() == want.keys()
-            for a, b in zip(got['Hits'], want['Hits']):
-                assert (a is None and b is None) or a == b, (topk, switch_positive, got['Hits'], want['Hits'])
-            assert np.isclose(got['Experience'].coverage, want['Experience'].coverage, rtol=1e-13)
-            rk_got, rk_want = got['Ranking']._asdict(), want['Ranking']._asdict()
+                                                                    holdout_size=holdout_size, **kw))
+            assert sorted(got) == list(g[q + 'families'])
+            same_hits(got['Hits'], g[q + 'hits'])
+            assert np.isclose(got['Experience'].coverage, g[q + 'coverage'], rtol=1e-13)
+            rk_got = got['Ranking']._asdict()
             for name in set(rk_got) & {'map', 'arhr', 'mrr'}:
-                assert np.isclose(rk_got[name], rk_want[name], rtol=1e-12), (name, topk, switch_positive)
-            rl_got, rl_want = got['Relevance']._asdict(), want['Relevance']._asdict()
+                assert np.isclose(rk_got[name], g[q + 'ranking_' + name], rtol=1e-12), (name, topk, switch_positive)
+            rl_got = got['Relevance']._asdict()
             if 'hr' in rl_got:
-                assert np.isclose(rl_got['hr'], rl_want['hr'], rtol=1e-13)
+                assert np.isclose(rl_got['hr'], g[q + 'relevance_hr'], rtol=1e-13)
 
 
-@pytest.mark.parametrize('switch_positive', [None, 3])
-def test_zero_feedback_holdout_entries_count_like_the_reference(polara, switch_positive):
-    """Holdout entries with feedback exactly 0 (explicit zero ratings, ignore_feedback=False): never a hit or a miss in
-    the reference (boolean image x rank matrix), dropped from the per-class counts under a positive/negative split,
-    still holdout items without one (evaluation.py:60-84, 188-205)."""
-    import pandas as pd
-    from polara.recommender import evaluation as rev
-    from polara_amd import evaluation as ev
+def zero_feedback_inputs():
+    """seeded lists and a holdout with explicit zero ratings, two of every user's four holdout items recommended"""
     rng = np.random.RandomState(5)
     n_users, n_items, topk, per = 60, 40, 8, 4
     recs = np.stack([rng.permutation(n_items)[:topk] for _ in range(n_users)]).astype(np.int64)
@@ -464,19 +470,27 @@ def test_zero_feedback_holdout_entries_count_like_the_reference(polara, switch_p
                                 rng.permutation(np.setdiff1d(np.arange(n_items), recs[u]))[:per - 2]]
                           for u in range(n_users)])
     hf = rng.randint(0, 6, len(hu)).astype(np.float64)                                    # ... some with feedback 0
+    return recs, hu, hi_, hf, n_items, topk, per
+
+
+@pytest.mark.parametrize('switch_positive', [None, 3])
+def test_zero_feedback_holdout_entries_count_like_the_reference(switch_positive):
+    """Holdout entries with feedback exactly 0 (explicit zero ratings, ignore_feedback=False): never a hit or a miss in
+    the reference (boolean image x rank matrix), dropped from the per-class counts under a positive/negative split,
+    still holdout items without one (evaluation.py:60-84, 188-205).  The reference's numbers on these inputs
+    (`assemble_scoring_matrices` + `get_hits` / `get_map_score` / `get_arhr_score` / `get_hr_score` / `get_mrr_score`)
+    are recorded in tests/golden/dropin_metrics.npz."""
+    from polara_amd import evaluation as ev
+    recs, hu, hi_, hf, n_items, topk, per = zero_feedback_inputs()
     assert (hf == 0).sum() > 10 and ((hf == 0) & (np.arange(len(hf)) % per < 2)).sum() > 3
-    holdout = pd.DataFrame({'userid': hu, 'itemid': hi_, 'rating': hf})
-    is_positive = None if switch_positive is None else (hf >= switch_positive)
-    penalty = 1 if switch_positive is None else 0
-    sd = rev.assemble_scoring_matrices(recs, holdout, 'userid', 'itemid', is_positive, feedback='rating')
-    want_hits = rev.get_hits(*sd, not_rated_penalty=penalty)
+    g = golden_metrics()
+    q = 'zero_%s/' % switch_positive
     got = dict((type(s).__name__, s) for s in ev.evaluate(recs, hu, hi_, hf, n_items, metric_type='all',
                                                             switch_positive=switch_positive, holdout_size=per))
-    for a, b in zip(got['Hits'], want_hits):
-        assert (a is None and b is None) or a == b, (got['Hits'], want_hits)
-    assert np.isclose(got['Ranking'].map, rev.get_map_score(sd[1], sd[3], topk), rtol=1e-12)
-    assert np.isclose(got['Ranking'].arhr, rev.get_arhr_score(sd[1]), rtol=1e-12)
+    same_hits(got['Hits'], g[q + 'hits'])
+    assert np.isclose(got['Ranking'].map, g[q + 'map'], rtol=1e-12)
+    assert np.isclose(got['Ranking'].arhr, g[q + 'arhr'], rtol=1e-12)
     single = dict((type(s).__name__, s) for s in ev.evaluate(recs, hu, hi_, hf, n_items, metric_type=['relevance', 'ranking'],
                                                                switch_positive=switch_positive, simple_rates=True))
-    assert np.isclose(single['Relevance'].hr, rev.get_hr_score(sd[1]).hr, rtol=1e-13)
-    assert np.isclose(single['Ranking'].mrr, rev.get_mrr_score(sd[1]), rtol=1e-12)
+    assert np.isclose(single['Relevance'].hr, g[q + 'hr'], rtol=1e-13)
+    assert np.isclose(single['Ranking'].mrr, g[q + 'mrr'], rtol=1e-12)

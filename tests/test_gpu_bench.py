@@ -1,11 +1,13 @@
-"""-m gpu: bench.py end to end as the driver runs it (1 GPU, default blocks incl. the CPU baseline and the adversarial
-catalogues), on a scaled-down matrix (the sub-blocks are full-size only): the LAST stdout line must be the compact JSON
-record — parseable, under 3 KB, with `roofline` and `cpu_baseline`, the lists of the sample identical to the CPU path's."""
+"""-m gpu: bench.py end to end (1 GPU), on a scaled-down matrix (the sub-blocks are full-size only).  With --full (incl. the
+CPU baseline and the adversarial catalogues) the LAST stdout line must be the compact JSON record — parseable, under 3 KB,
+with `roofline` and `cpu_baseline`, the lists of the sample identical to the CPU path's; a plain run prints the headline
+fields only, and --dump-outputs writes the lists of the last timed step."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -15,7 +17,8 @@ pytestmark = pytest.mark.gpu
 
 def test_default_bench_prints_one_compact_parseable_line(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--scale', '0.05'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--scale', '0.05',
+                        '--full', '--dump-outputs', str(tmp_path / 'out')],
                        capture_output=True, text=True, env=env, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     last = r.stdout.strip().splitlines()[-1]
@@ -37,3 +40,27 @@ def test_default_bench_prints_one_compact_parseable_line(tmp_path):
     cal = detail['warmup_calibration_ms_per_step']
     assert cal['python_launch'] > 0 and cal.get('recorded_replay') is not None and cal['recorded_replay'] > 0, cal
     assert d['config']['launch'] in ('python', 'hipGraph', 'python, passes on 2 streams') or d['config']['launch'].startswith('recorded calls'), d['config']['launch']
+    # the lists the CPU baseline was compared with are the dumped ones (external item ids, every user)
+    recs = np.load(str(tmp_path / 'out' / 'recommendations.npy'))
+    assert recs.dtype == np.float64 and recs.shape == (d['config']['n_users'], d['config']['topk'])
+
+
+def test_plain_bench_measures_the_headline_only_and_dumps_the_last_step(tmp_path):
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1', '--scale', '0.05',
+                        '--dump-outputs', str(tmp_path / 'out')],
+                       capture_output=True, text=True, env=env, timeout=900, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'build_s', 'config'):
+        assert key in d, key
+    assert d['steps'] == 4 and d['value'] > 0 and d['ms_per_step'] > 0 and d['unit'] == 'users/s' and d['dtype'] == 'bf16x3'
+    assert abs(d['value'] * d['ms_per_step'] * 1e-3 - d['config']['n_users']) < 1e-3 * d['config']['n_users']
+    for key in ('roofline', 'cpu_baseline', 'cold', 'roofline_build', 'roofline_foldin'):      # --full only
+        assert key not in d, key
+    assert d['ms_per_step_long_region'] is None and 'adversarial_users_per_s' not in d['config']
+    recs = np.load(str(tmp_path / 'out' / 'recommendations.npy'))
+    n_users, topk, n_items = d['config']['n_users'], d['config']['topk'], d['config']['n_items']
+    assert recs.dtype == np.float64 and recs.shape == (n_users, topk)
+    assert (recs >= 0).all() and (recs < n_items).all() and (recs == np.round(recs)).all()
+    assert all(len(set(row)) == topk for row in recs.astype(np.int64))
