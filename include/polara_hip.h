@@ -579,6 +579,50 @@ int pk_topk_rows_f64(void *stream, int64_t n_rows, int64_t n_cols, const double 
                      int64_t *out_idx_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Item-to-item and most-popular baselines (CooccurrenceModel / PopularityModel, models.py:649-666, 699-725; their
+ * scores go through downvote_seen_items / get_topk_elements, models.py:494-563, and lib/sparse.py:33-55).
+ * Selection everywhere uses ONE total order: class descending (candidate > seen item of the dense branch under
+ * filter_seen > not a candidate), score descending, item index ascending; non-candidates come out as -1.
+ * ------------------------------------------------------------------------------------------ */
+/* Limits and planning (host functions): the largest topk of pk_i2i_topk, the columns of a scoring workgroup, the fp64
+ * columns of a build workgroup, the leading dimension of C for n_items (n_items rounded up to a multiple of 8), the
+ * users scored per launch pair and the scratch pk_i2i_topk needs. */
+int32_t pk_i2i_max_topk(void);
+int32_t pk_i2i_window(void);
+int32_t pk_i2i_build_window(void);
+int64_t pk_i2i_ld(int64_t n_items);
+int64_t pk_i2i_chunk_users(int64_t n_users, int64_t n_items, int32_t topk);
+int64_t pk_i2i_topk_work_bytes(int64_t n_users, int64_t n_items, int32_t topk);
+/* C = A^T A with the diagonal set to 0 (models.py:710-713), dense fp64 [n_items x ldc] (ldc = pk_i2i_ld(n_items); the
+ * columns beyond n_items are written as 0).  A: CSR user -> items with sorted columns (indptr, indices, values) and its
+ * CSC image item -> users (t_*, pk_csr_transpose), values of kind val_kind in both.  Accumulated in fp64: exact whenever
+ * every product and partial sum is representable (integer or half-integer feedback). */
+int pk_i2i_build_f64(void *stream, int64_t n_users, int64_t n_items, const int64_t *indptr_dev, const int32_t *indices_dev,
+                     const void *values_dev, int val_kind, const int64_t *t_indptr_dev, const int32_t *t_indices_dev,
+                     const void *t_values_dev, double *C_dev, int64_t ldc);
+/* C32[e] = (float)C64[e] for e < n; *inexact_dev |= 1 (an int32 the caller zeroed) where (double)(float)c != c. */
+int pk_i2i_image_f32(void *stream, int64_t n, const double *C64_dev, float *C32_dev, int32_t *inexact_dev);
+/* Scores s_u = sum_i t_ui C[i, :] of the n_users rows of the test CSR (t_*: sorted columns, values of kind t_val_kind,
+ * zero values kept: they add nothing but count as seen) against C (c_kind = PK_VAL_F32 / PK_VAL_F64, leading dimension
+ * ldc = pk_i2i_ld(n_items)), accumulated in fp64, and the top-k of every row:
+ *   sparse = 0 (dense branch): every item is a candidate; filter_seen ranks the seen items after all unseen ones;
+ *   sparse = 1 (sparse branch): the candidates are the items with a nonzero score, minus the seen ones under filter_seen.
+ * out_idx_dev int64 [n_users x topk] (-1 = fewer candidates than topk), out_scores_dev fp64 [n_users x topk] or NULL.
+ * 1 <= topk <= pk_i2i_max_topk().  work >= pk_i2i_topk_work_bytes(n_users, n_items, topk). */
+int pk_i2i_topk(void *stream, int64_t n_users, int64_t n_items, const int64_t *t_indptr_dev, const int32_t *t_indices_dev,
+                const void *t_values_dev, int t_val_kind, const void *C_dev, int c_kind, int64_t ldc, int32_t topk,
+                int32_t filter_seen, int32_t sparse, int64_t *out_idx_dev, double *out_scores_dev, void *work_dev);
+/* The global order of the catalogue for PopularityModel: order_dev[p] = the item at position p by (score descending,
+ * item ascending) — one stable device radix sort.  work >= pk_popular_order_work_bytes(n_items). */
+int64_t pk_popular_order_work_bytes(int64_t n_items);
+int pk_popular_order(void *stream, int64_t n_items, const double *scores_dev, int32_t *order_dev, void *work_dev);
+/* The dense branch of PopularityModel (models.py:494-563 on repeated item scores): per test row the first topk items of
+ * the global order, with filter_seen the row's unseen items first and its seen items after them in the same order.
+ * 1 <= topk <= n_items <= 2^19 (the seen bitmap lives in LDS).  out_idx_dev int64 [n_users x topk]. */
+int pk_popular_topk(void *stream, int64_t n_users, int64_t n_items, const int64_t *t_indptr_dev, const int32_t *t_indices_dev,
+                    const int32_t *order_dev, int32_t topk, int32_t filter_seen, int64_t *out_idx_dev);
+
+/* ------------------------------------------------------------------------------------------
  * K5.  Sparse tensor-times-matrix (CoFFee / HOOI).
  * Replaces numba `dttm_seq` / `dttm_par` (lib/sparse.py:203-234) called from `ttm3d_seq`
  * (lib/tensor.py:7-19):  res[i0, j, k] += val * u[i1, j] * v[i2, k].

@@ -122,6 +122,18 @@ PROTOTYPES = {
     'pk_unique_count_i64': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     'pk_dense_scores_f64': (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64]),
     'pk_topk_rows_f64': (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i32, _vp]),
+    'pk_i2i_max_topk': (_i32, []),
+    'pk_i2i_window': (_i32, []),
+    'pk_i2i_build_window': (_i32, []),
+    'pk_i2i_ld': (_i64, [_i64]),
+    'pk_i2i_chunk_users': (_i64, [_i64, _i64, _i32]),
+    'pk_i2i_topk_work_bytes': (_i64, [_i64, _i64, _i32]),
+    'pk_i2i_build_f64': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _i64]),
+    'pk_i2i_image_f32': (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    'pk_i2i_topk': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'pk_popular_order_work_bytes': (_i64, [_i64]),
+    'pk_popular_order': (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    'pk_popular_topk': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _vp]),
     'pk_ctx_create': (C.c_int, [_i32, C.POINTER(_vp)]),
     'pk_ctx_destroy': (None, [_vp]),
     'pk_ctx_error': (C.c_char_p, [_vp]),

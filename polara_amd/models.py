@@ -1021,3 +1021,198 @@ class CoffeeModel(RecommenderModel):
         wt_flat = flatten_scores(w.T, self.flattener)
         coef = w.dot(wt_flat)
         return coef[np.asarray(test_data[2], dtype=np.intp)]
+
+
+class _DenseItemModel(RecommenderModel):
+    """Shared plumbing of the item-to-item and most-popular baselines: single process, items kept in the data-level
+    order (`_item_rank = None`: the tie key of every list is the item's column in the test matrix), lists selected on the
+    device by csrc/i2i.hip."""
+    _topk_limit = None
+
+    def _single_process(self):
+        if self.comm.world > 1:
+            raise NotImplementedError('%s: multi-process scoring is not supported (comm.world = %d)'
+                                      % (type(self).__name__, self.comm.world))
+
+    def _training_coo(self):
+        from .data import ArrayData
+        if getattr(type(self.data), 'to_coo', None) is ArrayData.to_coo:
+            rows, cols, val, shp = self.data.matrix_triplets(feedback_threshold=self.feedback_threshold)
+        else:
+            idx, val, shp = self.data.to_coo(tensor_mode=False, feedback_threshold=self.feedback_threshold)
+            rows, cols = idx[:, 0], idx[:, 1]
+        return rows, cols, val, shp
+
+    def get_recommendations(self):
+        from . import i2i
+        if self.verify_integrity:
+            self.verify_data_integrity()
+        self._single_process()
+        T, n_users, n_items = self._device_test_csr()
+        i2i.check_topk(self.topk, n_items, self._topk_limit)
+        recs = self.ops.to_host(self._score(T, n_items)) if n_users else np.empty((0, self.topk), dtype=np.int64)
+        self._recs_dev = None
+        return recs
+
+
+class CooccurrenceModel(_DenseItemModel):
+    """Item-to-item (models.py:699-725): C = A^T A with the diagonal set to 0, scores s_u = sum_i t_ui C[i, :].
+
+    C is built on the device and kept there as a dense image, fp32 when every entry survives the rounding (integer
+    co-occurrence counts below 2^24 do) and fp64 otherwise (`i2i_dtype`); scores are always accumulated in fp64.
+    `dense_output` picks the reference's branch (lib/sparse.py:33-55): True — every item is a candidate, seen items
+    ranked after all unseen ones under `filter_seen`; False — the candidates are the items with a nonzero score, minus
+    the seen ones under `filter_seen`, rows with fewer than `topk` of them padded with -1.  Ties go to the lower item
+    index.  INTEGRATION.md lists where this differs from the reference."""
+    _topk_limit = 1024
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.method = 'item-to-item'
+        self._implicit = False
+        self._dense_output = False
+        self._pad_const = -1
+        self._i2i = None
+        self.i2i_dtype = None
+        self.build_stats = {}
+
+    implicit = _setting('implicit', '_renew_model', 'feedback values replaced by their sign (training and test): a new model')
+    dense_output = _setting('dense_output', '_refresh_model', 'the dense or the sparse branch of the scoring: new lists')
+
+    def _renew_model(self):
+        super()._renew_model()
+        self._i2i = None                   # the dense image is large: freed at once, not when the next build replaces it
+
+    @property
+    def i2i_matrix(self):
+        """The device image of C [n_items x leading dim] (columns beyond n_items are 0)."""
+        return self._i2i
+
+    def build(self):
+        """models.py:705-713 on the device: CSR of the training matrix, its CSC image, C in LDS row windows, the
+        certified fp32 image."""
+        self._single_process()
+        ops = self.ops
+        self._i2i = None
+        rows, cols, val, shp = self._training_coo()
+        A = ops.csr_from_coo(rows, cols, val, shp)
+        if self.implicit:
+            A = A.with_columns(A.indices, torch.sign(A.values))
+        start = timer()
+        C, dtype = ops.i2i_build(A)
+        ops.synchronize()
+        self._track(start)
+        self._i2i, self.i2i_dtype = C, dtype
+        self.build_stats = {'n_items': int(shp[1]), 'nnz': int(A.nnz), 'i2i_dtype': dtype,
+                            'image_bytes': int(C.numel() * C.element_size())}
+
+    def _test_values(self, T):
+        return T.with_columns(T.indices, torch.sign(T.values)) if self.implicit else T
+
+    def _score(self, T, n_items, want_scores=False):
+        recs, scores = self.ops.i2i_topk(self._test_values(T), self._i2i, n_items, self.topk, self.filter_seen,
+                                         sparse=not self.dense_output, want_scores=want_scores)
+        return (recs, scores) if want_scores else recs
+
+    def recommend_with_scores(self):
+        """(lists, their fp64 scores) of every test user, both host arrays (pads: item -1, score 0)."""
+        if not self._is_ready:
+            self.build()
+        self._single_process()
+        from . import i2i
+        T, n_users, n_items = self._device_test_csr()
+        i2i.check_topk(self.topk, n_items, self._topk_limit)
+        recs, scores = self._score(T, n_items, want_scores=True)
+        return self.ops.to_host(recs), self.ops.to_host(scores)
+
+    def slice_recommendations(self, test_data, shape, start, stop, test_users=None):
+        """models.py:716-725: the scores of test users [start, stop) — a dense ndarray (dense_output) or a SciPy CSR with
+        explicit zeros removed — and the slice triplet.  The product runs on the device (pk_spmm_csr_ex over C's image)."""
+        from scipy.sparse import csr_matrix
+        stop = min(stop, shape[0])
+        users, items, fdbk = self._slice_test_data(test_data, start, stop)
+        vals = np.asarray(fdbk, dtype=np.float64)
+        if self.implicit:
+            vals = np.sign(vals)
+        indptr, indices, values = scoring.test_csr_from_triplet((users, items, vals), (stop - start, shape[1]), None)
+        T = self.ops.csr(indptr, indices, values, (stop - start, shape[1]))
+        scores = self.ops.to_host(self.ops.spmm(T, self._i2i))[:, :shape[1]]
+        scores = np.ascontiguousarray(scores)
+        if not self.dense_output:
+            scores = csr_matrix(scores)
+            scores.eliminate_zeros()
+        return scores, (users, items, fdbk)
+
+    def downvote_seen_items(self, recs, idx_seen):
+        """models.py:494-519.  A SciPy matrix (sparse branch): the seen entries become 0 and leave the matrix, IN PLACE
+        (the reference's `recs -= ...` rebinds its local name and leaves the caller's matrix as it was); dense: the base
+        class's dense branch."""
+        if not hasattr(recs, 'tocsr'):
+            return super().downvote_seen_items(recs, idx_seen)
+        from scipy.sparse import coo_matrix
+        users, items = (np.asarray(x, dtype=np.int64) for x in idx_seen[:2])
+        seen = coo_matrix((np.ones(len(users), dtype=bool), (users, items)), shape=recs.shape)
+        new = (recs - recs.multiply(seen)).tocsr()
+        new.eliminate_zeros()
+        recs.data, recs.indices, recs.indptr = new.data, new.indices, new.indptr
+
+    def get_topk_elements(self, scores, topk=None):
+        """models.py:522-563.  A SciPy CSR (sparse branch): per row its stored entries by score descending, item
+        ascending, padded with -1; dense: the base class."""
+        if not hasattr(scores, 'tocsr'):
+            return super().get_topk_elements(scores, topk)
+        topk = self.topk if topk is None else int(topk)
+        s = scores.tocsr()
+        s.sum_duplicates()
+        out = np.full((s.shape[0], topk), self._pad_const, dtype=np.int64)
+        for r in range(s.shape[0]):
+            lo, hi = s.indptr[r], s.indptr[r + 1]
+            data, cols = s.data[lo:hi], s.indices[lo:hi]
+            keep = data != 0
+            data, cols = data[keep], cols[keep]
+            best = np.lexsort((cols, -data))[:topk]
+            out[r, :len(best)] = cols[best]
+        return out
+
+
+class PopularityModel(_DenseItemModel):
+    """Most popular (models.py:649-666): the score of an item is its number of training entries, or the sum of their
+    feedback with `by_feedback_value`; every user gets the catalogue in that order (score descending, item ascending),
+    seen items after all unseen ones under `filter_seen` (the dense branch of models.py:494-563).  Items without
+    training entries score 0."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.method = 'MP'
+        self._by_feedback_value = False
+        self.item_scores = None
+        self._order = None
+
+    by_feedback_value = _setting('by_feedback_value', '_renew_model', 'scores are feedback sums, not counts: a new model')
+
+    def build(self):
+        """models.py:656-663: per-item counts (or feedback sums) over the training entries, then one device sort of
+        the catalogue."""
+        self._single_process()
+        ops = self.ops
+        idx, val, shp = self.data.to_coo(tensor_mode=False)
+        start = timer()
+        cols = np.asarray(idx[:, 1], dtype=np.int64)
+        if self.by_feedback_value:
+            scores = np.bincount(cols, weights=np.asarray(val, dtype=np.float64), minlength=shp[1])
+        else:
+            scores = np.bincount(cols, minlength=shp[1])
+        self._order = ops.popular_order(ops.to_device(scores.astype(np.float64)))
+        ops.synchronize()
+        self._track(start)
+        self.item_scores = scores
+
+    def _score(self, T, n_items):
+        return self.ops.popular_topk(T, self._order, self.topk, self.filter_seen)
+
+    def slice_recommendations(self, test_data, shape, start, stop, test_users=None):
+        """models.py:664-668: the item scores repeated for every user of the slice."""
+        stop = min(stop, shape[0])
+        slice_data = self._slice_test_data(test_data, start, stop)
+        scores = np.repeat(np.asarray(self.item_scores, dtype=np.float64)[None, :], stop - start, axis=0)
+        return scores, slice_data

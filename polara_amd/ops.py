@@ -1540,6 +1540,66 @@ class HipOps:
                                              int(topk), _ptr(out)), 'pk_topk_rows_f64')
         return out
 
+    # ---- item-to-item / most popular (csrc/i2i.hip) ------------------------------------------------------------
+    def i2i_build(self, A):
+        """C = A^T A with the diagonal set to 0 as a dense device image [n_items x i2i.leading_dim(n_items)]
+        (pk_i2i_build_f64 on A's CSR and its CSC image), then certified: fp32 when every entry survives the rounding
+        (pk_i2i_image_f32), else fp64.  Raises MemoryError before allocating when the fp64 image would take more than
+        half of the free device memory.  Returns (C, 'float32' | 'float64')."""
+        from . import i2i
+        n_users, n_items = A.shape
+        ld = i2i.leading_dim(n_items)
+        i2i.check_build_memory(n_items, torch.cuda.mem_get_info(self.device)[0])
+        T = A.T
+        C64 = torch.empty(n_items, ld, dtype=torch.float64, device=self.device)
+        with self._timed('i2i_build', (n_users, n_items, A.nnz)):
+            _lib.check(self.lib.pk_i2i_build_f64(self.stream(), n_users, n_items, _ptr(A.indptr), _ptr(A.indices),
+                                                 _ptr(A.values), A.val_kind, _ptr(T.indptr), _ptr(T.indices),
+                                                 _ptr(T.values), _ptr(C64), ld), 'pk_i2i_build_f64')
+        C32 = torch.empty(n_items, ld, dtype=torch.float32, device=self.device)
+        flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.pk_i2i_image_f32(self.stream(), C64.numel(), _ptr(C64), _ptr(C32), _ptr(flag)),
+                   'pk_i2i_image_f32')
+        if int(flag.item()) == 0:
+            return C32, 'float32'
+        return C64, 'float64'
+
+    def i2i_topk(self, T, C, n_items, topk, filter_seen, sparse, want_scores=False):
+        """int64 [n_users x topk] (and fp64 scores or None): the top-k of s_u = T[u] C per row of the device CSR T
+        (pk_i2i_topk: fused masking, -1 where a row has fewer candidates).  sparse: the sparse branch's candidates."""
+        n_users = int(T.shape[0])
+        topk = int(topk)
+        out = torch.empty(n_users, topk, dtype=torch.int64, device=self.device)
+        scores = torch.empty(n_users, topk, dtype=torch.float64, device=self.device) if want_scores else None
+        c_kind = _lib.PK_VAL_F32 if C.dtype == torch.float32 else _lib.PK_VAL_F64
+        work = self._work(self.lib.pk_i2i_topk_work_bytes(n_users, int(n_items), topk))
+        with self._timed('i2i_topk', (n_users, int(n_items), T.nnz, topk)):
+            _lib.check(self.lib.pk_i2i_topk(self.stream(), n_users, int(n_items), _ptr(T.indptr), _ptr(T.indices),
+                                            _ptr(T.values), T.val_kind, _ptr(C), c_kind, C.stride(0), topk,
+                                            1 if filter_seen else 0, 1 if sparse else 0, _ptr(out), _ptr(scores),
+                                            _ptr(work)), 'pk_i2i_topk')
+        return out, scores
+
+    def popular_order(self, scores):
+        """int32 [n_items] device: the items by (score descending, item ascending) (pk_popular_order)."""
+        scores = scores.to(self.device, torch.float64).contiguous()
+        n = int(scores.numel())
+        order = torch.empty(n, dtype=torch.int32, device=self.device)
+        work = self._work(self.lib.pk_popular_order_work_bytes(n))
+        _lib.check(self.lib.pk_popular_order(self.stream(), n, _ptr(scores), _ptr(order), _ptr(work)), 'pk_popular_order')
+        return order
+
+    def popular_topk(self, T, order, topk, filter_seen):
+        """int64 [n_users x topk]: per row of the device CSR T the first topk items of `order`, unseen ones first under
+        filter_seen (pk_popular_topk)."""
+        n_users, n_items = (int(x) for x in T.shape)
+        out = torch.empty(n_users, int(topk), dtype=torch.int64, device=self.device)
+        with self._timed('popular_topk', (n_users, n_items, T.nnz, int(topk))):
+            _lib.check(self.lib.pk_popular_topk(self.stream(), n_users, n_items, _ptr(T.indptr), _ptr(T.indices),
+                                                _ptr(order), int(topk), 1 if filter_seen else 0, _ptr(out)),
+                       'pk_popular_topk')
+        return out
+
     def dense_scores(self, V, E):
         n_rows, K = E.shape
         n_items = V.shape[0]
