@@ -623,6 +623,32 @@ int pk_popular_topk(void *stream, int64_t n_users, int64_t n_items, const int64_
                     const int32_t *order_dev, int32_t topk, int32_t filter_seen, int64_t *out_idx_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * HybridSVD (hybrid/models.py:228-397): a dense Cholesky factor of the item-similarity matrix K = S + beta I and its
+ * products.  Every image of K / L is fp64, row-major, with pk_hybrid_ld(n) rows and a leading dimension ld that is a
+ * multiple of 64 and at least pk_hybrid_ld(n) (n rounded up to whole 64 x 64 tiles); only the lower triangle is read.
+ * ------------------------------------------------------------------------------------------ */
+/* Planning (host functions): the rows of an image (n rounded up to a multiple of 64), the largest nc of pk_trmm_f64
+ * and the scratch it needs for n rows and nc columns (0: none). */
+int64_t pk_hybrid_ld(int64_t n);
+int32_t pk_hybrid_max_nc(void);
+int64_t pk_trmm_work_bytes(int64_t n, int32_t nc);
+/* K = S + beta I in the internal item order: the image is cleared, entry (i, j) of the CSR of S (external ids, int64
+ * indptr / indices, no duplicates) is written at (rank[i], rank[j]) when rank[j] <= rank[i], then beta is added on the
+ * diagonal. */
+int pk_hybrid_densify_f64(void *stream, int64_t n, const int64_t *indptr_dev, const int64_t *indices_dev,
+                          const double *data_dev, const int64_t *rank_dev, double beta, double *K_dev, int64_t ld);
+/* In-place lower Cholesky K = L L^T of the n x n matrix in A (lower triangle read; on return the strict upper triangle
+ * is 0 and the rows / columns of the padding hold the identity).  *info_dev (int32) = -1 on success, else the first
+ * column whose pivot is <= 0 or not finite; the work after that column is skipped.  Deterministic. */
+int pk_chol_f64(void *stream, int64_t n, double *A_dev, int64_t ld, int32_t *info_dev);
+/* Y = L X (trans = 0) or Y = L^T X (trans = 1) for X [n x nc] (1 <= nc <= pk_hybrid_max_nc()), L the factor of
+ * pk_chol_f64.  work >= pk_trmm_work_bytes(n, nc); the partial sums of a row are added in a fixed order. */
+int pk_trmm_f64(void *stream, int32_t trans, int64_t n, int32_t nc, const double *L_dev, int64_t ld, const double *X_dev,
+                int64_t ldx, double *Y_dev, int64_t ldy, void *work_dev);
+/* B <- L^-T B in place, B [n x r] with pk_hybrid_ld(n) rows allocated (the rows beyond n are set to 0). */
+int pk_trsm_f64(void *stream, int64_t n, int32_t r, const double *L_dev, int64_t ld, double *B_dev, int64_t ldb);
+
+/* ------------------------------------------------------------------------------------------
  * K5.  Sparse tensor-times-matrix (CoFFee / HOOI).
  * Replaces numba `dttm_seq` / `dttm_par` (lib/sparse.py:203-234) called from `ttm3d_seq`
  * (lib/tensor.py:7-19):  res[i0, j, k] += val * u[i1, j] * v[i2, k].

@@ -134,6 +134,13 @@ PROTOTYPES = {
     'pk_popular_order_work_bytes': (_i64, [_i64]),
     'pk_popular_order': (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     'pk_popular_topk': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _vp]),
+    'pk_hybrid_ld': (_i64, [_i64]),
+    'pk_hybrid_max_nc': (_i32, []),
+    'pk_trmm_work_bytes': (_i64, [_i64, _i32]),
+    'pk_hybrid_densify_f64': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _i64]),
+    'pk_chol_f64': (C.c_int, [_vp, _i64, _vp, _i64, _vp]),
+    'pk_trmm_f64': (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    'pk_trsm_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64]),
     'pk_ctx_create': (C.c_int, [_i32, C.POINTER(_vp)]),
     'pk_ctx_destroy': (None, [_vp]),
     'pk_ctx_error': (C.c_char_p, [_vp]),

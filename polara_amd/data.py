@@ -276,3 +276,63 @@ class ShardedArrayData(ArrayData):
         if self._fixed_levels is not None:
             return self._fixed_levels
         return super()._levels()
+
+
+class SimilarityArrayData(ArrayData):
+    """ArrayData with side relations: the counterpart of Polara's `SimilarityDataModel` (SideRelationsMixin +
+    IdentityDiagonalMixin, hybrid/data.py:8-69) for HybridSVD.
+
+    relations_matrices: {entity field name: square SciPy sparse matrix or ndarray, or None}; relations_indices: {entity
+    field name: the entity id of every row of that matrix, or None when row r IS entity r}.  `get_relations_matrix(entity)`
+    returns the matrix in the data's id order with its diagonal set to 1 (a copy: the caller's matrix is not written), built
+    on first use and dropped on a data-change event."""
+
+    def __init__(self, training, *args, relations_matrices, relations_indices, **kwargs):
+        super().__init__(training, *args, **kwargs)
+        entities = (self.fields.userid, self.fields.itemid)
+        self._rel_mat = {e: m for e, m in relations_matrices.items() if e in entities}
+        self._rel_idx = {e: (None if idx is None else np.asarray(idx)) for e, idx in relations_indices.items() if e in entities}
+        self._relations = dict.fromkeys(entities)
+        self.subscribe(self.on_change_event, self._clean_relations)
+
+    def _clean_relations(self):
+        self._relations = dict.fromkeys(self._relations.keys())
+
+    @property
+    def item_relations(self):
+        return self.get_relations_matrix(self.fields.itemid)
+
+    @property
+    def user_relations(self):
+        return self.get_relations_matrix(self.fields.userid)
+
+    def get_relations_matrix(self, entity):
+        if self._relations.get(entity, None) is None:
+            self._update_relations(entity)
+        return self._relations[entity]
+
+    def _update_relations(self, entity):
+        from scipy.sparse import issparse
+        mat = self._rel_mat.get(entity, None)
+        if mat is None:
+            self._relations[entity] = None
+            return
+        n = self.n_users if entity == self.fields.userid else self.n_items
+        idx = self._rel_idx.get(entity, None)
+        if idx is None:
+            if mat.shape[0] != n:
+                raise ValueError('%s relations: %d rows for %d entities' % (entity, mat.shape[0], n))
+            rows = np.arange(n)
+        else:
+            pos = {int(e): p for p, e in enumerate(idx)}          # entity id -> row of the relations matrix
+            missing = [e for e in range(n) if e not in pos]
+            if missing:
+                raise ValueError('%s relations: no row for %d entities (first: %d)' % (entity, len(missing), missing[0]))
+            rows = np.fromiter((pos[e] for e in range(n)), dtype=np.int64, count=n)
+        if issparse(mat):
+            rel = mat.tocsr()[:, rows][rows, :].tocsr()
+            rel.setdiag(1)
+        else:
+            rel = np.array(np.asarray(mat)[np.ix_(rows, rows)], dtype=np.float64)
+            np.fill_diagonal(rel, 1)
+        self._relations[entity] = rel

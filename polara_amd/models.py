@@ -1216,3 +1216,253 @@ class PopularityModel(_DenseItemModel):
         slice_data = self._slice_test_data(test_data, start, stop)
         scores = np.repeat(np.asarray(self.item_scores, dtype=np.float64)[None, :], stop - start, axis=0)
         return scores, slice_data
+
+
+class DeviceCholeskyFactor:
+    """The Cholesky factor of K = S + beta I (the item similarity of HybridSVD) kept on the device: the square root
+    R = P^T L P with L the dense lower factor of K in the factor's internal item order (`perm`: external id -> internal
+    position, P the matching permutation), so R R^T = K and both sides of R are indexed by external item ids.  The
+    counterpart of polara/lib/cholesky.py's CholeskyFactor: `.dot(v)` = R v, `.T.dot(v)` = R^T v, `.T.solve(v)` = R^-T v,
+    `.L` a dense host copy of L made on demand."""
+
+    def __init__(self, ops, image, n, perm, beta, _transposed=False):
+        self.ops, self.image, self.n, self.beta = ops, image, int(n), float(beta)
+        self.perm = np.asarray(perm, dtype=np.int64)
+        self.inv = np.empty_like(self.perm)
+        self.inv[self.perm] = np.arange(len(self.perm), dtype=np.int64)
+        self._transposed = _transposed
+        self._L = None
+
+    @property
+    def T(self):
+        t = DeviceCholeskyFactor.__new__(DeviceCholeskyFactor)
+        t.__dict__.update(self.__dict__)
+        t._transposed = not self._transposed
+        return t
+
+    @property
+    def L(self):
+        if self._L is None:
+            self._L = self.ops.to_host(self.image[:self.n, :self.n])
+        return self._L
+
+    def _internal(self, v):
+        v = np.asarray(v, dtype=np.float64)
+        col = v.ndim == 1
+        v = v.reshape(self.n, -1)
+        return self.ops.to_device(np.ascontiguousarray(v[self.inv])), col
+
+    def _external(self, y, col):
+        y = self.ops.to_host(y)[self.perm]
+        return y[:, 0] if col else y
+
+    def dot(self, v):
+        x, col = self._internal(v)
+        return self._external(self.ops.trmm(self.image, self.n, x, trans=self._transposed), col)
+
+    def solve(self, v):
+        if not self._transposed:
+            raise NotImplementedError('only R^-T v (factor.T.solve) is provided, like the reference')
+        x, col = self._internal(v)
+        return self._external(self.ops.trsm(self.image, self.n, x), col)
+
+
+class HybridSVD(SVDModel):
+    """HybridSVD (hybrid/models.py:228-397): PureSVD of A R with R R^T = K = S + beta I, S the item relations (unit
+    diagonal), beta = (1 - w) / w, w = `features_weight`; scores T vr vl^T with vl = R^-T W, vr = R W (W: the leading
+    right singular vectors).  R comes from a dense Cholesky factor of K built on the device (csrc/hybrid.hip) in the
+    device's internal item order — any square root gives the same singular values, projectors (up to column signs),
+    scores and lists.  The product A R runs factored (operator.CholeskyProduct): one triangular product and one SpMM per
+    Gramian half-step.  Item-side relations only; single process; the dense factor must fit in half of the free device
+    memory (hybrid.check_factor_memory)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.method = 'HybridSVD'
+        self.precompute_auxiliary_matrix = False   # accepted: the factored operator always runs (same result)
+        self._features_weight = 0.5
+        self._chol = None
+        self._fold_src = None
+        self._similarity = None     # (the data's relations matrix, its checked canonical CSR copy)
+        self.data.subscribe(self.data.on_change_event, self._clean_cholesky)
+
+    def _clean_cholesky(self):
+        self._chol = None
+        self._similarity = None
+
+    @property
+    def features_weight(self):
+        return self._features_weight
+
+    @features_weight.setter
+    def features_weight(self, new_value):
+        if new_value != self._features_weight:
+            from . import hybrid
+            hybrid.beta_of(new_value)
+            self._features_weight = new_value
+            if self._chol is not None:             # re-factored at once, in the same item order (hybrid/models.py:258-263)
+                self._chol = self._factorize(self._chol.perm)
+            self._renew_model()
+
+    # ---- the Cholesky factor ----------------------------------------------------------------------------------------
+    def _relations(self, entity):
+        get = getattr(self.data, 'get_relations_matrix', None)
+        if get is None:
+            return None
+        try:
+            return get(entity)
+        except KeyError:
+            return None
+
+    def _item_similarity(self):
+        from scipy.sparse import csr_matrix, issparse
+        userid, itemid = self.data.fields.userid, self.data.fields.itemid
+        if self._relations(userid) is not None:
+            raise NotImplementedError('HybridSVD with user-side relations: a dense n_users x n_users Cholesky factor would '
+                                      'be needed (item-side relations only)')
+        src = self._relations(itemid)
+        if src is None:
+            raise ValueError('HybridSVD: the data provides no item relations (for PureSVD use SVDModel)')
+        if self._similarity is not None and self._similarity[0] is src:
+            return self._similarity[1]              # the data object hands out the same matrix until a data change
+        S = (src if issparse(src) else csr_matrix(np.asarray(src, dtype=np.float64))).tocsr().astype(np.float64)
+        if S.shape[0] != S.shape[1]:
+            raise ValueError('HybridSVD: item relations of shape %s are not square' % (S.shape,))
+        S.sum_duplicates()                          # canonical: sorted indices, no duplicates (what densify expects)
+        T = S.T.tocsr()
+        T.sum_duplicates()
+        if np.array_equal(S.indptr, T.indptr) and np.array_equal(S.indices, T.indices):
+            dev = float(np.abs(S.data - T.data).max()) if S.nnz else 0.0      # same pattern: compare the values in place
+        else:
+            diff = abs(S - T)
+            dev = float(diff.max()) if diff.nnz else 0.0
+        scale = max(1.0, float(np.abs(S.data).max()) if S.nnz else 1.0)
+        if dev > 1e-10 * scale:
+            raise ValueError('HybridSVD: the item relations matrix is not symmetric (max |S - S^T| = %.3e)' % dev)
+        self._similarity = (src, S)
+        return S
+
+    def _factorize(self, perm):
+        from . import hybrid
+        ops = self.ops
+        S = self._item_similarity()
+        beta = hybrid.beta_of(self.features_weight)
+        n = S.shape[0]
+        if n != len(perm):
+            raise ValueError('HybridSVD: item relations of shape %s for %d items' % (S.shape, len(perm)))
+        K = ops.hybrid_densify(S, perm, beta)
+        try:
+            ops.chol(K, n)
+        except np.linalg.LinAlgError as exc:
+            col = getattr(exc, 'column', None)
+            inv = np.empty_like(np.asarray(perm, dtype=np.int64))
+            inv[np.asarray(perm, dtype=np.int64)] = np.arange(n)
+            err = np.linalg.LinAlgError('HybridSVD: K = S + %g I is not positive definite: the pivot of column %d of the '
+                                        'factor (item %d) is not positive' % (beta, col, int(inv[col])))
+            err.column, err.item = col, int(inv[col])
+            raise err from None
+        return DeviceCholeskyFactor(ops, K, n, perm, beta)
+
+    def get_cholesky_factor(self, entity):
+        if entity != self.data.fields.itemid:
+            return None
+        if self._chol is None:
+            n_items = self.data.get_test_shape(tensor_mode=False)[1]
+            perm = self._item_rank if self._item_rank is not None else np.arange(n_items, dtype=np.int64)
+            self._chol = self._factorize(perm)
+        return self._chol
+
+    @property
+    def item_cholesky_factor(self):
+        return self.get_cholesky_factor(self.data.fields.itemid)
+
+    @property
+    def user_cholesky_factor(self):
+        return None
+
+    # ---- projectors ------------------------------------------------------------------------------------------------
+    def get_item_projector(self):
+        itemid = self.data.fields.itemid
+        return (self.factors.get(f'{itemid}_projector_left', None), self.factors.get(f'{itemid}_projector_right', None))
+
+    def round_item_projector(self, rank):
+        vl, vr = self.get_item_projector()
+        if vl is not None and rank < vl.shape[1]:
+            itemid = self.data.fields.itemid
+            self.factors = dict(self.factors)
+            self.factors[f'{itemid}_projector_left'] = vl[:, :rank]
+            self.factors[f'{itemid}_projector_right'] = vr[:, :rank]
+
+    def _check_reduced_rank(self, rank):
+        super()._check_reduced_rank(rank)
+        self.round_item_projector(rank)
+
+    def _item_factors_device(self):
+        """FactorImage(vl, fold=vr) in the serving order; the cached image belongs to ONE pair of projector arrays (the
+        rank-sweep pipelines swap `factors` behind the model's back)."""
+        vl, vr = self.get_item_projector()
+        if vl is None:
+            raise ValueError('%s: no item projectors (build the model first)' % self.method)
+        if self._factor_image is None or self._factor_src is not vl or self._fold_src is not vr:
+            inv = self._item_inv if self._item_inv is not None else np.arange(vl.shape[0])
+            self._factor_image = scoring.FactorImage(self.ops, self.ops.to_device(np.ascontiguousarray(vl[inv])),
+                                                     fold=self.ops.to_device(np.ascontiguousarray(vr[inv])))
+            self._factor_src, self._fold_src = vl, vr
+        return self._factor_image
+
+    # ---- build -------------------------------------------------------------------------------------------------------
+    def build(self, return_factors='vh'):
+        """hybrid/models.py:338-372 on the device: K densified and factored (pk_hybrid_densify_f64, pk_chol_f64), the
+        leading singular triplets of A L by the block eigensolver on the factored operator, vl = L^-T W (pk_trsm_f64),
+        vr = L W (pk_trmm_f64)."""
+        if self.comm.world > 1:
+            raise NotImplementedError('HybridSVD: multi-process builds are not supported (comm.world = %d)' % self.comm.world)
+        from .operator import CholeskyProduct
+        ops = self.ops
+        userid, itemid = self.data.fields.userid, self.data.fields.itemid
+        self._item_similarity()                     # the checks first (no relations, user relations, asymmetry)
+        start = timer()
+        A = self._training_device_csr()             # sets the internal (popularity) item order
+        chol = self._chol
+        if chol is None or not np.array_equal(chol.perm, self._item_rank):
+            chol = self._chol = self._factorize(np.array(self._item_rank, dtype=np.int64))
+        n_items = A.shape[1]
+        op = CholeskyProduct(ops, A, chol.image)
+        want_u = return_factors in (True, 'u')
+        U, sigma, W, stats = svd_topk(ops, op, self.rank, block=self.svd_block, tol=self.svd_tol,
+                                      max_outer=self.svd_max_outer, seed=self.svd_seed, want_u=want_u, verbose=False)
+        vl = ops.trsm(chol.image, n_items, W)
+        vr = ops.trmm(chol.image, n_items, W)
+        ops.synchronize()
+        self._track(start)
+        self.build_stats = stats
+        if not stats['converged']:
+            msg = ('%s: the block eigensolver did not converge in %d outer iterations (%d Gramian steps): worst '
+                   'relative residual %.2e of the leading %d pairs, tolerance %.1e' %
+                   (self.method, stats['outer'], stats['gramian_steps'], stats['final_rel_residual'], self.rank,
+                    self.svd_tol))
+            if self.svd_on_no_convergence == 'raise':
+                raise NoConvergence(msg, sigma=ops.to_host(sigma), V=ops.to_host(W), stats=stats)
+            import warnings
+            warnings.warn(msg, RuntimeWarning)
+        rank_build = self._item_rank
+        vl_h, vr_h = ops.to_host(vl), ops.to_host(vr)
+        factors = {userid: ops.to_host(U) if want_u else None,
+                   itemid: np.ascontiguousarray(ops.to_host(W)[rank_build]) if return_factors in (True, 'vh') else None,
+                   'singular_values': ops.to_host(sigma),
+                   f'{itemid}_projector_left': np.ascontiguousarray(vl_h[rank_build]),
+                   f'{itemid}_projector_right': np.ascontiguousarray(vr_h[rank_build])}
+        # serving order: DESCENDING vl ROW NORM (the pruning bound of the candidate sweep reads the rows of vl); vr follows
+        by_norm = np.argsort(-np.linalg.norm(vl_h, axis=1), kind='stable')
+        self._item_inv = np.ascontiguousarray(self._item_inv[by_norm])
+        self._item_rank = np.empty_like(self._item_inv)
+        self._item_rank[self._item_inv] = np.arange(len(self._item_inv), dtype=self._item_inv.dtype)
+        self.factors = factors
+        self._factor_image = scoring.FactorImage(ops, ops.to_device(np.ascontiguousarray(vl_h[by_norm])),
+                                                 fold=ops.to_device(np.ascontiguousarray(vr_h[by_norm])))
+        self._factor_src = factors[f'{itemid}_projector_left']
+        self._fold_src = factors[f'{itemid}_projector_right']
+
+
+class ScaledHybridSVD(ScaledMatrixMixin, HybridSVD):
+    """hybrid/models.py:397: HybridSVD of the scaled training matrix (ScaledMatrixMixin)."""

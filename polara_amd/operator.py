@@ -1,12 +1,14 @@
 """`SVDModel.build(operator=...)` (models.py:835-844): the reference hands `svds` an operator instead of the
 training matrix — HybridSVD passes  L_K^T A L_S  either multiplied out as one sparse matrix
 (`precompute_auxiliary_matrix`, hybrid/models.py:357-363) or as a SciPy LinearOperator chaining the three
-products (hybrid/models.py:364-381).  Three forms are accepted here:
+products (hybrid/models.py:364-381).  The forms accepted here:
 
   * a SciPy sparse matrix              -> a DeviceCSR: the whole build runs on the device like a plain one;
   * `SparseProduct(F_0, ..., F_m)`     -> the factors live on the device as CSR matrices and the operator is
     the chain of their SpMMs (the device form of HybridSVD's matvec/rmatvec closures: pass the sparse
     Cholesky factors themselves instead of wrapping them in host closures);
+  * `CholeskyProduct(A, L)`            -> HybridSVD's A L with L a dense device Cholesky factor (models.HybridSVD): one
+    triangular product and one SpMM per product;
   * any other LinearOperator           -> host code by definition: its products run on the host, the block
     eigensolver around them (Gram matrices, Jacobi eigh, tall-skinny GEMMs, Chebyshev recurrence) on the device.
 
@@ -67,6 +69,38 @@ class DeviceChain:
         for f in reversed(self.factors[1:]):
             X = self.ops.spmm(f, X)
         return self.ops.spmm(self.factors[0], X, out)
+
+
+class CholeskyProduct:
+    """M = A L with A a device matrix [n_users x n_items] and L the dense lower Cholesky factor of the item similarity
+    (an image of ops.chol, n_items rows in the same internal item order as A's columns): the device form of HybridSVD's
+    matvec / rmatvec closures (hybrid/models.py:364-381).  `apply(X)` = A (L X): one triangular product, one SpMM;
+    `T.apply(Y)` = L^T (A^T Y) through A's user-blocked transpose.  Single process."""
+
+    def __init__(self, ops, A, L, _transposed=False):
+        self.ops = ops
+        self.A = A
+        self.L = L
+        self.n = int(A.shape[1])
+        self._transposed = _transposed
+        self.shape = (int(A.shape[1]), int(A.shape[0])) if _transposed else (int(A.shape[0]), int(A.shape[1]))
+        # entries a product touches: the training matrix and the triangle (the solver's cost model)
+        self.nnz = int(A.nnz) + self.n * (self.n + 1) // 2
+        self._T = None
+
+    @property
+    def T(self):
+        if self._T is None:
+            self._T = CholeskyProduct(self.ops, self.A, self.L, _transposed=not self._transposed)
+            self._T._T = self
+        return self._T
+
+    def apply(self, X, out=None):
+        ops = self.ops
+        if not self._transposed:
+            return ops.spmm(self.A, ops.trmm(self.L, self.n, X), out)
+        At = self.A.transpose_operator() if hasattr(self.A, 'transpose_operator') else self.A.T
+        return ops.trmm(self.L, self.n, ops.spmm(At, X), trans=True, out=out)
 
 
 class HostOperator:

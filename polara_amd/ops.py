@@ -1600,6 +1600,85 @@ class HipOps:
                        'pk_popular_topk')
         return out
 
+    # ---- HybridSVD: dense Cholesky factor of the item similarity (csrc/hybrid.hip) ------------------------------------
+    def hybrid_densify(self, S, rank, beta):
+        """The image [ld x ld] of K = S + beta I in the internal item order (pk_hybrid_densify_f64): S a SciPy sparse
+        matrix in external ids, rank[external id] = internal position.  Raises MemoryError before allocating when the fp64
+        image would take more than half of the free device memory."""
+        from . import hybrid
+        n = int(S.shape[0])
+        hybrid.check_factor_memory(n, torch.cuda.mem_get_info(self.device)[0])
+        S = S.tocsr()
+        if not S.has_canonical_format:
+            S = S.copy()
+            S.sum_duplicates()
+        ld = hybrid.leading_dim(n)
+        K = torch.empty(ld, ld, dtype=torch.float64, device=self.device)
+        # the index arrays go up as they lie (int32 from SciPy) and are widened on the device
+        indptr = self.to_device(S.indptr).to(torch.int64)
+        indices = self.to_device(S.indices).to(torch.int64)
+        data = self.to_device(np.asarray(S.data, dtype=np.float64))
+        rank_dev = self.to_device(np.asarray(rank, dtype=np.int64))
+        with self._timed('hybrid_densify', (n, int(S.nnz))):
+            _lib.check(self.lib.pk_hybrid_densify_f64(self.stream(), n, _ptr(indptr), _ptr(indices), _ptr(data), _ptr(rank_dev),
+                                                      float(beta), _ptr(K), ld), 'pk_hybrid_densify_f64')
+        return K
+
+    def chol_image(self, K):
+        """A padded image [ld x ld] holding the dense symmetric n x n matrix K (host or device; its lower triangle is what
+        the factorisation reads), ready for `chol`."""
+        from . import hybrid
+        K = torch.as_tensor(np.ascontiguousarray(K) if isinstance(K, np.ndarray) else K)
+        n = int(K.shape[0])
+        ld = hybrid.leading_dim(n)
+        img = torch.zeros(ld, ld, dtype=torch.float64, device=self.device)
+        img[:n, :n] = K.to(device=self.device, dtype=torch.float64)
+        return img
+
+    def chol(self, A, n):
+        """In-place lower Cholesky of the n x n matrix in the image A (pk_chol_f64); one host read of the verdict at the end.
+        Raises numpy.linalg.LinAlgError naming the first column whose pivot is not positive (or not finite)."""
+        info = torch.empty(1, dtype=torch.int32, device=self.device)
+        with self._timed('chol', (int(n),)):
+            _lib.check(self.lib.pk_chol_f64(self.stream(), int(n), _ptr(A), A.stride(0), _ptr(info)), 'pk_chol_f64')
+        col = int(info.item())
+        if col >= 0:
+            err = np.linalg.LinAlgError('Cholesky factorisation: the matrix is not positive definite (the pivot of column '
+                                        '%d is not positive)' % col)
+            err.column = col
+            raise err
+        return A
+
+    def trmm(self, L, n, X, trans=False, out=None):
+        """Y = L X (trans False) or L^T X for X [n x nc] device, L the image of `chol` (pk_trmm_f64, in blocks of at most
+        64 columns).  `out`: an [n x nc] destination (its rows may be strided)."""
+        from . import hybrid
+        n = int(n)
+        if X.stride(-1) != 1:
+            X = X.contiguous()
+        nc = int(X.shape[1])
+        Y = out if out is not None else torch.empty(n, nc, dtype=torch.float64, device=self.device)
+        if Y.stride(-1) != 1:
+            raise ValueError('trmm: the destination must have unit column stride')
+        work = self._work(self.lib.pk_trmm_work_bytes(n, min(nc, hybrid.MAX_NC)))
+        for c0, c1 in hybrid.column_blocks(nc):
+            with self._timed('trmm', (n, c1 - c0, bool(trans))):
+                _lib.check(self.lib.pk_trmm_f64(self.stream(), 1 if trans else 0, n, c1 - c0, _ptr(L), L.stride(0),
+                                                _ptr(X, c0), X.stride(0), _ptr(Y, c0), Y.stride(0), _ptr(work)), 'pk_trmm_f64')
+        return Y
+
+    def trsm(self, L, n, B):
+        """X = L^-T B for B [n x r] (host or device), L the image of `chol` (pk_trsm_f64 on a padded copy)."""
+        from . import hybrid
+        n = int(n)
+        B = torch.as_tensor(np.ascontiguousarray(B) if isinstance(B, np.ndarray) else B)
+        r = int(B.shape[1])
+        W = torch.empty(hybrid.leading_dim(n), r, dtype=torch.float64, device=self.device)
+        W[:n] = B.to(device=self.device, dtype=torch.float64)
+        with self._timed('trsm', (n, r)):
+            _lib.check(self.lib.pk_trsm_f64(self.stream(), n, r, _ptr(L), L.stride(0), _ptr(W), W.stride(0)), 'pk_trsm_f64')
+        return W[:n]
+
     def dense_scores(self, V, E):
         n_rows, K = E.shape
         n_items = V.shape[0]

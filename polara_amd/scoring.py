@@ -31,12 +31,25 @@ SWEEP_FROM_ROWS = True
 
 class FactorImage:
     """Item factors resident in HBM in both forms the scoring kernels read: fp64 row-major
-    (re-scoring, fold-in) and fp32 MFMA-fragment packed (candidate pass)."""
+    (re-scoring, fold-in) and fp32 MFMA-fragment packed (candidate pass).
 
-    def __init__(self, ops, V):
+    fold: separate fold-in factors (HybridSVD: scores T vr vl^T with V = vl, fold = vr), fp64 [n_items x K] in the item
+    order of V.  With it, E = T fold is computed exactly in fp64 and the approximate fold-in is off (its certification
+    weights assume that fold-in and scoring read the same rows); the sweep, the pruning bound, the re-scoring, the
+    certification and the exact rows all run against V as before.  `fold_in` is the matrix the fold-in multiplies by:
+    `fold`, or V itself."""
+
+    def __init__(self, ops, V, fold=None):
         self.ops = ops
         self.V = V.contiguous()
         self.n_items, self.K = self.V.shape
+        self.fold = None
+        if fold is not None:
+            if tuple(fold.shape) != (self.n_items, self.K):
+                raise ValueError('fold-in factors of shape %s do not match the item factors %s'
+                                 % (tuple(fold.shape), (self.n_items, self.K)))
+            self.fold = fold.contiguous()
+        self.fold_in = self.V if self.fold is None else self.fold
         # the fused sweep's MFMA instances stop at rank 256; beyond it every user goes through the exact fp64 row
         # kernel (any rank) — the same lists, no fragment image needed
         self.fused = self.K <= MAX_FUSED_RANK
@@ -168,7 +181,7 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
     KC = ops.candidate_capacity(topk) if factors.fused else 0
     K = factors.K
     if KC == 0:
-        E = ops.spmm(T, factors.V)                   # fold-in, fp64 (K4)
+        E = ops.spmm(T, factors.fold_in)             # fold-in, fp64 (K4)
         # topk beyond the fused kernel's 52, or a rank beyond its 256: every user goes through the exact fp64 row
         # kernel (all items scored, two-class key) — slow but the same contract
         seen_ptr = T.indptr if filter_seen else None
@@ -186,7 +199,9 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
         return (out_idx, out_s) if return_scores else out_idx
     if approx_fold_in is None:
         approx_fold_in = not return_scores
-    approx_fold_in = bool(approx_fold_in) and not return_scores and factors.Kx <= 256 and T.nonneg()
+    # (separate fold-in factors: always the exact fold-in — the approximate one certifies against the rows of V)
+    approx_fold_in = (bool(approx_fold_in) and not return_scores and factors.Kx <= 256 and factors.fold is None
+                      and T.nonneg())
     Kx = factors.Kx if approx_fold_in else K
     Ex = ops.empty(n_users, Kx)
     E = Ex[:, :K]                       # row stride Kx: every kernel below takes a leading dimension
@@ -224,7 +239,7 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
                 ops.spmm(T, factors.V32x, out=Ex, rows=(u0, u1))           # fold-in against fl32(V) (K4)
             w = Ex[u0:u1, K]                                               # w_u: ||E' - E|| <= 2^-24 w_u (strided view)
         else:
-            ops.spmm(T, factors.V, out=Ex, rows=(u0, u1))                  # fold-in, fp64 (K4)
+            ops.spmm(T, factors.fold_in, out=Ex, rows=(u0, u1))            # fold-in, fp64 (K4)
             w = None
         Eb = E[u0:u1]
         # fragments of E for the MFMA sweep + the users' side of the exact Cauchy-Schwarz pruning bound (a group
@@ -496,5 +511,5 @@ class RecordedPass:
 def dense_scores(ops, factors, T, start, stop):
     """Dense fp64 scores of test users [start, stop) — kept for `slice_recommendations` /
     `_user_scores` (models.py:277-291, 857-861); not used by get_recommendations."""
-    E = ops.spmm(T, factors.V)
+    E = ops.spmm(T, factors.fold_in)
     return ops.dense_scores(factors.V, E[start:stop].contiguous())
