@@ -3,6 +3,7 @@
     from polara_amd import SVDModel, ScaledSVD, CoffeeModel        # the names polara/__init__.py exports for this path
     from polara_amd import CooccurrenceModel, PopularityModel     # the item-to-item and most-popular baselines
     from polara_amd import HybridSVD, ScaledHybridSVD             # PureSVD with item side information (dense Cholesky)
+    from polara_amd import SVDModelItemColdStart, HybridSVDItemColdStart   # item cold start (also the -s forms and MP(cs))
     from polara_amd import ArrayData, ShardedArrayData              # NumPy / on-disk data providers
 
 Resolved on first use, so that importing the package (or its build / binding modules) does not pull in torch."""
@@ -86,6 +87,9 @@ _EXPORTS = {
     'RecommenderModel': 'models', 'SVDModel': 'models', 'ScaledSVD': 'models', 'CoffeeModel': 'models',
     'CooccurrenceModel': 'models', 'PopularityModel': 'models', 'HybridSVD': 'models', 'ScaledHybridSVD': 'models',
     'SimilarityArrayData': 'data',
+    'SVDModelItemColdStart': 'coldstart', 'ScaledSVDItemColdStart': 'coldstart', 'HybridSVDItemColdStart': 'coldstart',
+    'ScaledHybridSVDItemColdStart': 'coldstart', 'PopularityModelItemColdStart': 'coldstart',
+    'ItemColdStartArrayData': 'data', 'ItemColdStartSimilarityArrayData': 'data',
     'ArrayData': 'data', 'ShardedArrayData': 'data',
     'SparseProduct': 'operator', 'find_optimal_svd_rank': 'pipelines', 'find_optimal_tucker_ranks': 'pipelines',
     'find_optimal_config': 'pipelines',

@@ -289,6 +289,9 @@ class SimilarityArrayData(ArrayData):
 
     def __init__(self, training, *args, relations_matrices, relations_indices, **kwargs):
         super().__init__(training, *args, **kwargs)
+        self._init_relations(relations_matrices, relations_indices)
+
+    def _init_relations(self, relations_matrices, relations_indices):
         entities = (self.fields.userid, self.fields.itemid)
         self._rel_mat = {e: m for e, m in relations_matrices.items() if e in entities}
         self._rel_idx = {e: (None if idx is None else np.asarray(idx)) for e, idx in relations_indices.items() if e in entities}
@@ -336,3 +339,111 @@ class SimilarityArrayData(ArrayData):
             rel = np.array(np.asarray(mat)[np.ix_(rows, rows)], dtype=np.float64)
             np.fill_diagonal(rel, 1)
         self._relations[entity] = rel
+
+
+def one_hot_csr(features, n_rows=None, n_labels=None):
+    """A SciPy CSR feature matrix [n_rows x n_labels] from a SciPy matrix or from one list of label ids per row (the
+    layout `stack_features(..., normalize=False)` gives the reference, lib/similarity.py:327-348): canonical (sorted
+    indices, duplicates summed), fp64."""
+    from scipy.sparse import csr_matrix, issparse
+    if issparse(features):
+        m = csr_matrix(features, dtype=np.float64)
+    else:
+        rows = [np.unique(np.asarray(r, dtype=np.int64)) for r in features]      # a label counts once (feature2sparse: set)
+        indptr = np.r_[0, np.cumsum([len(r) for r in rows])].astype(np.int64)
+        indices = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+        width = int(n_labels if n_labels is not None else (indices.max() + 1 if len(indices) else 0))
+        if len(indices) and (indices.min() < 0 or indices.max() >= width):      # (SciPy's constructor does not check this)
+            raise ValueError('feature label %d outside the %d labels' % (int(indices.max() if indices.min() >= 0 else indices.min()), width))
+        m = csr_matrix((np.ones(len(indices)), indices, indptr), shape=(len(rows), width))
+    if n_rows is not None and m.shape[0] != n_rows:
+        raise ValueError('features for %d rows, %d expected' % (m.shape[0], n_rows))
+    if n_labels is not None and m.shape[1] != n_labels:
+        raise ValueError('features over %d labels, %d expected' % (m.shape[1], n_labels))
+    m.sum_duplicates()
+    m.sort_indices()
+    return m
+
+
+class ItemColdStartArrayData(ArrayData):
+    """ArrayData for item cold start: the counterpart of Polara's `ItemColdStartData` (coldstart/data.py:10-225) after
+    `prepare()`.
+
+    training: triplets of the training (warm) items, as in ArrayData.  holdout: triplets (user, cold item, feedback) with the
+    cold items numbered 0..n_cold-1; kept sorted by cold item (coldstart/data.py:212-217).  item_features /
+    cold_item_features: the features of the training items (rows in item id order) and of the cold items over ONE label
+    space — SciPy matrices, or one list of label ids per item.  Cold items that share no label with any training item are
+    dropped and the remaining ones renumbered, in the feature matrix and in the holdout (`is_valid`,
+    coldstart/data.py:162-209); `cold_items_kept` holds their original numbers.  representative_users: sorted internal user
+    ids or None (`data.representative_users`; only MP(cs) restricts itself to them).  `holdout_size` reads -1."""
+
+    def __init__(self, training, holdout, item_features, cold_item_features, n_users=None, n_items=None,
+                 representative_users=None, fields=('userid', 'itemid', 'rating')):
+        self._constructing = True               # the base constructor sets an empty test state through set_test_data
+        ArrayData.__init__(self, training, n_users=n_users, n_items=n_items, fields=fields)
+        self._constructing = False
+        self.item_features = one_hot_csr(item_features, n_rows=self.n_items)
+        self._set_cold_items(holdout, cold_item_features)
+        self.representative_users = (None if representative_users is None
+                                     else np.unique(np.asarray(representative_users, dtype=np.int64)))
+        if self.representative_users is not None and len(self.representative_users) and not (
+                0 <= self.representative_users[0] and self.representative_users[-1] < self.n_users):
+            raise ValueError('representative users outside 0..%d' % (self.n_users - 1))
+
+    @property
+    def holdout_size(self):
+        return -1
+
+    @holdout_size.setter
+    def holdout_size(self, new_value):
+        if new_value:                       # (0 is what the base constructor writes; coldstart/data.py:30-35)
+            raise NotImplementedError('Setting holdout size is currently not supported in item cold start.')
+
+    def _set_holdout_size(self):
+        pass
+
+    def _set_cold_items(self, holdout, cold_item_features):
+        cold = one_hot_csr(cold_item_features, n_labels=self.item_features.shape[1])
+        known = np.diff(self.item_features.tocsc().indptr) > 0                 # labels some training item carries
+        valid = np.asarray(cold[:, np.flatnonzero(known)].getnnz(axis=1)).ravel() > 0
+        u, c, f = (np.asarray(a) for a in holdout)
+        c = c.astype(np.int64)
+        if len(c) and (c.min() < 0 or c.max() >= cold.shape[0]):
+            raise ValueError('holdout names cold item %d, the features describe %d cold items' % (int(c.max()), cold.shape[0]))
+        if len(u) and (u.min() < 0 or u.max() >= self.n_users):
+            raise ValueError('holdout names user %d of %d training users' % (int(u.max()), self.n_users))
+        self.cold_items_kept = np.flatnonzero(valid)
+        new_id = np.full(cold.shape[0], -1, dtype=np.int64)
+        new_id[self.cold_items_kept] = np.arange(len(self.cold_items_kept))
+        keep = valid[c]
+        u, c, f = u[keep], new_id[c[keep]], np.asarray(f, dtype=np.float64)[keep]
+        order = np.argsort(c, kind='stable')
+        self.cold_item_features = cold[self.cold_items_kept]
+        self.n_cold_items = int(len(self.cold_items_kept))
+        self._test = TestData(None, self._frozen(u[order], c[order], f[order]))
+
+    def set_test_data(self, testset=None, holdout=None, notify=True, cold_item_features=None):
+        """A new holdout (user, cold item, feedback), with the features of its cold items when those change too."""
+        if self._constructing:
+            self._test = TestData(None, None)       # (the holdout follows once the features are known)
+            return
+        if holdout is None:
+            raise ValueError('item cold start needs a holdout of (user, cold item, feedback) triplets')
+        self._set_cold_items(holdout, self.cold_item_features if cold_item_features is None else cold_item_features)
+        if notify:
+            self._notify(self.on_update_event)
+
+    def get_test_shape(self, tensor_mode=False):
+        """(cold items, training items): the models take (n_cold_items, n_users) from the data instead."""
+        shape = (self.n_cold_items, self.n_items)
+        return shape + (len(self._levels()),) if tensor_mode else shape
+
+
+class ItemColdStartSimilarityArrayData(ItemColdStartArrayData, SimilarityArrayData):
+    """ItemColdStartArrayData plus the relations of SimilarityArrayData (the counterpart of `ItemColdStartSimilarityData`,
+    coldstart/data.py:256-259) — what the hybrid cold-start models are built on."""
+
+    def __init__(self, training, holdout, item_features, cold_item_features, *, relations_matrices, relations_indices,
+                 **kwargs):
+        ItemColdStartArrayData.__init__(self, training, holdout, item_features, cold_item_features, **kwargs)
+        self._init_relations(relations_matrices, relations_indices)

@@ -748,6 +748,8 @@ class SVDModel(RecommenderModel):
         self.factors['singular_values'] = ops.to_host(sigma)
         self._factor_image = scoring.FactorImage(ops, V) if item_factors is not None else None
         self._factor_src = item_factors
+        if getattr(self, '_keep_user_factors_on_device', False):     # (the cold-start models score against U: coldstart.py)
+            self._user_factors_dev = (user_factors, U) if want_u and self.comm.world == 1 else None
 
 
 
@@ -1462,6 +1464,8 @@ class HybridSVD(SVDModel):
                                                  fold=ops.to_device(np.ascontiguousarray(vr_h[by_norm])))
         self._factor_src = factors[f'{itemid}_projector_left']
         self._fold_src = factors[f'{itemid}_projector_right']
+        if getattr(self, '_keep_user_factors_on_device', False):     # (the cold-start models score against U: coldstart.py)
+            self._user_factors_dev = (factors[userid], U) if want_u else None
 
 
 class ScaledHybridSVD(ScaledMatrixMixin, HybridSVD):

@@ -547,6 +547,10 @@ class HipOps:
     def to_host(self, t):
         return t.detach().cpu().numpy()
 
+    def free_bytes(self):
+        """free device memory in bytes (what the memory guards of the dense images compare their needs with)"""
+        return int(torch.cuda.mem_get_info(self.device)[0])
+
     def csr(self, indptr, indices, values, shape, split=SPLIT_NNZ):
         return DeviceCSR(self, indptr, indices, values, shape, split)
 
@@ -1678,6 +1682,22 @@ class HipOps:
         with self._timed('trsm', (n, r)):
             _lib.check(self.lib.pk_trsm_f64(self.stream(), n, r, _ptr(L), L.stride(0), _ptr(W), W.stride(0)), 'pk_trsm_f64')
         return W[:n]
+
+    # ---- item cold start -----------------------------------------------------------------------------------------
+    def coldstart_queries(self, F, W, G):
+        """E = (F W) G for the cold items of a DeviceCSR over the training labels, fp64: the SpMM and the tall-skinny product
+        of the build (pk_spmm_csr_ex, pk_tsmm_f64), the second writing straight into a block whose rows are 16-byte aligned
+        with an even leading dimension (what `sweep_takes_rows` asks for; the padding column of an odd rank is zeroed).
+        Returns the [n_cold x rank] view.  (A fused kernel was built and measured slower: DESIGN.md 8c.)"""
+        assert W.dtype == torch.float64 and W.stride(1) == 1 and G.dtype == torch.float64 and G.stride(1) == 1
+        n_cold, rank = int(F.shape[0]), int(W.shape[1])
+        if F.shape[1] != W.shape[0] or tuple(G.shape) != (rank, rank):
+            raise ValueError('coldstart_queries: features %s, W %s, G %s do not fit' % (F.shape, tuple(W.shape), tuple(G.shape)))
+        lde = rank + (rank & 1)
+        block = self.zeros(n_cold, lde) if lde != rank else self.empty(n_cold, lde)
+        with self._timed('coldstart_queries', (n_cold, int(W.shape[0]), rank)):
+            self.tsmm(self.spmm(F, W), G, out=block[:, :rank])
+        return block[:, :rank]
 
     def dense_scores(self, V, E):
         n_rows, K = E.shape

@@ -353,30 +353,117 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
         stats['approx_fold_in'] = bool(approx_fold_in)
         stats['candidate_capacity'] = KC
         stats['item_splits'] = splits
-        # tiles actually scored by the candidate sweep (pruning), for the roofline accounting
-        n_tiles = -(-n_items // 32)
-        if two_phase[0]:
-            # slot 0: the head sweep (tiles [0, H)); slots 1..S: split h owns tiles H + h, H + h + S, ...
-            H, S2 = two_phase
-            stats['item_splits'] = 1
-            stats['two_phase'] = {'head_tiles': H, 'splits': S2}
-            ex = ops.score_exit_tiles(n_users, S2 + 1)
-            first = H + torch.arange(S2, device=ex.device, dtype=torch.int64)[:, None]
-            tail = torch.div((ex[1:] - first).clamp_min(0) + S2 - 1, S2, rounding_mode='floor')
-            tail = torch.where(ex[:1] < H, torch.zeros_like(tail), tail)      # pruned inside the head: the splits did not run
-            scored = ex[0].clamp_max(H) + tail.sum(dim=0)                    # tiles scored per group, all sweeps together
-            chain = ex[0].clamp_max(H) + tail.max(dim=0).values              # the group's dependent chain (tile steps)
-            q2 = torch.quantile(chain.double(), torch.tensor([0.5, 0.99, 1.0], dtype=torch.float64, device=ex.device))
-            stats['two_phase']['chain_quantiles'] = dict(zip(('p50', 'p99', 'max'), [float(v) for v in q2.tolist()]))
+        _tile_stats(ops, stats, n_users, n_items, splits, two_phase)
+    if return_scores:
+        return out_idx, out_s
+    if out is not None:
+        return ops.scatter_rows(out_idx, None, out=out)
+    return out_idx
+
+
+def _tile_stats(ops, stats, n_users, n_items, splits, two_phase):
+    """tiles the last candidate sweep of the stream actually scored (pruning), per group of 32 rows: the roofline accounting
+    of `recommend` / `recommend_dense` (reads the sweep's state buffer: host round trips)"""
+    n_tiles = -(-n_items // 32)
+    if two_phase[0]:
+        # slot 0: the head sweep (tiles [0, H)); slots 1..S: split h owns tiles H + h, H + h + S, ...
+        H, S2 = two_phase
+        stats['item_splits'] = 1
+        stats['two_phase'] = {'head_tiles': H, 'splits': S2}
+        ex = ops.score_exit_tiles(n_users, S2 + 1)
+        first = H + torch.arange(S2, device=ex.device, dtype=torch.int64)[:, None]
+        tail = torch.div((ex[1:] - first).clamp_min(0) + S2 - 1, S2, rounding_mode='floor')
+        tail = torch.where(ex[:1] < H, torch.zeros_like(tail), tail)      # pruned inside the head: the splits did not run
+        scored = ex[0].clamp_max(H) + tail.sum(dim=0)                    # tiles scored per group, all sweeps together
+        chain = ex[0].clamp_max(H) + tail.max(dim=0).values              # the group's dependent chain (tile steps)
+        q2 = torch.quantile(chain.double(), torch.tensor([0.5, 0.99, 1.0], dtype=torch.float64, device=ex.device))
+        stats['two_phase']['chain_quantiles'] = dict(zip(('p50', 'p99', 'max'), [float(v) for v in q2.tolist()]))
+    else:
+        ex = ops.score_exit_tiles(n_users, splits)                      # absolute tile index, per split and group
+        first = torch.arange(splits, device=ex.device, dtype=torch.int64)[:, None]   # split h owns tiles h, h+S, ...
+        scored = torch.div((ex - first).clamp_min(0) + splits - 1, splits, rounding_mode='floor')
+    stats['tiles_scored'] = int(scored.sum().item())
+    stats['tiles_total'] = int(ex.shape[1]) * n_tiles
+    q = torch.quantile(scored.flatten().double(),
+                       torch.tensor([0.5, 0.9, 0.99, 0.999, 1.0], dtype=torch.float64, device=ex.device))
+    stats['exit_tile_quantiles'] = dict(zip(('p50', 'p90', 'p99', 'p999', 'max'), [float(v) for v in q.tolist()]))
+
+
+def recommend_dense(ops, factors, E, topk, return_scores=False, stats=None, prune=True, out=None):
+    """Top-k catalogue rows for DENSE queries: scores E V^T with E fp64 [n_queries x K] on the device (a view with a leading
+    dimension is fine), V the rows of `factors` (FactorImage), nothing masked.  Returns int64 device tensor [n_queries x
+    topk] of catalogue positions (+ fp64 scores), columns by descending score — the ordering of `recommend`.
+    What `recommend` does after its fold-in, with E given and exact: candidate sweep (read straight from the rows of E when
+    they are aligned, ops.sweep_takes_rows; item splits or the two-phase sweep when the queries do not fill the chip) ->
+    exact fp64 re-scoring and certification -> exact rows for who is still flagged; no seen lists, no approximate fold-in
+    (so no error weights), no batching.  The item cold-start models call it with the cold items as queries and the
+    training users as the catalogue (polara_amd/coldstart.py).  `out`: as in `recommend`."""
+    lock = getattr(ops, 'pass_lock', None)
+    if lock is not None and not getattr(_in_pass, 'held', False):
+        with lock:
+            _in_pass.held = True
+            try:
+                return recommend_dense(ops, factors, E, topk, return_scores, stats, prune, out)
+            finally:
+                _in_pass.held = False
+    if E.dim() != 2 or E.dtype != torch.float64 or E.stride(1) != 1:
+        raise ValueError('recommend_dense: E must be an fp64 [n_queries x K] block with unit column stride')
+    n_q, K = (int(x) for x in E.shape)
+    n_items = factors.n_items
+    if K != factors.K:
+        raise ValueError('queries of rank %d against factors of rank %d' % (K, factors.K))
+    if out is not None and (return_scores or tuple(out.shape) != (n_q, topk) or out.dtype != torch.int64 or not out.is_contiguous()
+                            or not (out.is_cuda or out.is_pinned())):
+        raise ValueError('recommend_dense: `out` takes the ids only: a contiguous int64 [n_queries x topk] device or pinned host tensor')
+    if topk > n_items:
+        raise ValueError('kth(=%d) out of bounds (%d)' % (n_items - topk, n_items))  # numpy argpartition's error
+    out_idx = torch.empty(n_q, topk, dtype=torch.int64, device=E.device)
+    out_s = torch.empty(n_q, topk, dtype=torch.float64, device=E.device)
+    KC = ops.candidate_capacity(topk) if factors.fused else 0
+    if n_q == 0:
+        return (out_idx, out_s) if return_scores else out_idx
+    if KC == 0:
+        # topk beyond the fused kernel's 52, or a rank beyond its 256: every query goes through the exact fp64 row kernel
+        per = max(1, int(EXACT_ROWS_BYTES // (n_items * 9 + 16)))
+        for s0 in range(0, n_q, per):
+            sub = torch.arange(s0, min(n_q, s0 + per), dtype=torch.int32, device=E.device)
+            ex_idx, ex_s = ops.score_exact_rows(sub, factors.V, E, n_items, None, None, topk)
+            out_idx[s0:s0 + len(sub)] = ex_idx
+            out_s[s0:s0 + len(sub)] = ex_s
+        if stats is not None:
+            stats.update(flagged_users=n_q, candidate_capacity=0, item_splits=0)
+    else:
+        splits = ops.score_splits(n_q, KC, prune)
+        use_two_phase = bool(prune and hasattr(ops, 'two_phase_plan') and not getattr(ops, 'score_splits_override', 0))
+        two_phase = ops.two_phase_plan(n_q, n_items, KC) if use_two_phase else (0, 0)
+        flags = torch.empty(n_q, dtype=torch.int32, device=E.device)
+        fused_lists = hasattr(ops, 'zero_counters')        # (the CPU double of the tests keeps the separate compaction)
+        final = None
+        if fused_lists:
+            final = (torch.empty(n_q, dtype=torch.int32, device=E.device), ops.zero_counters(1), 0)
+        rows_kw = {}
+        if SWEEP_FROM_ROWS and prune and hasattr(ops, 'sweep_takes_rows') and ops.sweep_takes_rows(E):
+            Ep = ub = None
+            rows_kw = {'E_rows': (E, None, 0.0)}
         else:
-            ex = ops.score_exit_tiles(n_users, splits)                      # absolute tile index, per split and group
-            first = torch.arange(splits, device=ex.device, dtype=torch.int64)[:, None]   # split h owns tiles h, h+S, ...
-            scored = torch.div((ex - first).clamp_min(0) + splits - 1, splits, rounding_mode='floor')
-        stats['tiles_scored'] = int(scored.sum().item())
-        stats['tiles_total'] = int(ex.shape[1]) * n_tiles
-        q = torch.quantile(scored.flatten().double(),
-                           torch.tensor([0.5, 0.9, 0.99, 0.999, 1.0], dtype=torch.float64, device=ex.device))
-        stats['exit_tile_quantiles'] = dict(zip(('p50', 'p90', 'p99', 'p999', 'max'), [float(v) for v in q.tolist()]))
+            Ep, ub = ops.pack_frag_bound(E)
+        if two_phase[0]:
+            cs, ci = ops.score_two_phase(factors.Vp, Ep, n_q, n_items, K, None, KC, two_phase[0], two_phase[1], ub,
+                                         factors.tile_bound, **rows_kw)
+            splits = 1
+        else:
+            cs, ci = ops.score_candidates(factors.Vp, Ep, n_q, n_items, K, None, None, KC, splits,
+                                          user_bound=ub if prune else None, tile_bound=factors.tile_bound if prune else None,
+                                          **rows_kw)
+        ops.rescore_topk(factors.V, E, n_items, None, KC, cs, ci, topk, factors.vmax, want_scores=True, splits=splits,
+                         out=(out_idx, out_s, flags), **({'flagged': final} if fused_lists else {}))
+        lst, cnt = final[:2] if fused_lists else ops.flag_compact(flags, 0x7fffffff)
+        ops.score_exact_list(lst, cnt, factors.V, E, n_items, None, None, topk, out_idx, out_s)
+        if stats is not None:
+            stats['flagged_users'] = int(cnt.item())
+            stats['candidate_capacity'] = KC
+            stats['item_splits'] = splits
+            _tile_stats(ops, stats, n_q, n_items, splits, two_phase)
     if return_scores:
         return out_idx, out_s
     if out is not None:
