@@ -649,6 +649,36 @@ int pk_trmm_f64(void *stream, int32_t trans, int64_t n, int32_t nc, const double
 int pk_trsm_f64(void *stream, int64_t n, int32_t r, const double *L_dev, int64_t ld, double *B_dev, int64_t ldb);
 
 /* ------------------------------------------------------------------------------------------
+ * Local Collective Embeddings (csrc/lce.hip).  Replace the NumPy element-wise updates and traces of
+ * `local_collective_embeddings` (lib/optimize.py:347-379).  The factors are tall row-major fp64 blocks, the H factors
+ * transposed ([labels x k], [users x k]), so the three multiplicative updates are one form:
+ *     X <- X o (a N) / max(X M + (lamb + c_i) X, 1e-10),    M = ma M1 + mb M2 (k x k; M2 may be NULL)
+ *   Hs^T: N = Xs^T W, M = alpha W^T W;  Hu^T: N = Xu^T W, M = gamma W^T W  (optimize.py:350-356)
+ *   W:    N = alpha Xs Hs^T + gamma Xu Hu^T + beta A W, M = alpha Hs Hs^T + gamma Hu Hu^T, c = beta d  (optimize.py:359-363)
+ * pk_lce_update_f64: ONE launch, M in LDS, k <= pk_lce_fused_max_rank() (128: 128 KiB of the CU's 160 KiB hold M, 16 KiB the
+ * staged rows); every row of X and N is read once.  Above that rank: P = X M by pk_tsmm_f64, then pk_lce_update_ew_f64.
+ * c_dev: [m] or NULL.  X must not alias N or P. */
+int32_t pk_lce_fused_max_rank(void);
+int pk_lce_update_f64(void *stream, int64_t m, int32_t k, double *X_dev, int64_t ldx, const double *N_dev, int64_t ldn,
+                      const double *M1_dev, int64_t ldm1, double ma, const double *M2_dev, int64_t ldm2, double mb,
+                      double a, double lamb, const double *c_dev);
+int pk_lce_update_ew_f64(void *stream, int64_t m, int32_t k, double *X_dev, int64_t ldx, const double *N_dev, int64_t ldn,
+                         const double *P_dev, int64_t ldp, double a, double lamb, const double *c_dev);
+/* The traces of the objective (optimize.py:374-379) in two launches: dot_p = sum_ij w_p[i] P_p[i, j] Q_p[i, j] for
+ * n_pairs <= PK_LCE_MAX_PAIRS blocks [m_p x k_p] (Q_p NULL: ones; w_p NULL: ones; the arrays of pointers and sizes are HOST
+ * arrays of n_pairs entries, the pointers in them DEVICE pointers), out_dev[0] = bias + sum_p coef_p dot_p,
+ * out_dev[1 + p] = dot_p.  Fixed summation order, no atomics: pair p is cut into pk_lce_dot_blocks(m_p k_p) contiguous
+ * ranges whose sums are added in ascending order — equal inputs give equal bits.  work >= pk_lce_dots_work_bytes(). */
+#define PK_LCE_MAX_PAIRS 16
+int32_t pk_lce_dot_blocks(int64_t n_elems);
+int64_t pk_lce_dots_work_bytes(void);
+int pk_lce_dots_f64(void *stream, int32_t n_pairs, const double *const *P_dev, const double *const *Q_dev,
+                    const double *const *w_dev, const int64_t *m, const int32_t *k, const int64_t *ldp, const int64_t *ldq,
+                    const double *coef, double bias, double *out_dev, void *work_dev);
+/* E <- max(E, lo) over an [m x k] block: the clamp of LCE's cold-start queries (coldstart/models.py:144) */
+int pk_clamp_min_f64(void *stream, int64_t m, int32_t k, double *E_dev, int64_t lde, double lo);
+
+/* ------------------------------------------------------------------------------------------
  * K5.  Sparse tensor-times-matrix (CoFFee / HOOI).
  * Replaces numba `dttm_seq` / `dttm_par` (lib/sparse.py:203-234) called from `ttm3d_seq`
  * (lib/tensor.py:7-19):  res[i0, j, k] += val * u[i1, j] * v[i2, k].

@@ -4,6 +4,7 @@
     from polara_amd import CooccurrenceModel, PopularityModel     # the item-to-item and most-popular baselines
     from polara_amd import HybridSVD, ScaledHybridSVD             # PureSVD with item side information (dense Cholesky)
     from polara_amd import SVDModelItemColdStart, HybridSVDItemColdStart   # item cold start (also the -s forms and MP(cs))
+    from polara_amd import LCEModel, LCEModelItemColdStart          # Local Collective Embeddings, standard and item cold start
     from polara_amd import ArrayData, ShardedArrayData              # NumPy / on-disk data providers
 
 Resolved on first use, so that importing the package (or its build / binding modules) does not pull in torch."""
@@ -89,6 +90,7 @@ _EXPORTS = {
     'SimilarityArrayData': 'data',
     'SVDModelItemColdStart': 'coldstart', 'ScaledSVDItemColdStart': 'coldstart', 'HybridSVDItemColdStart': 'coldstart',
     'ScaledHybridSVDItemColdStart': 'coldstart', 'PopularityModelItemColdStart': 'coldstart',
+    'LCEModel': 'lce', 'LCEModelItemColdStart': 'lce',
     'ItemColdStartArrayData': 'data', 'ItemColdStartSimilarityArrayData': 'data',
     'ArrayData': 'data', 'ShardedArrayData': 'data',
     'SparseProduct': 'operator', 'find_optimal_svd_rank': 'pipelines', 'find_optimal_tucker_ranks': 'pipelines',

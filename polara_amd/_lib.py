@@ -141,6 +141,13 @@ PROTOTYPES = {
     'pk_chol_f64': (C.c_int, [_vp, _i64, _vp, _i64, _vp]),
     'pk_trmm_f64': (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     'pk_trsm_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64]),
+    'pk_lce_fused_max_rank': (_i32, []),
+    'pk_lce_update_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _vp, _i64, _f64, _f64, _f64, _vp]),
+    'pk_lce_update_ew_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _f64, _vp]),
+    'pk_lce_dot_blocks': (_i32, [_i64]),
+    'pk_lce_dots_work_bytes': (_i64, []),
+    'pk_lce_dots_f64': (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp]),
+    'pk_clamp_min_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _f64]),
     'pk_ctx_create': (C.c_int, [_i32, C.POINTER(_vp)]),
     'pk_ctx_destroy': (None, [_vp]),
     'pk_ctx_error': (C.c_char_p, [_vp]),

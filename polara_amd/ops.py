@@ -1699,6 +1699,86 @@ class HipOps:
             self.tsmm(self.spmm(F, W), G, out=block[:, :rank])
         return block[:, :rank]
 
+    def clamp_min(self, E, lo=0.0):
+        """E <- max(E, lo) in place (pk_clamp_min_f64): LCE's cold-start queries (coldstart/models.py:144)."""
+        assert E.dtype == torch.float64 and E.dim() == 2 and E.stride(1) == 1
+        _lib.check(self.lib.pk_clamp_min_f64(self.stream(), int(E.shape[0]), int(E.shape[1]), _ptr(E), E.stride(0), float(lo)),
+                   'pk_clamp_min_f64')
+        return E
+
+    # ---- Local Collective Embeddings (csrc/lce.hip) ----------------------------------------------------------------
+    def csr_scaled(self, A, s):
+        """A DeviceCSR with the pattern (and plan) of A and the fp64 values s * A.values"""
+        new = A.with_columns(A.indices, A.values.to(torch.float64) * float(s))
+        new.val_kind = _lib.PK_VAL_F64
+        return new
+
+    def csr_values(self, A):
+        return A.values
+
+    def spmm_acc(self, A, X, out):
+        """out += A @ X (pk_spmm_csr_ex with accumulate = 1; the sums of a row are added to what `out` holds)"""
+        assert X.dtype == torch.float64 and X.stride(-1) == 1 and X.shape[0] == A.shape[1] and out.shape[0] == A.shape[0]
+        for c0 in range(0, X.shape[1], 256):        # one output row per wave in registers: 256 columns per launch
+            self._spmm_launch(A, X[:, c0:c0 + 256], out[:, c0:c0 + 256], (0, A.n_tasks, 0, A.n_long), accumulate=True)
+        return out
+
+    def lce_fused_max_rank(self):
+        return int(self.lib.pk_lce_fused_max_rank())
+
+    def lce_update(self, X, N, M1, ma=1.0, M2=None, mb=0.0, a=1.0, lamb=0.0, c=None, fused=None):
+        """X <- X o (a N) / max(X M + (lamb + c_i) X, 1e-10) in place, M = ma M1 + mb M2 (k x k).  fused=None: one launch
+        (pk_lce_update_f64) up to lce_fused_max_rank(), above it the composition M -> pk_tsmm_f64 -> pk_lce_update_ew_f64;
+        True / False force one form (False at any rank: the comparison of tools/bench_lce.py; True above the bound raises)."""
+        assert X.dtype == torch.float64 and X.dim() == 2 and X.stride(1) == 1 and N.stride(1) == 1 and tuple(N.shape) == tuple(X.shape)
+        m, k = int(X.shape[0]), int(X.shape[1])
+        assert tuple(M1.shape) == (k, k) and M1.stride(1) == 1 and (M2 is None or (tuple(M2.shape) == (k, k) and M2.stride(1) == 1))
+        assert c is None or (c.dtype == torch.float64 and c.numel() == m and c.is_contiguous())
+        if fused is None:
+            fused = k <= self.lce_fused_max_rank()
+        if fused:
+            with self._timed('lce_update', (m, k)):
+                _lib.check(self.lib.pk_lce_update_f64(self.stream(), m, k, _ptr(X), X.stride(0), _ptr(N), N.stride(0), _ptr(M1),
+                                                      M1.stride(0), float(ma), _ptr(M2), M2.stride(0) if M2 is not None else 0,
+                                                      float(mb), float(a), float(lamb), _ptr(c)), 'pk_lce_update_f64')
+            return X
+        with self._timed('lce_update_composed', (m, k)):
+            M = self.axpbypcz(float(ma), M1.contiguous(), float(mb) if M2 is not None else 0.0, M2.contiguous() if M2 is not None else None)
+            P = self.tsmm(X, M)
+            _lib.check(self.lib.pk_lce_update_ew_f64(self.stream(), m, k, _ptr(X), X.stride(0), _ptr(N), N.stride(0), _ptr(P),
+                                                     P.stride(0), float(a), float(lamb), _ptr(c)), 'pk_lce_update_ew_f64')
+        return X
+
+    def lce_dots(self, pairs, bias=0.0):
+        """[1 + n] device doubles: out[1 + p] = sum_ij w[i] P[i, j] Q[i, j] of pairs[p] = (coef, P, Q | None, w | None) and
+        out[0] = bias + sum_p coef_p out[1 + p] (pk_lce_dots_f64: two launches, fixed summation order, no atomics)."""
+        n = len(pairs)
+        vp = C.c_void_p * n
+        ptr = lambda t: None if t is None else t.data_ptr()
+        for _, P, Q, w in pairs:
+            assert P.dtype == torch.float64 and P.dim() == 2 and (P.stride(1) == 1 or P.shape[1] == 1)
+            assert Q is None or (Q.dtype == torch.float64 and tuple(Q.shape) == tuple(P.shape) and (Q.stride(1) == 1 or Q.shape[1] == 1))
+            assert w is None or (w.dtype == torch.float64 and w.numel() == P.shape[0] and w.is_contiguous())
+        Pa = vp(*[ptr(p[1]) for p in pairs])
+        Qa = vp(*[ptr(p[2]) for p in pairs])
+        wa = vp(*[ptr(p[3]) for p in pairs])
+        ma = (C.c_int64 * n)(*[int(p[1].shape[0]) for p in pairs])
+        ka = (C.c_int32 * n)(*[int(p[1].shape[1]) for p in pairs])
+        lp = (C.c_int64 * n)(*[int(p[1].stride(0)) for p in pairs])
+        lq = (C.c_int64 * n)(*[int(p[2].stride(0)) if p[2] is not None else 0 for p in pairs])
+        co = (C.c_double * n)(*[float(p[0]) for p in pairs])
+        if _PTR_KEEP is not None:
+            _PTR_KEEP.extend(t for p in pairs for t in p[1:] if t is not None)
+        out = self.empty(1 + n)
+        if getattr(self, '_lce_dots_work', None) is None:
+            self._lce_dots_work = {}
+        work = self._lce_dots_work.get(self.stream_key())
+        if work is None:
+            work = self._lce_dots_work[self.stream_key()] = self._work(self.lib.pk_lce_dots_work_bytes())
+        _lib.check(self.lib.pk_lce_dots_f64(self.stream(), n, Pa, Qa, wa, ma, ka, lp, lq, co, float(bias), _ptr(out), _ptr(work)),
+                   'pk_lce_dots_f64')
+        return out
+
     def dense_scores(self, V, E):
         n_rows, K = E.shape
         n_items = V.shape[0]

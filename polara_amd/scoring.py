@@ -126,13 +126,16 @@ def renumbered_test_rows(ops, users):
 
 
 def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stats=None, prune=True, batches=None,
-              approx_fold_in=None, order_users=True, head_users=None, two_phase_ok=True, out=None):
+              approx_fold_in=None, order_users=True, head_users=None, two_phase_ok=True, out=None, queries=None):
     """factors: FactorImage; T: ops-level CSR of the test users [n_users x n_items].
     Returns int64 device tensor [n_users x topk] (+ fp64 scores), rows in test-user order,
     columns by descending score — the contract of models.py:400-405.
     out (ids only): where the lists are to end up — a device tensor or a PINNED HOST tensor [n_users x topk] int64; the last
     kernel of the pass writes it (ops.scatter_rows: the host-side array of the reference's contract without a copy-engine
     transfer behind the pass) and it is what the call returns.
+    queries: a device fp64 block [n_users x K] of ready-made user rows in test-user order (a view with a leading dimension is
+    fine), used as E INSTEAD of the fold-in E = T V — models whose user factors are not a fold-in (LCE: rows of Hu^T).  T then
+    only names the seen items.  The rows are exact: the approximate fold-in and its re-fold step are off.
 
     approx_fold_in (default: on when only the ids are asked for and the feedback is non-negative): the fold-in
     E = T V gathers the fp32 image of V (half the bytes of the product that is bound by them), and so does the
@@ -149,7 +152,7 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
             _in_pass.held = True
             try:
                 return recommend(ops, factors, T, topk, filter_seen, return_scores, stats, prune, batches, approx_fold_in,
-                                 order_users, head_users, two_phase_ok, out)
+                                 order_users, head_users, two_phase_ok, out, queries)
             finally:
                 _in_pass.held = False
     n_users, n_items = T.shape
@@ -160,6 +163,10 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
         raise ValueError('test matrix and item factors disagree on the number of items')
     if topk > n_items:
         raise ValueError('kth(=%d) out of bounds (%d)' % (n_items - topk, n_items))  # numpy argpartition's error
+    if queries is not None and (queries.dim() != 2 or queries.dtype != torch.float64 or queries.stride(1) != 1
+                                or tuple(queries.shape) != (n_users, factors.K)):
+        raise ValueError('recommend: `queries` must be an fp64 [n_users x K] = [%d x %d] block with unit column stride'
+                         % (n_users, factors.K))
     if order_users and prune and factors.fused and n_users >= ORDER_USERS_MIN and hasattr(T, 'by_activity'):
         # A wave sweeps the catalogue for 32 consecutive users until the LAST of them can be pruned, so users are
         # grouped by activity (the row order is a cached image of the test matrix); rows go back to their places at
@@ -168,7 +175,8 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
         if head_users is None:
             head_users = HEAD_USERS
         res = recommend(ops, factors, Tp, topk, filter_seen, return_scores, stats, prune, batches, approx_fold_in,
-                        order_users=False, head_users=head_users, two_phase_ok=two_phase_ok)
+                        order_users=False, head_users=head_users, two_phase_ok=two_phase_ok,
+                        queries=None if queries is None else queries.index_select(0, perm))     # the rows move with T's
         if return_scores:
             idx_p, sc_p = res
             out_idx, out_s = torch.empty_like(idx_p), torch.empty_like(sc_p)
@@ -181,7 +189,7 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
     KC = ops.candidate_capacity(topk) if factors.fused else 0
     K = factors.K
     if KC == 0:
-        E = ops.spmm(T, factors.fold_in)             # fold-in, fp64 (K4)
+        E = ops.spmm(T, factors.fold_in) if queries is None else queries       # fold-in, fp64 (K4)
         # topk beyond the fused kernel's 52, or a rank beyond its 256: every user goes through the exact fp64 row
         # kernel (all items scored, two-class key) — slow but the same contract
         seen_ptr = T.indptr if filter_seen else None
@@ -201,9 +209,9 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
         approx_fold_in = not return_scores
     # (separate fold-in factors: always the exact fold-in — the approximate one certifies against the rows of V)
     approx_fold_in = (bool(approx_fold_in) and not return_scores and factors.Kx <= 256 and factors.fold is None
-                      and T.nonneg())
+                      and queries is None and T.nonneg())
     Kx = factors.Kx if approx_fold_in else K
-    Ex = ops.empty(n_users, Kx)
+    Ex = ops.empty(n_users, Kx) if queries is None else queries
     E = Ex[:, :K]                       # row stride Kx: every kernel below takes a leading dimension
     seen_ptr = T.indptr if filter_seen else None
     seen_idx = T.indices if filter_seen else None
@@ -238,6 +246,8 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
             else:
                 ops.spmm(T, factors.V32x, out=Ex, rows=(u0, u1))           # fold-in against fl32(V) (K4)
             w = Ex[u0:u1, K]                                               # w_u: ||E' - E|| <= 2^-24 w_u (strided view)
+        elif queries is not None:
+            w = None                                                       # E is given
         else:
             ops.spmm(T, factors.fold_in, out=Ex, rows=(u0, u1))            # fold-in, fp64 (K4)
             w = None
