@@ -457,6 +457,21 @@ int pk_rescore_topk_rows_norms_f64(void *stream, int64_t n_rows, const int32_t *
                              int64_t *out_idx_dev, double *out_score_dev, int32_t *flags_dev,
                              int32_t *flagged_list_dev, int32_t *flagged_count_dev, int32_t flagged_offset,
                              const float *item_norm_dev);
+/* ... and with out_perm_dev (int64 [n_users], or NULL): the out_idx row of user u is written to row out_perm_dev[u]; the rows
+ * of out_score and flags stay where they are.  A pass that sweeps its users in another order than the caller's then needs
+ * no pk_scatter_rows_i64 behind it. */
+int pk_rescore_topk_rows_perm_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
+                             const int32_t *n_rows_dev, int64_t n_users, int64_t n_items,
+                             int32_t K, const double *V_dev, int64_t ldv,
+                             const float *V32_dev, int64_t ldv32,
+                             const double *E_dev, int64_t lde,
+                             const double *e_err_dev, int64_t e_err_ld, int32_t e_exact,
+                             const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
+                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
+                             double v_row_norm_max,
+                             int64_t *out_idx_dev, double *out_score_dev, int32_t *flags_dev,
+                             int32_t *flagged_list_dev, int32_t *flagged_count_dev, int32_t flagged_offset,
+                             const float *item_norm_dev, const int64_t *out_perm_dev);
 int pk_zero_i32(void *stream, int32_t *p_dev, int32_t n);
 /* The re-do of flagged users without a host round trip: pk_flag_compact lists the users with (flags & mask) != 0
  * (list capacity n, *count_dev = list length), pk_fold_rows_f64 recomputes the listed rows of E = A_test V in fp64
@@ -519,6 +534,14 @@ int pk_fold_q20(void *stream, int64_t n_tasks, const int32_t *task_row_dev, cons
                 const int32_t *indices_dev, const void *vals_dev, int val_kind, const void *img_dev,
                 const double *tab_dev, int64_t n_items, int32_t K, int32_t Kx, double *out_dev, int64_t ldo,
                 double *partial_dev);
+/* pk_fold_q20 that also zeroes the int32 counters zero_dev[0 .. zero_n) in its fix-up launch (which then runs even when no
+ * row is split): the counters of a scoring pass are first touched behind the sweep, so their reset needs no launch. */
+int pk_fold_q20_zero(void *stream, int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
+                     const int64_t *task_end_dev, const int32_t *task_slot_dev, int64_t n_long,
+                     const int32_t *long_row_dev, const int32_t *long_slot_begin_dev, const int32_t *long_slot_end_dev,
+                     const int32_t *indices_dev, const void *vals_dev, int val_kind, const void *img_dev,
+                     const double *tab_dev, int64_t n_items, int32_t K, int32_t Kx, double *out_dev, int64_t ldo,
+                     double *partial_dev, int32_t *zero_dev, int32_t zero_n);
 /* dst[perm_dev[r], :] = src_dev[r, :] for rows of `width` int64 (perm_dev == NULL: a plain copy): the lists of a pass whose
  * users were grouped by activity go back to the caller's user order.  `dst` is device memory or MAPPED PINNED HOST memory:
  * the host-side [n_users x topk] int64 array of get_recommendations (models.py:400-405) can be written by the kernel
@@ -539,8 +562,15 @@ int pk_score_exact_rows_f64(void *stream, int32_t n_rows, const int32_t *rows_de
                             const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev, int32_t topk,
                             int64_t *out_idx_dev, double *out_score_dev, void *work_dev);
 /* The same rows for a DEVICE-side list (pk_flag_compact output): users list_dev[0 .. *count_dev); results go to the rows
- * of those users in the [n_users x topk] outputs.  n_wg workgroups walk the list (work >= pk_exact_work_bytes(n_wg,
- * n_items)); the list never visits the host, so a scoring pass needs no synchronisation. */
+ * of those users in the [n_users x topk] outputs.  One launch; n_wg row slots (work >= pk_exact_work_bytes(n_wg, n_items),
+ * prepared ONCE with pk_exact_work_init(stream, work, n_wg, n_items): the buffer ends in one int32 ticket per row slot that
+ * must be zero at the first use and that every call leaves zero); the list never visits the host, so a scoring pass needs
+ * no synchronisation.  A buffer serves one stream at a time.  _perm: out_perm_dev as in pk_rescore_topk_rows_perm_f64. */
+int pk_exact_work_init(void *stream, void *work_dev, int32_t n_rows, int64_t n_items);
+int pk_score_exact_list_perm_f64(void *stream, int32_t n_wg, const int32_t *list_dev, const int32_t *count_dev, int64_t n_items,
+                                 int32_t K, const double *V_dev, int64_t ldv, const double *E_dev, int64_t lde,
+                                 const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev, int32_t topk, int64_t *out_idx_dev,
+                                 double *out_score_dev, void *work_dev, const int64_t *out_perm_dev);
 int pk_score_exact_list_f64(void *stream, int32_t n_wg, const int32_t *list_dev, const int32_t *count_dev, int64_t n_items,
                             int32_t K, const double *V_dev, int64_t ldv, const double *E_dev, int64_t lde,
                             const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev, int32_t topk, int64_t *out_idx_dev,

@@ -100,12 +100,16 @@ PROTOTYPES = {
     'pk_q20_decode_f64': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _i64]),
     'pk_fold_q20': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _i64, _i32, _i32,
                               _vp, _i64, _vp]),
+    'pk_fold_q20_zero': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _i64, _i32, _i32,
+                                   _vp, _i64, _vp, _vp, _i32]),
     'pk_rescore_topk_rows_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
                                            _vp, _vp, _i32, _f64, _vp, _vp, _vp]),
     'pk_rescore_topk_rows_list_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
                                            _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),
     'pk_rescore_topk_rows_norms_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
                                            _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    'pk_rescore_topk_rows_perm_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
+                                           _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     'pk_zero_i32': (C.c_int, [_vp, _vp, _i32]),
     'pk_scatter_rows_i64': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     'pk_map_ids_i64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
@@ -114,6 +118,9 @@ PROTOTYPES = {
                                           _vp, _vp, _vp]),
     'pk_score_exact_list_f64': (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32,
                                           _vp, _vp, _vp]),
+    'pk_score_exact_list_perm_f64': (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32,
+                                               _vp, _vp, _vp, _vp]),
+    'pk_exact_work_init': (C.c_int, [_vp, _vp, _i32, _i64]),
     'pk_eval_ranks': (C.c_int, [_vp, _i64, _vp, _i32, _vp, _vp, _vp]),
     'pk_eval_cols': (_i32, []),
     'pk_eval_user_metrics': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _f64, _i32, _vp]),

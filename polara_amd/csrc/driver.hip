@@ -1981,6 +1981,7 @@ struct pk_serving {
     Dev vnorm, q20_raw, q20_tab;     // fp32 norm bounds of the item rows; the packed fold-in image (csrc/foldq.hip) and its bracket scales
     char *q20_img = nullptr;      // 128-byte aligned start of the image inside q20_raw (nullptr: no packed image)
     int dense_tiles = 0;          // window of the dense seen masks (0: none)
+    Dev exact_work;               // row slots + tickets of the exact-row tail (rescore.hip: pk_exact_work_bytes), tickets zeroed once
 };
 
 namespace {
@@ -2085,8 +2086,12 @@ int serving_score(pk_ctx *ctx, pk_serving *sv, int32_t topk, int32_t filter_seen
     if (!out_i.p || !out_s.p || !flags.p || !lst.p || !cnt.p || !lst2.p || !cnt2.p) return fail(ctx, PK_E_LAUNCH, "out of device memory (outputs)");
     const int KC = sv->fused ? pk_candidate_capacity(topk) : 0;
     const int n_wg = 128;
-    Dev exact_work((size_t)pk_exact_work_bytes(n_wg, n_items));
-    if (!exact_work.p) return fail(ctx, PK_E_LAUNCH, "out of device memory (exact rows)");
+    // the exact tail's work buffer lives with the handle: its tickets are zeroed where it is allocated, not per pass
+    Dev &exact_work = sv->exact_work;
+    if (!exact_work.p) {
+        if (!exact_work.alloc((size_t)pk_exact_work_bytes(n_wg, n_items))) return fail(ctx, PK_E_LAUNCH, "out of device memory (exact rows)");
+        CK(pk_exact_work_init(st, exact_work.p, n_wg, n_items));
+    }
     if (KC == 0) {
         // beyond the fused sweep (topk > 52 or rank > 256): every user through the exact fp64 row kernel
         DMat E(n_users, K);
@@ -2101,16 +2106,19 @@ int serving_score(pk_ctx *ctx, pk_serving *sv, int32_t topk, int32_t filter_seen
         const int Kx = approx ? sv->Kx_full : K, ld32 = sv->ld32;
         DMat Ex(n_users, Kx);
         if (!Ex.ok()) return fail(ctx, PK_E_LAUNCH, "out of device memory (E)");
+        bool counters_zeroed = false;
         if (approx && sv->q20_img && topk <= 20) {      // (scoring.py: PACKED_MAX_TOPK — longer lists keep the fp32 image)
             // K4q: the packed image — E'[:, :K], the certified weight w in column K, zeros behind it
             Plan &P = Ts.plan;
             const size_t need = (size_t)P.n_slots * Kx * 8;
             if (need > P.partial.bytes && !P.partial.alloc(need)) return fail(ctx, PK_E_LAUNCH, "out of device memory (fold-in partials)");
-            CK(pk_fold_q20(st, all.nt, P.task_row.as<int32_t>() + all.t0, P.task_begin.as<int64_t>() + all.t0,
-                           P.task_end.as<int64_t>() + all.t0, P.task_slot.as<int32_t>() + all.t0, all.nl,
-                           P.long_row.as<int32_t>() + all.l0, P.long_sb.as<int32_t>() + all.l0, P.long_se.as<int32_t>() + all.l0,
-                           Ts.indices.as<int32_t>(), Ts.values.p, Ts.val_kind, sv->q20_img, sv->q20_tab.as<double>(), n_items, K, Kx,
-                           Ex.p(), Kx, P.partial.as<double>()));
+            // ... and the two list counters of the pass (cnt2, below) zeroed by the fold-in's fix-up launch (scoring.py: fold_zeroes)
+            CK(pk_fold_q20_zero(st, all.nt, P.task_row.as<int32_t>() + all.t0, P.task_begin.as<int64_t>() + all.t0,
+                                P.task_end.as<int64_t>() + all.t0, P.task_slot.as<int32_t>() + all.t0, all.nl,
+                                P.long_row.as<int32_t>() + all.l0, P.long_sb.as<int32_t>() + all.l0, P.long_se.as<int32_t>() + all.l0,
+                                Ts.indices.as<int32_t>(), Ts.values.p, Ts.val_kind, sv->q20_img, sv->q20_tab.as<double>(), n_items, K, Kx,
+                                Ex.p(), Kx, P.partial.as<double>(), cnt2.as<int32_t>(), 2));
+            counters_zeroed = true;
         } else if (approx) CK(spmm(ctx, Ts, sv->V32.p, PK_VAL_F32, ld32, Kx, Ex.p(), Kx, all));
         else CK(spmm(ctx, Ts, V.p(), PK_VAL_F64, K, K, Ex.p(), Kx, all));
         const double *w = approx ? Ex.p() + K : nullptr;
@@ -2176,7 +2184,7 @@ int serving_score(pk_ctx *ctx, pk_serving *sv, int32_t topk, int32_t filter_seen
         }
         // the lists of users to re-do are appended by the re-scoring kernel itself (scoring.py: fused lists): cnt2[0] counts
         // the re-fold list (lst), cnt2[1] the final list for the exact-row kernel (lst2)
-        CK(pk_zero_i32(st, cnt2.as<int32_t>(), 2));
+        if (!counters_zeroed) CK(pk_zero_i32(st, cnt2.as<int32_t>(), 2));
         int32_t *c_refold = cnt2.as<int32_t>(), *c_final = cnt2.as<int32_t>() + 1;
         CK(pk_rescore_topk_rows_norms_f64(st, n_users, nullptr, nullptr, n_users, n_items, K, V.p(), K, approx ? sv->V32.as<float>() : nullptr, approx ? ld32 : 0,
                                           Ex.p(), Kx, w, approx ? Kx : 0, 0, seen_ptr, KC, splits, cs.as<float>(), ci.as<int32_t>(), topk, vmax,

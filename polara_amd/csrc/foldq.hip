@@ -489,10 +489,15 @@ __global__ __launch_bounds__(256) void fold_q20_kernel(
     }
 }
 
-// out[row, :] = sum of the row's partial slots (fixed order): the tail of a row split into several tasks
+// out[row, :] = sum of the row's partial slots (fixed order): the tail of a row split into several tasks.
+// zero[0 .. zero_n) = 0 on the way (workgroup 0): the counters of a scoring pass, whose first user is the re-scoring behind the
+// sweep — this launch sits between the fold-in and the sweep, so the reset costs the pass no launch of its own.
 __global__ __launch_bounds__(256) void fold_q20_fixup_kernel(int64_t n_long, const int32_t *__restrict__ long_row,
                                                              const int32_t *__restrict__ slot_begin, const int32_t *__restrict__ slot_end,
-                                                             const double *__restrict__ partial, int nc, double *__restrict__ out, int64_t ldo) {
+                                                             const double *__restrict__ partial, int nc, double *__restrict__ out, int64_t ldo,
+                                                             int32_t *__restrict__ zero, int zero_n) {
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < zero_n; i += blockDim.x) zero[i] = 0;
     const int64_t r = blockIdx.x;
     if (r >= n_long) return;
     const int s0 = slot_begin[r], s1 = slot_end[r];
@@ -527,34 +532,50 @@ static void launch_fold_q20(hipStream_t st, int L, int64_t n_tasks, const int32_
 #undef PK_FOLDQ
 }
 
+// pk_fold_q20 that also zeroes zero_dev[0 .. zero_n) (int32 device counters; zero_n == 0: nothing) in its fix-up launch —
+// which then runs even without a split row, as one workgroup that only zeroes
+extern "C" int pk_fold_q20_zero(void *stream, int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
+                                const int64_t *task_end_dev, const int32_t *task_slot_dev, int64_t n_long,
+                                const int32_t *long_row_dev, const int32_t *long_slot_begin_dev, const int32_t *long_slot_end_dev,
+                                const int32_t *indices_dev, const void *vals_dev, int val_kind, const void *img_dev,
+                                const double *tab_dev, int64_t n_items, int32_t K, int32_t Kx, double *out_dev, int64_t ldo,
+                                double *partial_dev, int32_t *zero_dev, int32_t zero_n) {
+    const int L = q20_lanes(K);
+    PK_REQUIRE(L != 0 && n_tasks >= 0 && Kx >= K + 1 && ldo >= Kx, "pk_fold_q20: bad sizes (K=%d, Kx=%d)", K, Kx);
+    PK_REQUIRE(n_items >= 1 && n_items < (1 << 24) && n_items * L * 16 < ((int64_t)1 << 32), "pk_fold_q20: image beyond 32-bit offsets");
+    PK_REQUIRE(n_long == 0 || partial_dev != nullptr, "pk_fold_q20: partial buffer required");
+    PK_REQUIRE(val_kind == PK_VAL_F32 || val_kind == PK_VAL_F64, "pk_fold_q20: bad val_kind %d", val_kind);
+    PK_REQUIRE(zero_n >= 0 && zero_n <= (1 << 20) && (zero_n == 0 || zero_dev != nullptr), "pk_fold_q20: bad counter range");
+    hipStream_t st = pk_stream(stream);
+    if (n_tasks == 0) n_long = 0;      // nothing to fold: only the counters are left to do
+    if (n_tasks > 0) {
+        const uint4 *img = static_cast<const uint4 *>(img_dev);
+        const double kappa = q20_kappa(K);
+        if (val_kind == PK_VAL_F32)
+            launch_fold_q20<float>(st, L, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev, vals_dev, img,
+                                   tab_dev, kappa, K, Kx, out_dev, ldo, partial_dev);
+        else
+            launch_fold_q20<double>(st, L, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev, vals_dev, img,
+                                    tab_dev, kappa, K, Kx, out_dev, ldo, partial_dev);
+        PK_CHECK_LAUNCH("fold_q20_kernel");
+    }
+    if (n_long > 0 || zero_n > 0) {
+        hipLaunchKernelGGL(fold_q20_fixup_kernel, dim3((unsigned)(n_long > 0 ? n_long : 1)), dim3(256), 0, st, n_long, long_row_dev,
+                           long_slot_begin_dev, long_slot_end_dev, partial_dev, Kx, out_dev, ldo, zero_dev, (int)zero_n);
+        PK_CHECK_LAUNCH("fold_q20_fixup_kernel");
+    }
+    return PK_OK;
+}
+
 extern "C" int pk_fold_q20(void *stream, int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
                            const int64_t *task_end_dev, const int32_t *task_slot_dev, int64_t n_long,
                            const int32_t *long_row_dev, const int32_t *long_slot_begin_dev, const int32_t *long_slot_end_dev,
                            const int32_t *indices_dev, const void *vals_dev, int val_kind, const void *img_dev,
                            const double *tab_dev, int64_t n_items, int32_t K, int32_t Kx, double *out_dev, int64_t ldo,
                            double *partial_dev) {
-    const int L = q20_lanes(K);
-    PK_REQUIRE(L != 0 && n_tasks >= 0 && Kx >= K + 1 && ldo >= Kx, "pk_fold_q20: bad sizes (K=%d, Kx=%d)", K, Kx);
-    PK_REQUIRE(n_items >= 1 && n_items < (1 << 24) && n_items * L * 16 < ((int64_t)1 << 32), "pk_fold_q20: image beyond 32-bit offsets");
-    PK_REQUIRE(n_long == 0 || partial_dev != nullptr, "pk_fold_q20: partial buffer required");
-    PK_REQUIRE(val_kind == PK_VAL_F32 || val_kind == PK_VAL_F64, "pk_fold_q20: bad val_kind %d", val_kind);
-    if (n_tasks == 0) return PK_OK;
-    hipStream_t st = pk_stream(stream);
-    const uint4 *img = static_cast<const uint4 *>(img_dev);
-    const double kappa = q20_kappa(K);
-    if (val_kind == PK_VAL_F32)
-        launch_fold_q20<float>(st, L, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev, vals_dev, img,
-                               tab_dev, kappa, K, Kx, out_dev, ldo, partial_dev);
-    else
-        launch_fold_q20<double>(st, L, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev, vals_dev, img,
-                                tab_dev, kappa, K, Kx, out_dev, ldo, partial_dev);
-    PK_CHECK_LAUNCH("fold_q20_kernel");
-    if (n_long > 0) {
-        hipLaunchKernelGGL(fold_q20_fixup_kernel, dim3((unsigned)n_long), dim3(256), 0, st, n_long, long_row_dev, long_slot_begin_dev,
-                           long_slot_end_dev, partial_dev, Kx, out_dev, ldo);
-        PK_CHECK_LAUNCH("fold_q20_fixup_kernel");
-    }
-    return PK_OK;
+    return pk_fold_q20_zero(stream, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, n_long, long_row_dev,
+                            long_slot_begin_dev, long_slot_end_dev, indices_dev, vals_dev, val_kind, img_dev, tab_dev, n_items, K, Kx,
+                            out_dev, ldo, partial_dev, nullptr, 0);
 }
 
 // eager load of this translation unit's code object (pk_warm_up, api.cpp): the runtime loads a code object at the first

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
     const float *__restrict__ cand_score, const int32_t *__restrict__ cand_idx, int topk, double vmax,
     int64_t *__restrict__ out_idx, double *__restrict__ out_score, int32_t *__restrict__ flags,
     int32_t *__restrict__ flagged_list, int32_t *__restrict__ flagged_count, int32_t flagged_offset,
-    const float *__restrict__ item_norm) {
+    const float *__restrict__ item_norm, const int64_t *__restrict__ out_perm) {
     constexpr int UPW = 64 / (SEG * LPC);
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -307,7 +307,10 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
             flag |= (!e_exact && delta > 0.0 && s_k - tau_cert > bound + delta) ? 4 : 1;
     }
     if (live && q == 0 && t < topk) {
-        out_idx[user * topk + t] = (my_i == PK_IDX_NONE) ? -1 : (int64_t)my_i;
+        // out_perm: the list goes straight to the caller's row of this user (scoring.recommend sweeps the users in activity
+        // order); scores and flags stay in sweep order
+        const int64_t irow = out_perm ? out_perm[user] : user;
+        out_idx[irow * topk + t] = (my_i == PK_IDX_NONE) ? -1 : (int64_t)my_i;
         if (out_score) out_score[user * topk + t] = my_s;
     }
     if (live && q == 0 && t == 0) {
@@ -319,17 +322,19 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
     }
 }
 
-extern "C" int pk_rescore_topk_rows_norms_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
-                                             const int32_t *n_rows_dev, int64_t n_users,
-                                             int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
-                                             const float *V32_dev, int64_t ldv32,
-                                             const double *E_dev, int64_t lde, const double *e_err_dev,
-                                             int64_t e_err_ld, int32_t e_exact,
-                                             const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                                             double v_row_norm_max, int64_t *out_idx_dev, double *out_score_dev,
-                                             int32_t *flags_dev, int32_t *flagged_list_dev, int32_t *flagged_count_dev,
-                                             int32_t flagged_offset, const float *item_norm_dev) {
+// out_perm_dev (int64 [n_users], may be NULL): the out_idx row of user u is written to row out_perm[u] (out_score and flags
+// rows stay where they are) — the pass then needs no scatter of its lists at the end
+extern "C" int pk_rescore_topk_rows_perm_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
+                                            const int32_t *n_rows_dev, int64_t n_users,
+                                            int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
+                                            const float *V32_dev, int64_t ldv32,
+                                            const double *E_dev, int64_t lde, const double *e_err_dev,
+                                            int64_t e_err_ld, int32_t e_exact,
+                                            const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
+                                            const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
+                                            double v_row_norm_max, int64_t *out_idx_dev, double *out_score_dev,
+                                            int32_t *flags_dev, int32_t *flagged_list_dev, int32_t *flagged_count_dev,
+                                            int32_t flagged_offset, const float *item_norm_dev, const int64_t *out_perm_dev) {
     PK_REQUIRE((flagged_list_dev == nullptr) == (flagged_count_dev == nullptr), "pk_rescore_topk_f64: flagged list without its counter");
     PK_REQUIRE(n_users >= 1 && K >= 1 && K <= 256 && ldv >= K && lde >= K, "pk_rescore_topk_f64: bad sizes");
     PK_REQUIRE(n_rows >= 0 && n_rows <= n_users, "pk_rescore_topk_f64: bad row count");
@@ -345,7 +350,8 @@ extern "C" int pk_rescore_topk_rows_norms_f64(void *stream, int64_t n_rows, cons
     hipLaunchKernelGGL((rescore_topk_kernel<SEGV, LPCV, S4>), dim3((unsigned)pk_ceil_div(n_rows, 4 * (64 / (SEGV * LPCV)))), \
                        dim3(256), 0, pk_stream(stream), n_rows, rows_dev, n_rows_dev, n_users, n_items, K, V_dev, ldv, V32_dev, ldv32, E_dev, lde, \
                        e_err_dev, e_err_ld, e_exact, seen_ptr_dev, KC, splits, cand_score_dev, cand_idx_dev, topk, v_row_norm_max,   \
-                       out_idx_dev, out_score_dev, flags_dev, flagged_list_dev, flagged_count_dev, flagged_offset, item_norm_dev)
+                       out_idx_dev, out_score_dev, flags_dev, flagged_list_dev, flagged_count_dev, flagged_offset, item_norm_dev, \
+                       out_perm_dev)
     if (seg == 16) {
         if (lpc_req == 1) PK_RESCORE(16, 1);
         else if (lpc_req == 4) PK_RESCORE(16, 4);
@@ -363,6 +369,23 @@ extern "C" int pk_rescore_topk_rows_norms_f64(void *stream, int64_t n_rows, cons
 #undef PK_RESCORE_X
     PK_CHECK_LAUNCH("rescore_topk_kernel");
     return PK_OK;
+}
+
+extern "C" int pk_rescore_topk_rows_norms_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
+                                             const int32_t *n_rows_dev, int64_t n_users,
+                                             int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
+                                             const float *V32_dev, int64_t ldv32,
+                                             const double *E_dev, int64_t lde, const double *e_err_dev,
+                                             int64_t e_err_ld, int32_t e_exact,
+                                             const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
+                                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
+                                             double v_row_norm_max, int64_t *out_idx_dev, double *out_score_dev,
+                                             int32_t *flags_dev, int32_t *flagged_list_dev, int32_t *flagged_count_dev,
+                                             int32_t flagged_offset, const float *item_norm_dev) {
+    return pk_rescore_topk_rows_perm_f64(stream, n_rows, rows_dev, n_rows_dev, n_users, n_items, K, V_dev, ldv, V32_dev, ldv32, E_dev,
+                                         lde, e_err_dev, e_err_ld, e_exact, seen_ptr_dev, KC, splits, cand_score_dev, cand_idx_dev, topk,
+                                         v_row_norm_max, out_idx_dev, out_score_dev, flags_dev, flagged_list_dev, flagged_count_dev,
+                                         flagged_offset, item_norm_dev, nullptr);
 }
 
 extern "C" int pk_rescore_topk_rows_list_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
@@ -564,15 +587,27 @@ extern "C" int pk_fold_rows_f64(void *stream, int64_t cap, const int32_t *list_d
 #define PK_EXACT_TOPK_MAX 256
 #define PK_EXACT_CHUNKS_MAX 8192
 #define PK_EXACT_FAST_ROWS 1024
-static int64_t exact_per_row(int64_t n_items) {
-    // one-workgroup kernel: fp64 score + 1 class byte per item; chunk kernels: per chunk of PK_EXACT_CHUNK items at most
-    // min(PK_EXACT_TOPK_MAX, n_items) candidates of 13 bytes (score, index, class); padded to 16 bytes
-    const int64_t slow = n_items * 8 + ((n_items + 15) / 16) * 16;
+// one-workgroup kernel: fp64 score + 1 class byte per item; chunk kernels: per chunk of PK_EXACT_CHUNK items at most
+// min(PK_EXACT_TOPK_MAX, n_items) candidates of 13 bytes (score, index, class); padded to 16 bytes
+static int64_t exact_slow_bytes(int64_t n_items) { return n_items * 8 + ((n_items + 15) / 16) * 16; }
+static int64_t exact_fast_bytes(int64_t n_items) {
     const int64_t kmax = n_items < PK_EXACT_TOPK_MAX ? n_items : PK_EXACT_TOPK_MAX;
-    const int64_t fast = ((pk_ceil_div(n_items, PK_EXACT_CHUNK) * kmax * 13 + 15) / 16) * 16;
+    return ((pk_ceil_div(n_items, PK_EXACT_CHUNK) * kmax * 13 + 15) / 16) * 16;
+}
+static int64_t exact_per_row(int64_t n_items) {
+    const int64_t slow = exact_slow_bytes(n_items), fast = exact_fast_bytes(n_items);
     return slow > fast ? slow : fast;
 }
-extern "C" int64_t pk_exact_work_bytes(int32_t n_rows, int64_t n_items) { return (int64_t)n_rows * exact_per_row(n_items); }
+// The work buffer of n_rows row slots.  The host-count route uses the slots one after the other (chunk lists, then the
+// one-workgroup kernel in the same slots): n_rows * exact_per_row bytes.  The device-list route does both in ONE launch, so
+// its two roles have regions of their own — n_rows chunk-list slots, then n_rows one-workgroup slots — and behind them one
+// int32 ticket per row slot (exact_list_kernel), which must be zero when the buffer is first used: pk_exact_work_init.
+static int64_t exact_ticket_off(int32_t n_rows, int64_t n_items) {
+    return (int64_t)n_rows * (exact_fast_bytes(n_items) + exact_slow_bytes(n_items));
+}
+extern "C" int64_t pk_exact_work_bytes(int32_t n_rows, int64_t n_items) {
+    return exact_ticket_off(n_rows, n_items) + (((int64_t)n_rows * 4 + 15) / 16) * 16;
+}
 
 struct Best {
     int cls;  // 0 = unseen (ranks first), 1 = seen, 2 = taken / none
@@ -588,23 +623,25 @@ __device__ __forceinline__ bool best_before(const Best &a, const Best &b) {
 // Every workgroup walks the list from `first_row` with stride gridDim.x (one work slice per workgroup): the number of
 // listed users may live on the device (n_rows_dev), so that the caller never has to read it back before launching.
 // by_user: results go to row `user` of the outputs instead of row r of the list.
-__global__ __launch_bounds__(256) void score_exact_rows_kernel(
-    int32_t n_rows_host, const int32_t *__restrict__ n_rows_dev, int32_t first_row, const int32_t *__restrict__ rows,
-    int by_user, int64_t n_items, int K, const double *__restrict__ V, int64_t ldv,
+// (the body of score_exact_rows_kernel: workgroup `wg` of `n_wg`, scratch = its own row slot of the work buffer;
+// out_perm: the rows of out_idx — not of out_score — go to out_perm[row] instead, scoring.recommend's producer-side order)
+__device__ __forceinline__ void exact_rows_body(
+    int wg, int n_wg, int32_t n_rows, int32_t first_row, const int32_t *__restrict__ rows,
+    int by_user, const int64_t *__restrict__ out_perm, int64_t n_items, int K, const double *__restrict__ V, int64_t ldv,
     const double *__restrict__ E, int64_t lde, const int64_t *__restrict__ seen_ptr,
     const int32_t *__restrict__ seen_idx, int topk, int64_t *__restrict__ out_idx,
-    double *__restrict__ out_score, unsigned char *__restrict__ work, int64_t per_row) {
+    double *__restrict__ out_score, unsigned char *slot) {
     extern __shared__ double s_e[];   // the user's E row: K doubles (dynamic: any rank fits — the fused sweep stops at 256)
     __shared__ int s_cls[256];
     __shared__ double s_s[256];
     __shared__ int s_i[256];
     const int tid = threadIdx.x;
-    const int32_t n_rows = n_rows_dev ? *n_rows_dev : n_rows_host;
-    double *score = reinterpret_cast<double *>(work + (int64_t)blockIdx.x * per_row);
-    unsigned char *cls = work + (int64_t)blockIdx.x * per_row + n_items * 8;
-  for (int32_t r = first_row + blockIdx.x; r < n_rows; r += gridDim.x) {
+    double *score = reinterpret_cast<double *>(slot);
+    unsigned char *cls = slot + n_items * 8;
+  for (int32_t r = first_row + wg; r < n_rows; r += n_wg) {
     const int64_t user = rows[r];
     const int64_t orow = by_user ? user : (int64_t)r;
+    const int64_t irow = (by_user && out_perm) ? out_perm[user] : orow;
     __syncthreads();   // the previous user's s_e / cls are no longer read
 
     for (int c = tid; c < K; c += 256) s_e[c] = E[user * lde + c];
@@ -652,13 +689,23 @@ __global__ __launch_bounds__(256) void score_exact_rows_kernel(
         }
         if (tid == 0) {
             const bool ok = s_cls[0] < 2;
-            out_idx[orow * topk + t] = ok ? (int64_t)s_i[0] : -1;
+            out_idx[irow * topk + t] = ok ? (int64_t)s_i[0] : -1;
             if (out_score) out_score[orow * topk + t] = ok ? s_s[0] : -INFINITY;
             if (ok) cls[s_i[0]] = 2;
         }
         __syncthreads();
     }
   }
+}
+
+__global__ __launch_bounds__(256) void score_exact_rows_kernel(
+    int32_t n_rows_host, const int32_t *__restrict__ n_rows_dev, int32_t first_row, const int32_t *__restrict__ rows,
+    int by_user, int64_t n_items, int K, const double *__restrict__ V, int64_t ldv,
+    const double *__restrict__ E, int64_t lde, const int64_t *__restrict__ seen_ptr,
+    const int32_t *__restrict__ seen_idx, int topk, int64_t *__restrict__ out_idx,
+    double *__restrict__ out_score, unsigned char *__restrict__ work, int64_t per_row, const int64_t *__restrict__ out_perm) {
+    exact_rows_body((int)blockIdx.x, (int)gridDim.x, n_rows_dev ? *n_rows_dev : n_rows_host, first_row, rows, by_user, out_perm,
+                    n_items, K, V, ldv, E, lde, seen_ptr, seen_idx, topk, out_idx, out_score, work + (int64_t)blockIdx.x * per_row);
 }
 
 // ---- the same result from the whole chip -------------------------------------------------------------------------
@@ -694,11 +741,13 @@ __device__ __forceinline__ Best best_wave_min(Best b) {
     return b;
 }
 
-__global__ __launch_bounds__(256) void exact_chunk_kernel(
-    int32_t n_rows_host, const int32_t *__restrict__ n_rows_dev, int32_t row_slots, const int32_t *__restrict__ rows,
+// (the body of exact_chunk_kernel for ONE listed row r: the chunk's best ksel entries of that user, in order, into
+// row slot r of the work buffer)
+__device__ __forceinline__ void exact_chunk_row(
+    int64_t chunk, int32_t r, const int32_t *__restrict__ rows,
     int64_t n_items, int K, const double *__restrict__ V, int64_t ldv, const double *__restrict__ E, int64_t lde,
     const int64_t *__restrict__ seen_ptr, const int32_t *__restrict__ seen_idx, int ksel,
-    unsigned char *__restrict__ work, int64_t per_row, int64_t idx_off, int64_t cls_off) {
+    unsigned char *work, int64_t per_row, int64_t idx_off, int64_t cls_off) {
     extern __shared__ __attribute__((aligned(16))) double s_e[];   // K doubles
     __shared__ double s_score[PK_EXACT_CHUNK];
     __shared__ unsigned char s_cls[PK_EXACT_CHUNK];
@@ -706,13 +755,10 @@ __global__ __launch_bounds__(256) void exact_chunk_kernel(
     __shared__ double s_ws[4];
     __shared__ int s_wi[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int32_t n_rows = n_rows_dev ? *n_rows_dev : n_rows_host;
-    if (n_rows > row_slots) n_rows = row_slots;
-    const int64_t chunk = blockIdx.x;
     const int64_t i0 = chunk * PK_EXACT_CHUNK;
     const int cn = (int)((n_items - i0 < PK_EXACT_CHUNK) ? (n_items - i0) : PK_EXACT_CHUNK);
     const bool vvec2 = ((ldv & 1) == 0) && ((((uintptr_t)V) & 15) == 0);
-    for (int32_t r = blockIdx.y; r < n_rows; r += gridDim.y) {
+    {
         const int64_t user = rows[r];
         __syncthreads();   // the previous user's s_e / s_score / s_cls are no longer read
         for (int c = tid; c < K; c += 256) s_e[c] = E[user * lde + c];
@@ -775,20 +821,33 @@ __global__ __launch_bounds__(256) void exact_chunk_kernel(
     }
 }
 
-__global__ __launch_bounds__(256) void exact_merge_kernel(
+__global__ __launch_bounds__(256) void exact_chunk_kernel(
     int32_t n_rows_host, const int32_t *__restrict__ n_rows_dev, int32_t row_slots, const int32_t *__restrict__ rows,
-    int by_user, int n_chunks, int ksel, int topk, int64_t *__restrict__ out_idx, double *__restrict__ out_score,
-    const unsigned char *__restrict__ work, int64_t per_row, int64_t idx_off, int64_t cls_off) {
+    int64_t n_items, int K, const double *__restrict__ V, int64_t ldv, const double *__restrict__ E, int64_t lde,
+    const int64_t *__restrict__ seen_ptr, const int32_t *__restrict__ seen_idx, int ksel,
+    unsigned char *__restrict__ work, int64_t per_row, int64_t idx_off, int64_t cls_off) {
+    int32_t n_rows = n_rows_dev ? *n_rows_dev : n_rows_host;
+    if (n_rows > row_slots) n_rows = row_slots;
+    for (int32_t r = blockIdx.y; r < n_rows; r += gridDim.y)
+        exact_chunk_row(blockIdx.x, r, rows, n_items, K, V, ldv, E, lde, seen_ptr, seen_idx, ksel, work, per_row, idx_off, cls_off);
+}
+
+// (the body of exact_merge_kernel for ONE listed row r: the sorted chunk lists of row slot r merged by their heads;
+// out_perm as in exact_rows_body.  `work` carries no __restrict__: in the one-launch form other workgroups of the same
+// kernel wrote the lists)
+__device__ __forceinline__ void exact_merge_row(
+    int32_t r, const int32_t *__restrict__ rows, int by_user, const int64_t *__restrict__ out_perm, int n_chunks, int ksel,
+    int topk, int64_t *__restrict__ out_idx, double *__restrict__ out_score,
+    const unsigned char *work, int64_t per_row, int64_t idx_off, int64_t cls_off) {
     extern __shared__ int s_cur[];   // n_chunks cursors into the (sorted) chunk lists
     __shared__ int s_wc[4];
     __shared__ double s_ws[4];
     __shared__ int s_wi[4];
     __shared__ int s_wk[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int32_t n_rows = n_rows_dev ? *n_rows_dev : n_rows_host;
-    if (n_rows > row_slots) n_rows = row_slots;
-    for (int32_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+    {
         const int64_t orow = by_user ? (int64_t)rows[r] : (int64_t)r;
+        const int64_t irow = (by_user && out_perm) ? out_perm[orow] : orow;
         const unsigned char *base = work + (int64_t)r * per_row;
         const double *c_s = reinterpret_cast<const double *>(base);
         const int32_t *c_i = reinterpret_cast<const int32_t *>(base + idx_off);
@@ -845,7 +904,7 @@ __global__ __launch_bounds__(256) void exact_merge_kernel(
                     }
                 }
                 const bool ok = w.cls < 2;
-                out_idx[orow * topk + t] = ok ? (int64_t)w.idx : -1;
+                out_idx[irow * topk + t] = ok ? (int64_t)w.idx : -1;
                 if (out_score) out_score[orow * topk + t] = ok ? w.s : -INFINITY;
                 if (ok) s_cur[wk] += 1;
             }
@@ -854,22 +913,98 @@ __global__ __launch_bounds__(256) void exact_merge_kernel(
     }
 }
 
+__global__ __launch_bounds__(256) void exact_merge_kernel(
+    int32_t n_rows_host, const int32_t *__restrict__ n_rows_dev, int32_t row_slots, const int32_t *__restrict__ rows,
+    int by_user, int n_chunks, int ksel, int topk, int64_t *__restrict__ out_idx, double *__restrict__ out_score,
+    const unsigned char *__restrict__ work, int64_t per_row, int64_t idx_off, int64_t cls_off) {
+    int32_t n_rows = n_rows_dev ? *n_rows_dev : n_rows_host;
+    if (n_rows > row_slots) n_rows = row_slots;
+    for (int32_t r = blockIdx.x; r < n_rows; r += gridDim.x)
+        exact_merge_row(r, rows, by_user, nullptr, n_chunks, ksel, topk, out_idx, out_score, work, per_row, idx_off, cls_off);
+}
+
+// ---- the device-list route in ONE launch ---------------------------------------------------------------------------
+// With the count on the device the three kernels above were three launches that, in the normal case of an empty list, only
+// read the count and left (25 + 18 + 28 us inside a two-stream loop of ML-20M-shaped passes).  Here workgroups take their
+// role from the block index: the first n_chunks * gy are chunk workgroups (chunk = block % n_chunks; rows y, y + gy, ...),
+// the last n_wg_slow take the rows beyond the slots with the one-workgroup body.  The merge of a row is done by the LAST
+// chunk workgroup of that row to arrive: each publishes its list (__threadfence) and draws a ticket (one atomicAdd on the
+// row's word); who draws n_chunks - 1 knows every list of the row is visible, merges, and puts the ticket back to zero for
+// the next launch on this buffer.  No workgroup ever waits for another.  Same bodies, same selection and summation order:
+// the results are those of the three kernels bit for bit.
+__global__ __launch_bounds__(256) void exact_list_kernel(
+    const int32_t *__restrict__ n_rows_dev, int32_t row_slots, int n_chunks, int gy, int n_wg_slow,
+    const int32_t *__restrict__ rows, const int64_t *__restrict__ out_perm, int64_t n_items, int K,
+    const double *__restrict__ V, int64_t ldv, const double *__restrict__ E, int64_t lde,
+    const int64_t *__restrict__ seen_ptr, const int32_t *__restrict__ seen_idx, int ksel, int topk,
+    int64_t *__restrict__ out_idx, double *__restrict__ out_score, unsigned char *work, int64_t per_row,
+    int64_t idx_off, int64_t cls_off, unsigned char *slow_work, int64_t slow_per_row, int32_t *tickets) {
+    __shared__ int s_last;
+    const int32_t count = *n_rows_dev;
+    if (count <= 0) return;
+    const int n_chunk_wg = n_chunks * gy;
+    if ((int)blockIdx.x >= n_chunk_wg) {
+        const int wg = (int)blockIdx.x - n_chunk_wg;
+        if (count > row_slots)
+            exact_rows_body(wg, n_wg_slow, count, row_slots, rows, 1, out_perm, n_items, K, V, ldv, E, lde, seen_ptr, seen_idx, topk,
+                            out_idx, out_score, slow_work + (int64_t)wg * slow_per_row);
+        return;
+    }
+    const int chunk = (int)blockIdx.x % n_chunks, y = (int)blockIdx.x / n_chunks;
+    const int32_t n_rows = count < row_slots ? count : row_slots;
+    for (int32_t r = y; r < n_rows; r += gy) {
+        exact_chunk_row(chunk, r, rows, n_items, K, V, ldv, E, lde, seen_ptr, seen_idx, ksel, work, per_row, idx_off, cls_off);
+        // (the chunk body ends on a barrier behind thread 0's stores of the list)
+        if (threadIdx.x == 0) {
+            __threadfence();
+            s_last = atomicAdd(&tickets[r], 1) == n_chunks - 1;
+        }
+        __syncthreads();
+        if (s_last) {
+            __threadfence();
+            exact_merge_row(r, rows, 1, out_perm, n_chunks, ksel, topk, out_idx, out_score, work, per_row, idx_off, cls_off);
+            if (threadIdx.x == 0) tickets[r] = 0;
+        }
+    }
+}
+
 // rows [0, min(count, row_slots)) through the chunk kernels when they apply, the rest (or everything) through the
-// one-workgroup kernel; `count` on the host (n_rows_dev == nullptr) or on the device
+// one-workgroup kernel; `count` on the host (n_rows_dev == nullptr: up to three launches, one region of row slots) or on
+// the device (one launch, the layout of pk_exact_work_bytes)
 static int exact_launch(hipStream_t st, int32_t n_rows_host, const int32_t *n_rows_dev, int32_t row_slots,
                         const int32_t *rows_dev, int by_user, int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
                         const double *E_dev, int64_t lde, const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev,
-                        int32_t topk, int64_t *out_idx_dev, double *out_score_dev, unsigned char *work, int32_t n_wg_slow) {
-    const int64_t per_row = exact_per_row(n_items);
+                        int32_t topk, int64_t *out_idx_dev, double *out_score_dev, unsigned char *work, int32_t n_wg_slow,
+                        const int64_t *out_perm_dev) {
     const int64_t n_chunks = pk_ceil_div(n_items, PK_EXACT_CHUNK);
     const bool fast = row_slots > 0 && topk <= PK_EXACT_TOPK_MAX && n_chunks <= PK_EXACT_CHUNKS_MAX && (size_t)K * 8 <= 48 * 1024;
+    const int ksel = (int)(topk < n_items ? topk : n_items);   // <= PK_EXACT_TOPK_MAX when fast: what exact_fast_bytes provides for
+    const ExactLayout lay = exact_layout(n_chunks, ksel);
+    int64_t gy = 2048 / n_chunks;
+    if (gy < 1) gy = 1;
+    if (gy > row_slots) gy = row_slots;
+    if (n_rows_dev) {
+        const int64_t fast_row = exact_fast_bytes(n_items), slow_row = exact_slow_bytes(n_items);
+        unsigned char *slow_work = work + (int64_t)row_slots * fast_row;
+        if (!fast) {
+            hipLaunchKernelGGL(score_exact_rows_kernel, dim3((unsigned)n_wg_slow), dim3(256), (size_t)K * 8, st, 0, n_rows_dev, 0,
+                               rows_dev, by_user, n_items, K, V_dev, ldv, E_dev, lde, seen_ptr_dev, seen_idx_dev, topk, out_idx_dev,
+                               out_score_dev, slow_work, slow_row, out_perm_dev);
+            PK_CHECK_LAUNCH("score_exact_rows_kernel");
+            return PK_OK;
+        }
+        int32_t *tickets = reinterpret_cast<int32_t *>(work + exact_ticket_off(row_slots, n_items));
+        const size_t lds = (size_t)K * 8 > (size_t)n_chunks * 4 ? (size_t)K * 8 : (size_t)n_chunks * 4;
+        hipLaunchKernelGGL(exact_list_kernel, dim3((unsigned)(n_chunks * gy + n_wg_slow)), dim3(256), lds, st, n_rows_dev, row_slots,
+                           (int)n_chunks, (int)gy, n_wg_slow, rows_dev, out_perm_dev, n_items, K, V_dev, ldv, E_dev, lde, seen_ptr_dev,
+                           seen_idx_dev, ksel, topk, out_idx_dev, out_score_dev, work, fast_row, lay.idx_off, lay.cls_off, slow_work,
+                           slow_row, tickets);
+        PK_CHECK_LAUNCH("exact_list_kernel");
+        return PK_OK;
+    }
+    const int64_t per_row = exact_per_row(n_items);
     int32_t first_slow = 0;
     if (fast) {
-        const int ksel = (int)(topk < n_items ? topk : n_items);   // <= PK_EXACT_TOPK_MAX: what exact_per_row provides for
-        const ExactLayout lay = exact_layout(n_chunks, ksel);
-        int64_t gy = 2048 / n_chunks;
-        if (gy < 1) gy = 1;
-        if (gy > row_slots) gy = row_slots;
         hipLaunchKernelGGL(exact_chunk_kernel, dim3((unsigned)n_chunks, (unsigned)gy), dim3(256), (size_t)K * 8, st, n_rows_host,
                            n_rows_dev, row_slots, rows_dev, n_items, K, V_dev, ldv, E_dev, lde, seen_ptr_dev, seen_idx_dev, ksel,
                            work, per_row, lay.idx_off, lay.cls_off);
@@ -879,11 +1014,11 @@ static int exact_launch(hipStream_t st, int32_t n_rows_host, const int32_t *n_ro
                            per_row, lay.idx_off, lay.cls_off);
         PK_CHECK_LAUNCH("exact_merge_kernel");
         first_slow = row_slots;
-        if (!n_rows_dev && n_rows_host <= row_slots) return PK_OK;
+        if (n_rows_host <= row_slots) return PK_OK;
     }
     hipLaunchKernelGGL(score_exact_rows_kernel, dim3((unsigned)n_wg_slow), dim3(256), (size_t)K * 8, st, n_rows_host, n_rows_dev,
                        first_slow, rows_dev, by_user, n_items, K, V_dev, ldv, E_dev, lde, seen_ptr_dev, seen_idx_dev, topk,
-                       out_idx_dev, out_score_dev, work, per_row);
+                       out_idx_dev, out_score_dev, work, per_row, nullptr);
     PK_CHECK_LAUNCH("score_exact_rows_kernel");
     return PK_OK;
 }
@@ -902,22 +1037,42 @@ extern "C" int pk_score_exact_rows_f64(void *stream, int32_t n_rows, const int32
     const int32_t fast_rows = n_rows <= PK_EXACT_FAST_ROWS ? n_rows : 0;
     return exact_launch(pk_stream(stream), n_rows, nullptr, fast_rows, rows_dev, 0, n_items, K, V_dev, ldv, E_dev, lde,
                         seen_ptr_dev, seen_idx_dev, topk, out_idx_dev, out_score_dev, static_cast<unsigned char *>(work_dev),
-                        n_rows);
+                        n_rows, nullptr);
 }
 
 /* The same over a DEVICE-side list (pk_flag_compact): users list_dev[0 .. *count_dev), results written to the
  * rows of those users in the [n_users x topk] outputs; the work buffer has n_wg row slots (work >= pk_exact_work_bytes(n_wg,
- * n_items)): the first n_wg listed users go through the chunk kernels, any further ones share n_wg workgroups of the
- * one-workgroup kernel.  Nothing about the list visits the host, so a scoring pass needs no synchronisation. */
-extern "C" int pk_score_exact_list_f64(void *stream, int32_t n_wg, const int32_t *list_dev, const int32_t *count_dev,
-                                       int64_t n_items, int32_t K, const double *V_dev, int64_t ldv, const double *E_dev,
-                                       int64_t lde, const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev, int32_t topk,
-                                       int64_t *out_idx_dev, double *out_score_dev, void *work_dev) {
+ * n_items), its tickets zeroed once by pk_exact_work_init(n_wg, n_items)): the first n_wg listed users go through the chunk
+ * workgroups, any further ones share n_wg one-workgroup slices — one launch (exact_list_kernel).  Nothing about the list
+ * visits the host, so a scoring pass needs no synchronisation.
+ * _perm form: out_perm_dev (int64 [n_users], may be NULL) sends the out_idx row of user u to row out_perm[u]; out_score rows
+ * stay where they are. */
+extern "C" int pk_score_exact_list_perm_f64(void *stream, int32_t n_wg, const int32_t *list_dev, const int32_t *count_dev,
+                                            int64_t n_items, int32_t K, const double *V_dev, int64_t ldv, const double *E_dev,
+                                            int64_t lde, const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev, int32_t topk,
+                                            int64_t *out_idx_dev, double *out_score_dev, void *work_dev,
+                                            const int64_t *out_perm_dev) {
     PK_REQUIRE(n_wg >= 1 && n_items >= 1 && K >= 1 && K <= 8192 && topk >= 1 && list_dev && count_dev,
                "pk_score_exact_list_f64: bad sizes");
     PK_REQUIRE(ldv >= K && lde >= K && work_dev && out_idx_dev, "pk_score_exact_list_f64: bad arguments");
     return exact_launch(pk_stream(stream), 0, count_dev, n_wg, list_dev, 1, n_items, K, V_dev, ldv, E_dev, lde, seen_ptr_dev,
-                        seen_idx_dev, topk, out_idx_dev, out_score_dev, static_cast<unsigned char *>(work_dev), n_wg);
+                        seen_idx_dev, topk, out_idx_dev, out_score_dev, static_cast<unsigned char *>(work_dev), n_wg, out_perm_dev);
+}
+
+extern "C" int pk_score_exact_list_f64(void *stream, int32_t n_wg, const int32_t *list_dev, const int32_t *count_dev,
+                                       int64_t n_items, int32_t K, const double *V_dev, int64_t ldv, const double *E_dev,
+                                       int64_t lde, const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev, int32_t topk,
+                                       int64_t *out_idx_dev, double *out_score_dev, void *work_dev) {
+    return pk_score_exact_list_perm_f64(stream, n_wg, list_dev, count_dev, n_items, K, V_dev, ldv, E_dev, lde, seen_ptr_dev,
+                                        seen_idx_dev, topk, out_idx_dev, out_score_dev, work_dev, nullptr);
+}
+
+// zeroes the tickets of a work buffer of pk_exact_work_bytes(n_rows, n_items) bytes: once, where the buffer is allocated —
+// every launch leaves them zero again
+extern "C" int pk_exact_work_init(void *stream, void *work_dev, int32_t n_rows, int64_t n_items) {
+    PK_REQUIRE(work_dev && n_rows >= 1 && n_items >= 1, "pk_exact_work_init: bad arguments");
+    return pk_zero_i32(stream, reinterpret_cast<int32_t *>(static_cast<unsigned char *>(work_dev) + exact_ticket_off(n_rows, n_items)),
+                       n_rows);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -938,9 +938,10 @@ class HipOps:
                    'pk_q20_decode_f64')
         return out
 
-    def fold_q20(self, A, image, K, out, rows=None):
+    def fold_q20(self, A, image, K, out, rows=None, counters=None):
         """out[:, :K] = A @ decode(image), out[:, K] = w = A @ D (the certified weight of the image's error),
-        zeros up to out's width.  A: DeviceCSR with non-negative values; rows as in `spmm`."""
+        zeros up to out's width.  A: DeviceCSR with non-negative values; rows as in `spmm`.
+        counters (int32 device tensor): zeroed by the fold-in's fix-up launch (`fold_q20_zero`)."""
         img, tab = image
         Kx = out.shape[1]
         assert out.dtype == torch.float64 and out.stride(1) == 1 and Kx >= K + 1 and img.shape[0] == A.shape[1]
@@ -949,13 +950,25 @@ class HipOps:
         meta = None
         if self.timers is not None:
             meta = (A.shape[0], A.shape[1], A.nnz, Kx, A.values.element_size(), img.shape[1])
-        with self._timed('fold_q20', meta):
-            _lib.check(self.lib.pk_fold_q20(
-                self.stream(), n_tasks, _ptr(p['task_row'], t0), _ptr(p['task_begin'], t0), _ptr(p['task_end'], t0),
+        args = (self.stream(), n_tasks, _ptr(p['task_row'], t0), _ptr(p['task_begin'], t0), _ptr(p['task_end'], t0),
                 _ptr(p['task_slot'], t0), n_long, _ptr(p['long_row'], l0), _ptr(p['long_slot_begin'], l0),
                 _ptr(p['long_slot_end'], l0), _ptr(A.indices), _ptr(A.values), A.val_kind, _ptr(img), _ptr(tab),
-                int(A.shape[1]), int(K), int(Kx), _ptr(out), out.stride(0), _ptr(A.partial(Kx))), 'pk_fold_q20')
+                int(A.shape[1]), int(K), int(Kx), _ptr(out), out.stride(0), _ptr(A.partial(Kx)))
+        with self._timed('fold_q20', meta):
+            if counters is None:
+                _lib.check(self.lib.pk_fold_q20(*args), 'pk_fold_q20')
+            else:
+                assert counters.dtype == torch.int32 and counters.is_contiguous() and counters.numel() >= 1
+                _lib.check(self.lib.pk_fold_q20_zero(*args, _ptr(counters), int(counters.numel())), 'pk_fold_q20_zero')
         return out
+
+    def fold_q20_zero(self, A, image, K, out, n_counters, rows=None):
+        """`fold_q20` + `zero_counters(n_counters)` in the launches of the fold-in alone: returns the int32 [n] counters, zero
+        once the stream has passed the fold-in (its fix-up launch does it, behind the product and in front of whatever
+        follows on the stream)."""
+        c = torch.empty(int(n_counters), dtype=torch.int32, device=self.device)
+        self.fold_q20(A, image, K, out, rows=rows, counters=c)
+        return c
 
     # ---- K2 ---------------------------------------------------------------------------------
     def gram(self, A, B=None):
@@ -1371,14 +1384,16 @@ class HipOps:
         return rec[:, :, 0, 0].clone()
 
     def rescore_topk(self, V, E, n_items, seen_ptr, KC, cs, ci, topk, vmax, want_scores=True, splits=1, out=None,
-                     rows=None, n_rows_dev=None, e_err=None, e_exact=False, v32=None, flagged=None, item_norm=None):
+                     rows=None, n_rows_dev=None, e_err=None, e_exact=False, v32=None, flagged=None, item_norm=None,
+                     out_perm=None):
         """Exact fp64 re-scoring + certification.  rows (int32 tensor): only these users are re-done (outputs
         are still indexed by user: pass the full-size `out`); e_err: per-user error weight of an approximate E
         (flags bit 4 = not certified at that accuracy); v32: fp32 image of V [n_items x >= K], gathered instead
         of V while E is approximate (its rounding joins the certified error); item_norm: float32 [n_items] upper bounds of
         the rows' norms (the order of two entries is then certified against their own norms).  flagged = (list int32, count int32[1],
         offset): every user that ends up flagged is appended to that device-side list as offset + user while the
-        kernel runs (the counter is the caller's to zero: `zero_counters`)."""
+        kernel runs (the counter is the caller's to zero: `zero_counters`).  out_perm (int64 [n_users]): the id list of user
+        u goes to row out_perm[u] of out_idx (scores and flags stay at row u)."""
         assert V.stride(1) == 1 and E.stride(1) == 1
         assert v32 is None or (v32.dtype == torch.float32 and v32.stride(1) == 1 and v32.shape[1] >= E.shape[1])
         n_users, K = E.shape
@@ -1394,16 +1409,15 @@ class HipOps:
         with self._timed('rescore_topk' if rows is None else 'rescore_topk_refolded', (n_rows, KC, K)):
             fl, fc, fo = flagged if flagged is not None else (None, None, 0)
             assert item_norm is None or (item_norm.dtype == torch.float32 and item_norm.is_contiguous() and item_norm.numel() == n_items)
-            _lib.check(self.lib.pk_rescore_topk_rows_norms_f64(self.stream(), n_rows, _ptr(rows), _ptr(n_rows_dev), n_users,
-                                                              n_items, K, _ptr(V),
-                                                              V.stride(0), _ptr(v32), 0 if v32 is None else v32.stride(0),
-                                                              _ptr(E), E.stride(0), _ptr(e_err), e_ld,
-                                                              1 if e_exact else 0,
-                                                              _ptr(seen_ptr),
-                                                              KC, splits, _ptr(cs), _ptr(ci), topk, float(vmax),
-                                                              _ptr(out_idx), _ptr(out_s), _ptr(flags), _ptr(fl), _ptr(fc), int(fo),
-                                                              _ptr(item_norm)),
-                       'pk_rescore_topk_rows_norms_f64')
+            args = (self.stream(), n_rows, _ptr(rows), _ptr(n_rows_dev), n_users, n_items, K, _ptr(V),
+                    V.stride(0), _ptr(v32), 0 if v32 is None else v32.stride(0), _ptr(E), E.stride(0), _ptr(e_err), e_ld,
+                    1 if e_exact else 0, _ptr(seen_ptr), KC, splits, _ptr(cs), _ptr(ci), topk, float(vmax),
+                    _ptr(out_idx), _ptr(out_s), _ptr(flags), _ptr(fl), _ptr(fc), int(fo), _ptr(item_norm))
+            if out_perm is None:
+                _lib.check(self.lib.pk_rescore_topk_rows_norms_f64(*args), 'pk_rescore_topk_rows_norms_f64')
+            else:
+                assert out_perm.dtype == torch.int64 and out_perm.is_contiguous() and out_perm.numel() == n_users
+                _lib.check(self.lib.pk_rescore_topk_rows_perm_f64(*args, _ptr(out_perm)), 'pk_rescore_topk_rows_perm_f64')
         return out_idx, out_s, flags
 
     def zero_counters(self, n):
@@ -1442,22 +1456,30 @@ class HipOps:
                    'pk_score_exact_rows_f64')
         return out_idx, out_s
 
-    def score_exact_list(self, lst, cnt, V, E, n_items, seen_ptr, seen_idx, topk, out_idx, out_s, n_wg=128):
-        """score_exact_rows for the device-side list (lst[:cnt]) straight into rows of out_idx / out_s: no host sync."""
+    lists_in_caller_order = True     # `rescore_topk` and `score_exact_list` take `out_perm` (scoring.recommend)
+
+    def score_exact_list(self, lst, cnt, V, E, n_items, seen_ptr, seen_idx, topk, out_idx, out_s, n_wg=128, out_perm=None):
+        """score_exact_rows for the device-side list (lst[:cnt]) straight into rows of out_idx / out_s: no host sync, one launch.
+        out_perm: as in `rescore_topk`."""
         K = E.shape[1]
-        # one work buffer per launch stream (two passes on different streams must not share it), regrown on demand
-        skey = self.stream_key()
-        need = self.lib.pk_exact_work_bytes(n_wg, n_items)
+        # one work buffer per launch stream (two passes on different streams must not share it) and layout (the tickets at
+        # its end are zeroed once, here, and sit where (n_wg, n_items) puts them)
+        key = (self.stream_key(), int(n_wg), int(n_items))
         if getattr(self, '_exact_work', None) is None:
             self._exact_work = {}
-        if skey not in self._exact_work or self._exact_work[skey].numel() < need:
-            self._exact_work[skey] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        work = self._exact_work[skey]
+        work = self._exact_work.get(key)
+        if work is None:
+            work = torch.empty(self.lib.pk_exact_work_bytes(n_wg, n_items), dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.pk_exact_work_init(self.stream(), _ptr(work), int(n_wg), n_items), 'pk_exact_work_init')
+            self._exact_work[key] = work
         with self._timed('score_exact_list', (n_items, K, topk)):
-            _lib.check(self.lib.pk_score_exact_list_f64(self.stream(), int(n_wg), _ptr(lst), _ptr(cnt), n_items, K, _ptr(V),
-                                                        V.stride(0), _ptr(E), E.stride(0), _ptr(seen_ptr), _ptr(seen_idx),
-                                                        topk, _ptr(out_idx), _ptr(out_s), _ptr(work)),
-                       'pk_score_exact_list_f64')
+            args = (self.stream(), int(n_wg), _ptr(lst), _ptr(cnt), n_items, K, _ptr(V), V.stride(0), _ptr(E), E.stride(0),
+                    _ptr(seen_ptr), _ptr(seen_idx), topk, _ptr(out_idx), _ptr(out_s), _ptr(work))
+            if out_perm is None:
+                _lib.check(self.lib.pk_score_exact_list_f64(*args), 'pk_score_exact_list_f64')
+            else:
+                assert out_perm.dtype == torch.int64 and out_perm.is_contiguous()
+                _lib.check(self.lib.pk_score_exact_list_perm_f64(*args, _ptr(out_perm)), 'pk_score_exact_list_perm_f64')
         return work
 
     def scatter_rows(self, src, perm, out=None):

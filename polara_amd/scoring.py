@@ -125,8 +125,21 @@ def renumbered_test_rows(ops, users):
     return rows
 
 
+def _one_batch(n_users, batches, head_users, stats):
+    """(B, head) of a pass: the number of user batches and the size of the head batch (B == 1 and no head: one batch)"""
+    B = int(batches) if batches else -(-n_users // (1 << 22))
+    B = max(1, min(B, n_users // 4096)) if n_users >= 4096 else 1
+    # batch starts must be multiples of 128 users (one workgroup; the dense seen masks are addressed by 32-user group)
+    head = (int(head_users or 0) // 128) * 128
+    if stats is not None:
+        B, head = 1, 0                       # sweep statistics are read from the (single) state buffer
+    if not (0 < head and 4 * head <= n_users):
+        head = 0
+    return B, head
+
+
 def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stats=None, prune=True, batches=None,
-              approx_fold_in=None, order_users=True, head_users=None, two_phase_ok=True, out=None, queries=None):
+              approx_fold_in=None, order_users=True, head_users=None, two_phase_ok=True, out=None, queries=None, _out_perm=None):
     """factors: FactorImage; T: ops-level CSR of the test users [n_users x n_items].
     Returns int64 device tensor [n_users x topk] (+ fp64 scores), rows in test-user order,
     columns by descending score — the contract of models.py:400-405.
@@ -152,7 +165,7 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
             _in_pass.held = True
             try:
                 return recommend(ops, factors, T, topk, filter_seen, return_scores, stats, prune, batches, approx_fold_in,
-                                 order_users, head_users, two_phase_ok, out, queries)
+                                 order_users, head_users, two_phase_ok, out, queries, _out_perm)
             finally:
                 _in_pass.held = False
     n_users, n_items = T.shape
@@ -174,9 +187,18 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
         Tp, perm = T.by_activity()
         if head_users is None:
             head_users = HEAD_USERS
+        # ids only, no destination of the caller's, one batch: the kernels that write the lists (the two re-scorings, the
+        # exact rows) store row perm[u] themselves and the scatter at the end — a launch, and a second pass over the lists —
+        # is gone.  (With `out=` the scatter stays: it is the kernel that writes a pinned host destination.)
+        producer_order = (not return_scores and out is None and getattr(ops, 'lists_in_caller_order', False)
+                          and _one_batch(n_users, batches, head_users, stats) == (1, 0)
+                          and (ops.candidate_capacity(topk) if factors.fused else 0) > 0)
         res = recommend(ops, factors, Tp, topk, filter_seen, return_scores, stats, prune, batches, approx_fold_in,
                         order_users=False, head_users=head_users, two_phase_ok=two_phase_ok,
-                        queries=None if queries is None else queries.index_select(0, perm))     # the rows move with T's
+                        queries=None if queries is None else queries.index_select(0, perm),     # the rows move with T's
+                        _out_perm=perm if producer_order else None)
+        if producer_order:
+            return res
         if return_scores:
             idx_p, sc_p = res
             out_idx, out_s = torch.empty_like(idx_p), torch.empty_like(sc_p)
@@ -241,7 +263,9 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
         splits = ops.score_splits(nb, KC, prune)     # of THIS batch: a small head batch is dealt out over item splits
         two_phase = ops.two_phase_plan(nb, n_items, KC) if use_two_phase else (0, 0)     # ... or swept in two phases
         if approx_fold_in:
-            if factors.Q20 is not None and PACKED_FOLD_IN and topk <= PACKED_MAX_TOPK:
+            if fold_zeroes:
+                pass                                                       # folded below, with the counters (one batch)
+            elif factors.Q20 is not None and PACKED_FOLD_IN and topk <= PACKED_MAX_TOPK:
                 ops.fold_q20(T, factors.Q20, K, out=Ex, rows=(u0, u1))     # fold-in against the packed image (K4q)
             else:
                 ops.spmm(T, factors.V32x, out=Ex, rows=(u0, u1))           # fold-in against fl32(V) (K4)
@@ -293,7 +317,7 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
         else:
             first = to_final
         ops.rescore_topk(factors.V, Eb, n_items, sp, KC, cs, ci, topk, factors.vmax, want_scores=True,
-                         splits=splits, out=outs, e_err=w, v32=factors.V32x if approx_fold_in else None, **(
+                         splits=splits, out=outs, e_err=w, v32=factors.V32x if approx_fold_in else None, **perm_kw, **(
                              {'flagged': first, 'item_norm': factors.vnorm if approx_fold_in else None} if fused_lists else {}))
         if approx_fold_in:
             # every flagged user — order not certified at the accuracy of the approximate fold-in (bit 4), or
@@ -314,7 +338,7 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
             else:
                 ops.fold_rows(T, lst, cnt, factors.V, Ex, row_offset=u0)
             ops.rescore_topk(factors.V, Eb, n_items, sp, KC, cs, ci, topk, factors.vmax, want_scores=True,
-                             splits=splits, out=outs, rows=lst, n_rows_dev=cnt, e_err=w, e_exact=True, **(
+                             splits=splits, out=outs, rows=lst, n_rows_dev=cnt, e_err=w, e_exact=True, **perm_kw, **(
                                  {'flagged': to_final} if fused_lists else {}))
             refolded.append(cnt)
 
@@ -322,17 +346,25 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
     # MI355X (S-1M): the fold-in SpMM of one batch and the MFMA sweep of another hardly overlap (B = 2:
     # -4 %, B = 4: -1 %, B = 8: +55 % per pass — each kernel fills the chip on its own), so batching is
     # only used to bound the temporaries of very large user sets (4M users per batch).
-    B = int(batches) if batches else -(-n_users // (1 << 22))
-    B = max(1, min(B, n_users // 4096)) if n_users >= 4096 else 1
-    # batch starts must be multiples of 128 users (one workgroup; the dense seen masks are addressed by 32-user group)
-    head = (int(head_users or 0) // 128) * 128
-    if stats is not None:
-        B, head = 1, 0                       # sweep statistics are read from the (single) state buffer
+    B, head = _one_batch(n_users, batches, head_users, stats)
+    one_batch = B == 1 and not head
+    perm_kw = {}
+    if _out_perm is not None:
+        assert one_batch and not return_scores and out is None, 'producer-side order: ids only, one batch'
+        perm_kw = {'out_perm': _out_perm}
+    # One batch through the packed fold-in: the counters are zeroed by the fold-in's own fix-up launch, which sits behind
+    # the product and in front of the sweep — their first user is the re-scoring behind the sweep, so stream order is enough
+    # and the reset costs no launch.  Every other fold-in route (and batches, whose streams fork below) keeps `zero_counters`.
+    fold_zeroes = bool(fused_lists and one_batch and approx_fold_in and factors.Q20 is not None and PACKED_FOLD_IN
+                       and topk <= PACKED_MAX_TOPK and hasattr(ops, 'fold_q20_zero'))
     if fused_lists:
-        counters = ops.zero_counters(2 + max(B, 2))          # on the calling stream, before any batch stream forks from it
+        if fold_zeroes:
+            counters = ops.fold_q20_zero(T, factors.Q20, K, Ex, 2 + max(B, 2), rows=(0, n_users))
+        else:
+            counters = ops.zero_counters(2 + max(B, 2))      # on the calling stream, before any batch stream forks from it
         final_cnt = counters[0:1]
         final_list = torch.empty(n_users, dtype=torch.int32, device=E.device)
-    if B == 1 and not (0 < head and 4 * head <= n_users):
+    if one_batch:
         run_batch(0, n_users)
     else:
         if B == 1:
@@ -356,7 +388,7 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
     # users still flagged (fewer than k unseen items, or not certifiable) are re-done by the exact-row kernel from a
     # device-side list: nothing of the pass visits the host, so consecutive passes queue up without a gap
     lst, cnt = (final_list, final_cnt) if fused_lists else ops.flag_compact(flags, 0x7fffffff)
-    ops.score_exact_list(lst, cnt, factors.V, E, n_items, seen_ptr, seen_idx, topk, out_idx, out_s)
+    ops.score_exact_list(lst, cnt, factors.V, E, n_items, seen_ptr, seen_idx, topk, out_idx, out_s, **perm_kw)
     if stats is not None:
         stats['flagged_users'] = int(cnt.item())
         stats['refolded_users'] = int(sum(int(c.item()) for c in refolded))
