@@ -1389,27 +1389,6 @@ __global__ void band_block_kernel(int N, int b, int ldt, const double *__restric
     T[(int64_t)r * ldt + (N - b) + c] = in_band ? C[i] : 0.0;
     if (r < N - b) T[(int64_t)(N - b + c) * ldt + r] = in_band ? C[i] : 0.0;
 }
-__global__ void lanczos_flags_kernel(int l, const double *__restrict__ G, const int32_t *__restrict__ info, double *__restrict__ flags) {
-    // flags[0] += Cholesky verdicts of the three passes; flags[1] = max(flags[1], |G - I|_max)  (one workgroup)
-    __shared__ double s_max[256];
-    double m = 0.0;
-    for (int i = threadIdx.x; i < l * l; i += blockDim.x) {
-        const int r = i / l, c = i - r * l;
-        const double d = fabs(G[i] - (r == c ? 1.0 : 0.0));
-        m = (d == d) ? fmax(m, d) : 1.0;
-    }
-    s_max[threadIdx.x] = m;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) s_max[threadIdx.x] = fmax(s_max[threadIdx.x], s_max[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        flags[0] += (double)(abs(info[0]) + abs(info[1]) + abs(info[2]));
-        flags[1] = fmax(flags[1], s_max[0]);
-    }
-}
-
 struct LanczosBuffers {
     double *Q; int64_t ldq;      // the Krylov basis [n x >= (j + 1) b], block j in columns [(j - 1) b, j b)
     double *T; int64_t ldt;      // the projected matrix [>= j b square]
@@ -1488,7 +1467,9 @@ static int lanczos_orth(pk_ctx *ctx, Solver &S, int64_t n, int b, int j, bool la
                                 B.info + p));
             CK(pk_tsmm_f64(S.st, n, b, b, Yp.p(), b, Rinv.p(), b, B.Q + N, ldq));
         }
-        hipLaunchKernelGGL(lanczos_flags_kernel, dim3(1), dim3(256), 0, S.st, b, Gp, B.info, B.flags);
+        // flags[0] += the Cholesky verdicts of the three passes; flags[1] = max(flags[1], |G - I|_max) of the last pass's Gram
+        // matrix, NaN and inf counted as 1 (the one bookkeeping kernel of the library: dense.hip)
+        CK(pk_orth_check_f64(S.st, b, Gp, ldgp, B.info, 3, B.flags));
     } else {
         DMat Wp(n, b);
         if (!Wp.ok()) return fail(ctx, PK_E_LAUNCH, "out of device memory (block Lanczos)");
