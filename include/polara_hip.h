@@ -642,6 +642,27 @@ int pk_i2i_image_f32(void *stream, int64_t n, const double *C64_dev, float *C32_
 int pk_i2i_topk(void *stream, int64_t n_users, int64_t n_items, const int64_t *t_indptr_dev, const int32_t *t_indices_dev,
                 const void *t_values_dev, int t_val_kind, const void *C_dev, int c_kind, int64_t ldc, int32_t topk,
                 int32_t filter_seen, int32_t sparse, int64_t *out_idx_dev, double *out_scores_dev, void *work_dev);
+/* ---- row-wise sparse x sparse product with the top-k fused in (csrc/simagg.hip) -----------------------------------
+ * scores[r, :] = sum_p L.values[p] * B[L.indices[p], :] for the rows of a CSR L [n_rows x n_inner] (int64 indptr, int32
+ * indices, values of kind l_val_kind, zero values kept) against a canonical CSR B [n_inner x n_cols] (strictly increasing
+ * columns per row, fp64 values).  Contract: for every (r, column) the products are added in ascending order of p starting
+ * from +0.0, each a separate fp64 multiply and add (no contraction, no atomics), and -0 is stored as +0 — the scores are
+ * bit-equal to SciPy's L.dot(B).  n_cols < 2^30. */
+/* Scratch of pk_spsp_topk (rows are scored in chunks under the candidate budget of pk_i2i_topk). */
+int64_t pk_spsp_topk_work_bytes(int64_t n_rows, int64_t n_cols, int32_t topk);
+/* The top-k of every row under the total order of pk_i2i_topk (same classes for sparse = 0 / 1, same pads).  filter_seen
+ * marks the row's own stored columns (zero-valued entries included) as seen and is accepted only when n_inner == n_cols.
+ * out_idx_dev int64 [n_rows x topk] (-1 = fewer candidates), out_scores_dev fp64 [n_rows x topk] (0 at pads) or NULL.
+ * 1 <= topk <= pk_i2i_max_topk().  work >= pk_spsp_topk_work_bytes(n_rows, n_cols, topk). */
+int pk_spsp_topk(void *stream, int64_t n_rows, int64_t n_inner, int64_t n_cols, const int64_t *l_indptr_dev,
+                 const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind, const int64_t *b_indptr_dev,
+                 const int32_t *b_indices_dev, const double *b_values_dev, int32_t topk, int32_t filter_seen, int32_t sparse,
+                 int64_t *out_idx_dev, double *out_scores_dev, void *work_dev);
+/* The same sums of rows [row0, row0 + n_rows) of L as a dense fp64 block: out_dev[(r - row0) * ld + c] for c < n_cols
+ * (ld >= n_cols; the columns beyond n_cols are not written). */
+int pk_spsp_rows_f64(void *stream, int64_t row0, int64_t n_rows, int64_t n_inner, int64_t n_cols, const int64_t *l_indptr_dev,
+                     const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind, const int64_t *b_indptr_dev,
+                     const int32_t *b_indices_dev, const double *b_values_dev, double *out_dev, int64_t ld);
 /* The global order of the catalogue for PopularityModel: order_dev[p] = the item at position p by (score descending,
  * item ascending) — one stable device radix sort.  work >= pk_popular_order_work_bytes(n_items). */
 int64_t pk_popular_order_work_bytes(int64_t n_items);

@@ -91,6 +91,7 @@ _EXPORTS = {
     'SVDModelItemColdStart': 'coldstart', 'ScaledSVDItemColdStart': 'coldstart', 'HybridSVDItemColdStart': 'coldstart',
     'ScaledHybridSVDItemColdStart': 'coldstart', 'PopularityModelItemColdStart': 'coldstart',
     'LCEModel': 'lce', 'LCEModelItemColdStart': 'lce',
+    'SimilarityAggregation': 'simagg', 'SimilarityAggregationItemColdStart': 'simagg',
     'ItemColdStartArrayData': 'data', 'ItemColdStartSimilarityArrayData': 'data',
     'ArrayData': 'data', 'ShardedArrayData': 'data',
     'SparseProduct': 'operator', 'find_optimal_svd_rank': 'pipelines', 'find_optimal_tucker_ranks': 'pipelines',

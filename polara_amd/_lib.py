@@ -138,6 +138,9 @@ PROTOTYPES = {
     'pk_i2i_build_f64': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _i64]),
     'pk_i2i_image_f32': (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     'pk_i2i_topk': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'pk_spsp_topk_work_bytes': (_i64, [_i64, _i64, _i32]),
+    'pk_spsp_topk': (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'pk_spsp_rows_f64': (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _i64]),
     'pk_popular_order_work_bytes': (_i64, [_i64]),
     'pk_popular_order': (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     'pk_popular_topk': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _vp]),

@@ -23,15 +23,9 @@
 // The key of a column, best first: class descending (2 = candidate, 1 = seen item of the dense branch under
 // filter_seen, 0 = not a candidate: pad), then score descending, then item ascending — one total order, so the lists
 // are a function of the scores alone.
-#include "pk_common.h"
+#include "i2i_keys.h"
 
 #define PK_I2I_BUILD_WIN 8192        // fp64 columns of C per build workgroup (64 KiB of LDS)
-#define PK_I2I_COLS 8                // columns of a scoring lane
-#define PK_I2I_THREADS 256
-#define PK_I2I_WIN (PK_I2I_COLS * PK_I2I_THREADS)   // 2048 columns per scoring workgroup
-#define PK_I2I_MAX_TOPK 1024
-#define PK_I2I_CAND_BUDGET (512ll << 20)           // bytes of window candidates per launch (users are chunked under it)
-#define PK_I2I_ITEM_MASK 0x3fffffffu
 #define PK_POP_MAX_ITEMS (1 << 19)   // the popularity kernel's seen bitmap: 64 KiB of LDS
 
 // ---- planning (host functions, no device needed) -------------------------------------------------------------
@@ -40,12 +34,6 @@ extern "C" int32_t pk_i2i_window(void) { return PK_I2I_WIN; }
 extern "C" int32_t pk_i2i_build_window(void) { return PK_I2I_BUILD_WIN; }
 
 extern "C" int64_t pk_i2i_ld(int64_t n_items) { return pk_ceil_div(n_items, PK_I2I_COLS) * PK_I2I_COLS; }
-
-static int32_t i2i_pow2(int32_t topk) {
-    int32_t p = 1;
-    while (p < topk) p <<= 1;
-    return p;
-}
 
 extern "C" int64_t pk_i2i_chunk_users(int64_t n_users, int64_t n_items, int32_t topk) {
     if (n_users <= 0 || n_items <= 0 || topk < 1 || topk > PK_I2I_MAX_TOPK) return 0;
@@ -60,67 +48,7 @@ extern "C" int64_t pk_i2i_topk_work_bytes(int64_t n_users, int64_t n_items, int3
     return n * 8 + n * 4 + 256;
 }
 
-// ---- keys ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t i2i_key(double s) {
-    const uint64_t b = (uint64_t)__double_as_longlong(s);
-    return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-__device__ __forceinline__ double i2i_unkey(uint64_t k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
-}
-// a strictly better than b under (class desc, score desc, item asc); m = class << 30 | item
-__device__ __forceinline__ bool i2i_better(uint64_t sa, uint32_t ma, uint64_t sb, uint32_t mb) {
-    const uint32_t ca = ma >> 30, cb = mb >> 30;
-    if (ca != cb) return ca > cb;
-    if (sa != sb) return sa > sb;
-    return (ma & PK_I2I_ITEM_MASK) < (mb & PK_I2I_ITEM_MASK);
-}
-__device__ __forceinline__ void i2i_cmpx(uint64_t *s, uint32_t *m, int i, int l) {
-    if (i2i_better(s[l], m[l], s[i], m[i])) {
-        const uint64_t ts = s[i];
-        const uint32_t tm = m[i];
-        s[i] = s[l];
-        m[i] = m[l];
-        s[l] = ts;
-        m[l] = tm;
-    }
-}
-// pair t of a compare distance j: (i, i + j) with bit j of i clear
-__device__ __forceinline__ int i2i_pair(int t, int j) { return 2 * t - (t & (j - 1)); }
-
-// best-first bitonic sort of n (power of two) keys in LDS by the block's NT threads
-template <int NT>
-__device__ void i2i_sort(uint64_t *s, uint32_t *m, int n) {
-    for (int k = 2; k <= n; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < n / 2; t += NT) {
-                const int i = i2i_pair(t, j);
-                if ((i & k) == 0)
-                    i2i_cmpx(s, m, i, i + j);
-                else
-                    i2i_cmpx(s, m, i + j, i);
-            }
-            __syncthreads();
-        }
-}
-
 // ---- build -------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double i2i_val(const void *v, int kind, int64_t p) {
-    return kind == PK_VAL_F32 ? (double)static_cast<const float *>(v)[p] : static_cast<const double *>(v)[p];
-}
-
-// first position in [lo, hi) whose column is >= c
-__device__ __forceinline__ int64_t i2i_lower_bound(const int32_t *__restrict__ idx, int64_t lo, int64_t hi, int64_t c) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (idx[mid] < c)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void i2i_build_kernel(int64_t n_items, const int64_t *__restrict__ indptr,
                                                         const int32_t *__restrict__ indices, const void *__restrict__ values,
                                                         int val_kind, const int64_t *__restrict__ t_indptr,
@@ -307,6 +235,12 @@ __global__ __launch_bounds__(64) void i2i_merge_kernel(int64_t u0, int n_win, in
     }
 }
 
+void i2i_launch_merge(hipStream_t s, int64_t nu, int64_t u0, int n_win, int P, int topk, const uint64_t *cand_s,
+                      const uint32_t *cand_m, int64_t *out_idx, double *out_scores) {
+    hipLaunchKernelGGL(i2i_merge_kernel, dim3((unsigned)nu), dim3(64), 0, s, u0, n_win, P, topk, cand_s, cand_m, out_idx,
+                       out_scores);
+}
+
 extern "C" int pk_i2i_topk(void *stream, int64_t n_users, int64_t n_items, const int64_t *t_indptr_dev,
                            const int32_t *t_indices_dev, const void *t_values_dev, int t_val_kind, const void *C_dev,
                            int c_kind, int64_t ldc, int32_t topk, int32_t filter_seen, int32_t sparse, int64_t *out_idx_dev,
@@ -336,8 +270,7 @@ extern "C" int pk_i2i_topk(void *stream, int64_t n_users, int64_t n_items, const
                                n_items, t_indptr_dev, t_indices_dev, t_values_dev, t_val_kind,
                                static_cast<const double *>(C_dev), ldc, P, filter_seen, sparse, cand_s, cand_m);
         PK_CHECK_LAUNCH("i2i_window_kernel");
-        hipLaunchKernelGGL(i2i_merge_kernel, dim3((unsigned)nu), dim3(64), 0, s, u0, (int)n_win, P, (int)topk, cand_s, cand_m,
-                           out_idx_dev, out_scores_dev);
+        i2i_launch_merge(s, nu, u0, (int)n_win, P, (int)topk, cand_s, cand_m, out_idx_dev, out_scores_dev);
         PK_CHECK_LAUNCH("i2i_merge_kernel");
     }
     return PK_OK;

@@ -441,9 +441,38 @@ class ItemColdStartArrayData(ArrayData):
 
 class ItemColdStartSimilarityArrayData(ItemColdStartArrayData, SimilarityArrayData):
     """ItemColdStartArrayData plus the relations of SimilarityArrayData (the counterpart of `ItemColdStartSimilarityData`,
-    coldstart/data.py:256-259) — what the hybrid cold-start models are built on."""
+    coldstart/data.py:256-259) — what the hybrid cold-start models are built on.
+
+    cold_relations_matrices (optional): {item field name: M}, M the similarity of the cold items, as numbered in the
+    holdout, to the training items [cold items x n_items], a SciPy sparse matrix or an ndarray — what SIM(cs) aggregates
+    over (`cold_items_similarity`, coldstart/data.py:228-253)."""
 
     def __init__(self, training, holdout, item_features, cold_item_features, *, relations_matrices, relations_indices,
-                 **kwargs):
+                 cold_relations_matrices=None, **kwargs):
+        self._cold_rel_mat = dict(cold_relations_matrices or {})
+        self._cold_similarity = None
         ItemColdStartArrayData.__init__(self, training, holdout, item_features, cold_item_features, **kwargs)
         self._init_relations(relations_matrices, relations_indices)
+
+    def _set_cold_items(self, holdout, cold_item_features):
+        super()._set_cold_items(holdout, cold_item_features)
+        self._cold_similarity = None                # the cold items that survive the validity filter may have changed
+
+    @property
+    def cold_items_similarity(self):
+        """fp64 SciPy CSR [n_cold_items x n_items]: the rows `cold_items_kept` of the given matrix, in the cold items' new
+        numbering, no diagonal treatment (the reference's `sim_mat[:, seen_idx][cold_idx, :]`); None when no cold relations
+        were given.  The entries of a row keep the order in which the given matrix stores them — the reference's matrix comes
+        out of its indexing unsorted, SIM(cs) adds a row's products in the stored order, and another order changes the last
+        bits of a score."""
+        mat = self._cold_rel_mat.get(self.fields.itemid, None)
+        if mat is None:
+            return None
+        if self._cold_similarity is None:
+            from scipy.sparse import csr_matrix
+            m = csr_matrix(mat, dtype=np.float64)
+            if m.shape[1] != self.n_items or (len(self.cold_items_kept) and self.cold_items_kept[-1] >= m.shape[0]):
+                raise ValueError('cold item relations of shape %s: %d training items and cold items up to number %d expected'
+                                 % (m.shape, self.n_items, int(self.cold_items_kept[-1]) if len(self.cold_items_kept) else -1))
+            self._cold_similarity = m[self.cold_items_kept]
+        return self._cold_similarity

@@ -1057,7 +1057,43 @@ class _DenseItemModel(RecommenderModel):
         return recs
 
 
-class CooccurrenceModel(_DenseItemModel):
+class _SparseScoresMixin:
+    """`downvote_seen_items` and `get_topk_elements` that also take the SciPy score matrices of a sparse branch
+    (CooccurrenceModel, SimilarityAggregation: what their `slice_recommendations` returns without `dense_output`)."""
+
+    def downvote_seen_items(self, recs, idx_seen):
+        """models.py:494-519.  A SciPy matrix (sparse branch): the seen entries become 0 and leave the matrix, IN PLACE
+        (the reference's `recs -= ...` rebinds its local name and leaves the caller's matrix as it was); dense: the base
+        class's dense branch."""
+        if not hasattr(recs, 'tocsr'):
+            return super().downvote_seen_items(recs, idx_seen)
+        from scipy.sparse import coo_matrix
+        users, items = (np.asarray(x, dtype=np.int64) for x in idx_seen[:2])
+        seen = coo_matrix((np.ones(len(users), dtype=bool), (users, items)), shape=recs.shape)
+        new = (recs - recs.multiply(seen)).tocsr()
+        new.eliminate_zeros()
+        recs.data, recs.indices, recs.indptr = new.data, new.indices, new.indptr
+
+    def get_topk_elements(self, scores, topk=None):
+        """models.py:522-563.  A SciPy CSR (sparse branch): per row its stored entries by score descending, item
+        ascending, padded with -1; dense: the base class."""
+        if not hasattr(scores, 'tocsr'):
+            return super().get_topk_elements(scores, topk)
+        topk = self.topk if topk is None else int(topk)
+        s = scores.tocsr()
+        s.sum_duplicates()
+        out = np.full((s.shape[0], topk), self._pad_const, dtype=np.int64)
+        for r in range(s.shape[0]):
+            lo, hi = s.indptr[r], s.indptr[r + 1]
+            data, cols = s.data[lo:hi], s.indices[lo:hi]
+            keep = data != 0
+            data, cols = data[keep], cols[keep]
+            best = np.lexsort((cols, -data))[:topk]
+            out[r, :len(best)] = cols[best]
+        return out
+
+
+class CooccurrenceModel(_SparseScoresMixin, _DenseItemModel):
     """Item-to-item (models.py:699-725): C = A^T A with the diagonal set to 0, scores s_u = sum_i t_ui C[i, :].
 
     C is built on the device and kept there as a dense image, fp32 when every entry survives the rounding (integer
@@ -1144,37 +1180,6 @@ class CooccurrenceModel(_DenseItemModel):
             scores = csr_matrix(scores)
             scores.eliminate_zeros()
         return scores, (users, items, fdbk)
-
-    def downvote_seen_items(self, recs, idx_seen):
-        """models.py:494-519.  A SciPy matrix (sparse branch): the seen entries become 0 and leave the matrix, IN PLACE
-        (the reference's `recs -= ...` rebinds its local name and leaves the caller's matrix as it was); dense: the base
-        class's dense branch."""
-        if not hasattr(recs, 'tocsr'):
-            return super().downvote_seen_items(recs, idx_seen)
-        from scipy.sparse import coo_matrix
-        users, items = (np.asarray(x, dtype=np.int64) for x in idx_seen[:2])
-        seen = coo_matrix((np.ones(len(users), dtype=bool), (users, items)), shape=recs.shape)
-        new = (recs - recs.multiply(seen)).tocsr()
-        new.eliminate_zeros()
-        recs.data, recs.indices, recs.indptr = new.data, new.indices, new.indptr
-
-    def get_topk_elements(self, scores, topk=None):
-        """models.py:522-563.  A SciPy CSR (sparse branch): per row its stored entries by score descending, item
-        ascending, padded with -1; dense: the base class."""
-        if not hasattr(scores, 'tocsr'):
-            return super().get_topk_elements(scores, topk)
-        topk = self.topk if topk is None else int(topk)
-        s = scores.tocsr()
-        s.sum_duplicates()
-        out = np.full((s.shape[0], topk), self._pad_const, dtype=np.int64)
-        for r in range(s.shape[0]):
-            lo, hi = s.indptr[r], s.indptr[r + 1]
-            data, cols = s.data[lo:hi], s.indices[lo:hi]
-            keep = data != 0
-            data, cols = data[keep], cols[keep]
-            best = np.lexsort((cols, -data))[:topk]
-            out[r, :len(best)] = cols[best]
-        return out
 
 
 class PopularityModel(_DenseItemModel):

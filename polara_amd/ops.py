@@ -1606,6 +1606,47 @@ class HipOps:
                                             _ptr(work)), 'pk_i2i_topk')
         return out, scores
 
+    # ---- sparse x sparse product with the top-k fused in (csrc/simagg.hip) -----------------------------------------
+    @staticmethod
+    def _spsp_values(B):
+        """B's values as fp64 (DeviceCSR keeps exactly representable values as fp32; the widening is exact), cached."""
+        if B.values.dtype == torch.float64:
+            return B.values
+        if getattr(B, '_values_f64', None) is None or B._values_f64[0] is not B.values:
+            B._values_f64 = (B.values, B.values.double())
+        return B._values_f64[1]
+
+    def spsp_topk(self, L, B, topk, filter_seen, sparse, want_scores=False):
+        """int64 [n_rows x topk] (and fp64 scores or None): the top-k of scores[r] = L[r] B per row of the device CSR L
+        against the canonical device CSR B (pk_spsp_topk: sums in SciPy's order, the masking and pads of i2i_topk)."""
+        from . import simagg
+        n_rows, n_inner, n_cols = simagg.check_shapes(L.shape, B.shape)
+        topk = int(topk)
+        out = torch.empty(n_rows, topk, dtype=torch.int64, device=self.device)
+        scores = torch.empty(n_rows, topk, dtype=torch.float64, device=self.device) if want_scores else None
+        work = self._work(self.lib.pk_spsp_topk_work_bytes(n_rows, n_cols, topk))
+        with self._timed('spsp_topk', (n_rows, n_cols, L.nnz, topk)):
+            _lib.check(self.lib.pk_spsp_topk(self.stream(), n_rows, n_inner, n_cols, _ptr(L.indptr), _ptr(L.indices),
+                                             _ptr(L.values), L.val_kind, _ptr(B.indptr), _ptr(B.indices),
+                                             _ptr(self._spsp_values(B)), topk, 1 if filter_seen else 0, 1 if sparse else 0,
+                                             _ptr(out), _ptr(scores), _ptr(work)), 'pk_spsp_topk')
+        return out, scores
+
+    def spsp_rows(self, L, B, rows=None):
+        """fp64 [n x n_cols] device block: the rows [lo, hi) = `rows` (default: all) of L B, bit-equal to SciPy's product
+        (pk_spsp_rows_f64)."""
+        from . import simagg
+        n_rows, n_inner, n_cols = simagg.check_shapes(L.shape, B.shape)
+        lo, hi = (0, n_rows) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= lo <= hi <= n_rows:
+            raise ValueError('spsp_rows: rows [%d, %d) outside the %d rows of L' % (lo, hi, n_rows))
+        out = torch.empty(hi - lo, n_cols, dtype=torch.float64, device=self.device)
+        with self._timed('spsp_rows', (hi - lo, n_cols, L.nnz)):
+            _lib.check(self.lib.pk_spsp_rows_f64(self.stream(), lo, hi - lo, n_inner, n_cols, _ptr(L.indptr), _ptr(L.indices),
+                                                 _ptr(L.values), L.val_kind, _ptr(B.indptr), _ptr(B.indices),
+                                                 _ptr(self._spsp_values(B)), _ptr(out), n_cols), 'pk_spsp_rows_f64')
+        return out
+
     def popular_order(self, scores):
         """int32 [n_items] device: the items by (score descending, item ascending) (pk_popular_order)."""
         scores = scores.to(self.device, torch.float64).contiguous()
