@@ -663,6 +663,39 @@ int pk_spsp_topk(void *stream, int64_t n_rows, int64_t n_inner, int64_t n_cols, 
 int pk_spsp_rows_f64(void *stream, int64_t row0, int64_t n_rows, int64_t n_inner, int64_t n_cols, const int64_t *l_indptr_dev,
                      const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind, const int64_t *b_indptr_dev,
                      const int32_t *b_indices_dev, const double *b_values_dev, double *out_dev, int64_t ld);
+/* ---- sampled-negatives evaluation (csrc/sampled.hip; models.py:1095-1183, lib/sparse.py::inner_product_at,
+ * lib/sampler.py::mf_random_item_scoring) ------------------------------------------------------------------------------
+ * Limits (host functions): the candidates per user the fused launch keeps in LDS, the largest rank, the largest sample. */
+int32_t pk_candidates_fused_max(void);
+int32_t pk_candidates_max_rank(void);
+int32_t pk_sample_max_n(void);
+/* Rounds of 64 draws within which every user of pk_sample_unseen is done except with probability below exp(-32), when each
+ * has at least min_eligible >= n items to draw from (-1: bad arguments), and the largest limit a launch is accepted with. */
+int64_t pk_sample_round_limit(int64_t n_items, int32_t n, int64_t min_eligible);
+int32_t pk_sample_max_rounds(void);
+/* s[u, c] = sum_f P[u, f] * V[cand[u, c], f] for the C candidates of every user and the top-k of every row.
+ * P fp64 [n_users x r], leading dimension ldp; V fp64 [n_items x r]: element (i, f) at V_dev[i * ldv + f * v_col_stride]
+ * (row-major: v_col_stride = 1, ldv >= r; column-major: ldv = 1, v_col_stride >= n_items); cand int32 [n_users x C] item
+ * ids, NOT range-checked on the device.  Contract: the sum starts from +0.0 and runs over f ascending, each term a
+ * separately rounded fp64 multiply and add (no contraction) — bit-equal to the reference's loops for the same P and V.
+ * out_idx_dev int64 [n_users x topk]: COLUMN POSITIONS 0..C-1, best first under (score descending, position ascending),
+ * the order of pk_topk_rows_f64.  out_scores_dev fp64 [n_users x C] or NULL; required when C > pk_candidates_fused_max()
+ * (the selection then runs in pk_topk_rows_f64).  1 <= r <= pk_candidates_max_rank(), 1 <= topk <= C < 2^30. */
+int pk_candidates_topk_f64(void *stream, int64_t n_users, int64_t n_items, int32_t r, const double *P_dev, int64_t ldp,
+                           const double *V_dev, int64_t ldv, int64_t v_col_stride, const int32_t *cand_dev, int64_t C,
+                           int32_t topk, int64_t *out_idx_dev, double *out_scores_dev);
+/* n distinct items per user, uniform over the items that are neither in the user's row of the CSR t_* (sorted columns) nor
+ * in its row of the CSR h_* (a few entries per row, any order; h_indptr_dev = NULL: no second exclusion), in draw order:
+ *   draw t = 0, 1, ...: z = splitmix64 finaliser of (seed_u * 2^32 + t), w = z >> 32, m = w * n_items; the draw is skipped
+ *   when (m mod 2^32) < (2^32 mod n_items), else x = m >> 32; x is accepted when it is not excluded and was not accepted
+ *   before; the output is the first n accepted x.
+ * out_dev int32 [n_users x n]; seeds_dev uint32 [n_users].  min_eligible: a lower bound of n_items - excluded_u over the users,
+ * which the caller guarantees to be >= n; it sets the round limit, pk_sample_round_limit(n_items, n, min_eligible) — at most
+ * proportional to n_items (1 + ln n) — and a limit above pk_sample_max_rounds() is refused (PK_E_INVALID, no launch).  The
+ * caller zeroes *err_dev: a user not done within the limit sets it to 1 and its row is incomplete.  1 <= n <= pk_sample_max_n(). */
+int pk_sample_unseen(void *stream, int64_t n_users, int64_t n_items, const int64_t *t_indptr_dev, const int32_t *t_indices_dev,
+                     const int64_t *h_indptr_dev, const int32_t *h_indices_dev, int32_t n, int64_t min_eligible,
+                     const uint32_t *seeds_dev, int32_t *out_dev, int32_t *err_dev);
 /* The global order of the catalogue for PopularityModel: order_dev[p] = the item at position p by (score descending,
  * item ascending) — one stable device radix sort.  work >= pk_popular_order_work_bytes(n_items). */
 int64_t pk_popular_order_work_bytes(int64_t n_items);

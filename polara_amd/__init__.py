@@ -5,6 +5,7 @@
     from polara_amd import HybridSVD, ScaledHybridSVD             # PureSVD with item side information (dense Cholesky)
     from polara_amd import SVDModelItemColdStart, HybridSVDItemColdStart   # item cold start (also the -s forms and MP(cs))
     from polara_amd import LCEModel, LCEModelItemColdStart          # Local Collective Embeddings, standard and item cold start
+    from polara_amd import SVDModelSampled, RandomSampleArrayData   # sampled-negatives evaluation (1 holdout + n unseen items)
     from polara_amd import ArrayData, ShardedArrayData              # NumPy / on-disk data providers
 
 Resolved on first use, so that importing the package (or its build / binding modules) does not pull in torch."""
@@ -94,6 +95,8 @@ _EXPORTS = {
     'SimilarityAggregation': 'simagg', 'SimilarityAggregationItemColdStart': 'simagg',
     'ItemColdStartArrayData': 'data', 'ItemColdStartSimilarityArrayData': 'data',
     'ArrayData': 'data', 'ShardedArrayData': 'data',
+    'RandomSampleEvaluationMixin': 'data', 'RandomSampleArrayData': 'data',
+    'RandomSampleEvaluationSVDMixin': 'sampled', 'SVDModelSampled': 'sampled', 'ScaledSVDSampled': 'sampled',
     'SparseProduct': 'operator', 'find_optimal_svd_rank': 'pipelines', 'find_optimal_tucker_ranks': 'pipelines',
     'find_optimal_config': 'pipelines',
 }

@@ -476,3 +476,72 @@ class ItemColdStartSimilarityArrayData(ItemColdStartArrayData, SimilarityArrayDa
                                  % (m.shape, self.n_items, int(self.cold_items_kept[-1]) if len(self.cold_items_kept) else -1))
             self._cold_similarity = m[self.cold_items_kept]
         return self._cold_similarity
+
+
+class RandomSampleEvaluationMixin:
+    """The data side of the sampled-negatives protocol (the reference's `RandomSampleEvaluationMixin`, data.py:938-994) on
+    arrays: every holdout item of a test user is ranked against a fixed number of items the user has not seen, given
+    explicitly (`set_unseen_interactions`) or drawn by the model (`unseen_items_num` and `seed`).
+
+    unseen_interactions: int64 [n_test_users x n] of internal item ids, row r for the r-th test user in sorted order, or
+    None.  unseen_items_num: n, or None.  `adapt_holdout()` gives the column of every holdout entry in the model's score
+    rows `[holdout items | unseen items]` — the reference's `cumcount`, kept in `holdout_positions`.
+
+    One difference from the reference: new test data (`set_test_data`) clears `unseen_interactions` — the stored rows
+    belong to the former test users; the reference keeps them and fails or mis-scores at the next lookup."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.unseen_interactions = None
+        self.unseen_items_num = None
+        self._holdout_item_prefix = 'x'
+        self.holdout_positions = None
+        if not hasattr(self, 'seed'):
+            self.seed = None
+
+    def set_test_data(self, *args, **kwargs):
+        super().set_test_data(*args, **kwargs)
+        self.unseen_interactions = None
+        self.holdout_positions = None
+
+    def adapt_holdout(self):
+        """int64 [n_holdout]: the position of every holdout entry among its user's entries (0, 1, ...) in the order of the
+        stored holdout, which is sorted by user."""
+        hold = self.test.holdout
+        if hold is None:
+            raise ValueError('adapt_holdout() needs a holdout')
+        u = np.asarray(hold.userid)
+        first = np.flatnonzero(np.r_[True, u[1:] != u[:-1]]) if len(u) else np.zeros(0, dtype=np.int64)
+        start = np.repeat(first, np.diff(np.r_[first, len(u)]))
+        self.holdout_positions = (np.arange(len(u)) - start).astype(np.int64)
+        return self.holdout_positions
+
+    def set_unseen_interactions(self, interactions, reindex=False):
+        """`interactions`: [n_test_users x n] internal item ids (any integer type; a list of equally long lists will do)."""
+        if reindex:
+            raise NotImplementedError('arrays carry internal ids only: reindex=True has nothing to map')
+        try:
+            arr = np.asarray(interactions)
+        except ValueError:                                     # NumPy >= 1.24 refuses a ragged list
+            arr = np.empty(0, dtype=object)
+        n_test_users = int(self.get_test_shape(tensor_mode=False)[0])
+        if arr.dtype == object or arr.ndim != 2:
+            raise ValueError('Number of unseen items is inconsistent')
+        if arr.shape[0] != n_test_users or arr.shape[1] < 1:
+            raise ValueError('unseen interactions of shape %s for %d test users' % (arr.shape, n_test_users))
+        if not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError('unseen interactions must hold integer item ids, got %s' % arr.dtype)
+        if arr.min() < 0 or arr.max() >= self.n_items:
+            raise ValueError('unseen interactions name item %d of %d' % (int(arr.max() if arr.min() >= 0 else arr.min()), self.n_items))
+        self.unseen_interactions = np.ascontiguousarray(arr, dtype=np.int64)
+        self.unseen_items_num = int(arr.shape[1])
+        self.adapt_holdout()
+
+
+class RandomSampleArrayData(RandomSampleEvaluationMixin, ArrayData):
+    """ArrayData for the sampled-negatives protocol; `seed` feeds the per-user seeds of the model's sampler
+    (`np.random.SeedSequence(seed).generate_state(n_test_users)`, models.py:1151)."""
+
+    def __init__(self, *args, seed=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.seed = seed

@@ -1647,6 +1647,77 @@ class HipOps:
                                                  _ptr(self._spsp_values(B)), _ptr(out), n_cols), 'pk_spsp_rows_f64')
         return out
 
+    # ---- sampled-negatives evaluation (csrc/sampled.hip) ---------------------------------------------------------
+    def candidates_topk(self, P, V, cand, topk, want_scores=False):
+        """int64 [n_users x topk] column POSITIONS of the best candidates of every user (and the fp64 scores
+        [n_users x C] or None): s[u, c] = P[u] . V[cand[u, c]] summed in the reference's order without contraction, the
+        selection of topk_rows (pk_candidates_topk_f64).  P: fp64 device [n_users x r] with unit column stride; V: fp64
+        device [n_items x r], row- or column-major; cand: int32 device [n_users x C] of item ids, validated here."""
+        from . import sampled
+        n_users, r, n_items, C = sampled.check_candidate_shapes(P.shape, V.shape, cand.shape, topk)
+        assert P.dtype == V.dtype == torch.float64 and P.stride(1) == 1
+        if V.stride(1) != 1 and V.stride(0) != 1:
+            V = V.contiguous()
+        cand = cand.to(self.device, torch.int32).contiguous()
+        if n_users and C:
+            lo, hi = (int(x) for x in torch.aminmax(cand))
+            if lo < 0 or hi >= n_items:
+                raise ValueError('candidate item ids span [%d, %d]: outside the %d items of the factors' % (lo, hi, n_items))
+        topk = int(topk)
+        out = torch.empty(n_users, topk, dtype=torch.int64, device=self.device)
+        keep = want_scores or C > self.lib.pk_candidates_fused_max()
+        scores = torch.empty(n_users, C, dtype=torch.float64, device=self.device) if keep else None
+        with self._timed('candidates_topk', (n_users, n_items, r, C, topk)):
+            _lib.check(self.lib.pk_candidates_topk_f64(self.stream(), n_users, n_items, r, _ptr(P), max(P.stride(0), r), _ptr(V), V.stride(0), V.stride(1), _ptr(cand), C, topk, _ptr(out),
+                                                       _ptr(scores)), 'pk_candidates_topk_f64')
+        return out, (scores if want_scores else None)
+
+    def sample_unseen(self, T, H, n, seeds):
+        """int32 device [n_users x n]: n distinct items per user drawn uniformly from the items outside the user's row of
+        the device CSR T (sorted columns) and of the device CSR H (None: no second exclusion), in draw order, from one
+        uint32 seed per user (pk_sample_unseen; the stream is restated in tests/sampled_reference.py).  Raises ValueError
+        before any launch when a user has fewer than n eligible items."""
+        from . import sampled
+        n_users, n_items = (int(x) for x in T.shape)
+        n = int(n)
+        if H is not None and tuple(int(x) for x in H.shape) != (n_users, n_items):
+            raise ValueError('sample_unseen: exclusions of shape %s and %s' % (tuple(T.shape), tuple(H.shape)))
+        if not getattr(T, 'sorted_cols', True):
+            raise ValueError('sample_unseen: the rows of the first exclusion matrix must have sorted columns')
+        seeds = np.ascontiguousarray(seeds)
+        sampled.check_sample_request(n, n_items, len(seeds), n_users, self.lib.pk_sample_max_n())
+        excluded = T.indptr[1:] - T.indptr[:-1]
+        if H is not None:
+            excluded = excluded + (H.indptr[1:] - H.indptr[:-1])
+        min_eligible = n_items - (int(excluded.max()) if n_users else 0)        # a lower bound: an item of both rows counts twice
+        limit = self.lib.pk_sample_round_limit(n_items, n, max(min_eligible, n))
+        if n_users and (min_eligible < n or limit > self.lib.pk_sample_max_rounds()):
+            # count the union exactly before giving up
+            host = (self.to_host(T.indptr), self.to_host(T.indices), None if H is None else self.to_host(H.indptr),
+                    None if H is None else self.to_host(H.indices))
+            short = sampled.users_short_of_items(*host, n_items, n)
+            if len(short):
+                raise ValueError('sample_unseen: %d users have fewer than %d items outside their rows (the first: user %d)'
+                                 % (len(short), n, int(short[0])))
+            min_eligible = sampled.fewest_eligible_items(*host, n_items)
+            limit = self.lib.pk_sample_round_limit(n_items, n, min_eligible)
+            if limit > self.lib.pk_sample_max_rounds():
+                raise ValueError('sample_unseen: a user has only %d items to draw %d from (of %d): up to %d rounds of 64 draws, '
+                                 'more than the %d a launch may take' % (min_eligible, n, n_items, limit,
+                                                                          self.lib.pk_sample_max_rounds()))
+        out = torch.empty(n_users, n, dtype=torch.int32, device=self.device)
+        err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        seeds_dev = torch.from_numpy(seeds.astype(np.uint32).view(np.int32)).to(self.device)
+        with self._timed('sample_unseen', (n_users, n_items, T.nnz, n)):
+            _lib.check(self.lib.pk_sample_unseen(self.stream(), n_users, n_items, _ptr(T.indptr), _ptr(T.indices),
+                                                 _ptr(H.indptr) if H is not None else None,
+                                                 _ptr(H.indices) if H is not None else None, n, min_eligible, _ptr(seeds_dev),
+                                                 _ptr(out),
+                                                 _ptr(err)), 'pk_sample_unseen')
+        if int(err.item()):
+            raise _lib.PolaraHipError('pk_sample_unseen: a user was not done within the round limit')
+        return out
+
     def popular_order(self, scores):
         """int32 [n_items] device: the items by (score descending, item ascending) (pk_popular_order)."""
         scores = scores.to(self.device, torch.float64).contiguous()
