@@ -763,6 +763,44 @@ int pk_lce_dots_f64(void *stream, int32_t n_pairs, const double *const *P_dev, c
 int pk_clamp_min_f64(void *stream, int64_t m, int32_t k, double *E_dev, int64_t lde, double lo);
 
 /* ------------------------------------------------------------------------------------------
+ * Probabilistic matrix factorisation (csrc/pmf.hip).  Replaces the numba loop `generalized_sgd_sweep`
+ * (lib/optimize.py:123-154) as `simple_pmf_sgd` drives it: one SGD sweep over all interactions per epoch.
+ * The interactions come in SCHEDULE order (polara_amd/pmf.py: block_schedule): the matrix is cut into B x B blocks, block
+ * (i, j) belongs to stratum s = (j - i) mod B, the schedule lists stratum 0's blocks i = 0..B-1, then stratum 1's, ...;
+ * block_ptr_dev[s * B + i] .. [s * B + i + 1] are the samples of block i of stratum s.  Two blocks of a stratum share
+ * no user and no item, so pk_pmf_epoch_f64 runs them side by side and the result equals the serial sweep over the
+ * schedule.  ONE launch per stratum on `stream`; stream order is the only synchronisation between strata (no grid
+ * barrier, no cooperative launch, no flag another workgroup waits on).
+ *   A block is swept sequentially by one group of w lanes, w = the smallest of 16, 32, 64 that is >= rank; lane c holds
+ *   column c, lanes c >= rank hold zeros.  Per sample (m, n, val), exactly optimize.py:129-153 in IEEE fp64 without
+ *   contraction, divisions and square roots correctly rounded:
+ *     d[c]  = pm[c] * qn[c]                              (0 for c >= rank)
+ *     dot   = halving tree: for h = w/2, w/4, .., 1:  d[c] <- d[c] + d[c + h]  (c < h);  dot = d[0]
+ *     err   = val - dot;  rl = lambd / row_nnz[m];  cl = lambd / col_nnz[n]
+ *     gp    = err * qn - pm * rl;   gq = err * pm - qn * cl            (both from the OLD pm, qn)
+ *     adjust (P first, then Q):  none: a = g
+ *                                adagrad: S <- S + g * g;                          a = g / sqrt(smoothing + S)
+ *                                rmsprop: S <- gamma * S + (1 - gamma) * (g * g);  a = g / sqrt(smoothing + S)
+ *     pm <- pm + eta * ap;  qn <- qn + eta * aq;  both rows (and both state rows) are stored
+ *   A row (and its state row) stays in registers while consecutive samples of the block share it.
+ *   Squared error: every block adds err * err in sample order; one more launch adds the block sums of each stratum in
+ *   block order and then the stratum sums in stratum order into sse_dev[0].  No atomics: equal inputs give equal bits.
+ * row_nnz_dev / col_nnz_dev: the entry counts per user / item as doubles.  S*_dev: the adjuster's state [n x rank]
+ * (NULL for PK_PMF_ADJUST_NONE); the caller zeroes it before every epoch (optimize.py:186-189).
+ * work_dev: pk_pmf_work_doubles(blocks) doubles.  The kernel trusts the plan (indices in range, block_ptr ascending). */
+#define PK_PMF_ADJUST_NONE 0
+#define PK_PMF_ADJUST_ADAGRAD 1
+#define PK_PMF_ADJUST_RMSPROP 2
+#define PK_PMF_MAX_BLOCKS 4096
+int32_t pk_pmf_max_rank(void);
+int64_t pk_pmf_work_doubles(int32_t blocks);
+int pk_pmf_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, const int64_t *block_ptr_dev,
+                     const int32_t *users_dev, const int32_t *items_dev, const double *vals_dev, double *P_dev, int64_t ldp,
+                     double *Q_dev, int64_t ldq, const double *row_nnz_dev, const double *col_nnz_dev, double eta,
+                     double lambd, int32_t adjust, double *SP_dev, int64_t ldsp, double *SQ_dev, int64_t ldsq, double gamma,
+                     double smoothing, double *work_dev, double *sse_dev);
+
+/* ------------------------------------------------------------------------------------------
  * K5.  Sparse tensor-times-matrix (CoFFee / HOOI).
  * Replaces numba `dttm_seq` / `dttm_par` (lib/sparse.py:203-234) called from `ttm3d_seq`
  * (lib/tensor.py:7-19):  res[i0, j, k] += val * u[i1, j] * v[i2, k].

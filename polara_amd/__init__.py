@@ -5,6 +5,7 @@
     from polara_amd import HybridSVD, ScaledHybridSVD             # PureSVD with item side information (dense Cholesky)
     from polara_amd import SVDModelItemColdStart, HybridSVDItemColdStart   # item cold start (also the -s forms and MP(cs))
     from polara_amd import LCEModel, LCEModelItemColdStart          # Local Collective Embeddings, standard and item cold start
+    from polara_amd import ProbabilisticMF                          # PMF trained by a blocked SGD sweep
     from polara_amd import SVDModelSampled, RandomSampleArrayData   # sampled-negatives evaluation (1 holdout + n unseen items)
     from polara_amd import ArrayData, ShardedArrayData              # NumPy / on-disk data providers
 
@@ -92,6 +93,7 @@ _EXPORTS = {
     'SVDModelItemColdStart': 'coldstart', 'ScaledSVDItemColdStart': 'coldstart', 'HybridSVDItemColdStart': 'coldstart',
     'ScaledHybridSVDItemColdStart': 'coldstart', 'PopularityModelItemColdStart': 'coldstart',
     'LCEModel': 'lce', 'LCEModelItemColdStart': 'lce',
+    'ProbabilisticMF': 'pmf',
     'SimilarityAggregation': 'simagg', 'SimilarityAggregationItemColdStart': 'simagg',
     'ItemColdStartArrayData': 'data', 'ItemColdStartSimilarityArrayData': 'data',
     'ArrayData': 'data', 'ShardedArrayData': 'data',

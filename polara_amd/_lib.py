@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('POLARA_HIP_LIB') or os.path.join(_HERE, 'libpolarahip.so')
 
 PK_VAL_F32, PK_VAL_F64 = 0, 1
+PK_PMF_MAX_BLOCKS = 4096      # include/polara_hip.h
 
 _vp, _i32, _i64, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 
@@ -164,6 +165,10 @@ PROTOTYPES = {
     'pk_lce_dot_blocks': (_i32, [_i64]),
     'pk_lce_dots_work_bytes': (_i64, []),
     'pk_lce_dots_f64': (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp]),
+    'pk_pmf_max_rank': (_i32, []),
+    'pk_pmf_work_doubles': (_i64, [_i32]),
+    'pk_pmf_epoch_f64': (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _f64, _f64, _i32,
+                                   _vp, _i64, _vp, _i64, _f64, _f64, _vp, _vp]),
     'pk_clamp_min_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _f64]),
     'pk_ctx_create': (C.c_int, [_i32, C.POINTER(_vp)]),
     'pk_ctx_destroy': (None, [_vp]),

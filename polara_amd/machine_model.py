@@ -15,6 +15,15 @@ MI355X = {
     'lanczos_step_fixed_s': (0.3e-3, 'profiles/r06_solver_timeline_lanczos_sync_looks.txt'),
     # wall time of a nested solve that runs on a side stream next to the products (the lag of the monitors)
     'look_wall_s': (5e-3, 'profiles/r06_krylov_block_ml20m.txt (monitor waits 4-8 ms at lag 4 x 0.55 ms steps)'),
+    # the blocked SGD sweep of PMF (pmf.default_blocks).  One sample of a block's chain — dependent row loads, a cross-lane
+    # sum, two row stores: 9.28 s for the serial epoch (B = 1) of 2.0e7 samples, 0.159 s at B = 64 with a longest block of 5 209
+    'pmf_sample_s': (0.47e-6, 'profiles/pmf_bench_line.json (epoch at B = 1 and B = 64, rank 10)'),
+    # what one more stratum adds to an epoch beyond its longest block.  NOT a launch latency (the B launches are queued
+    # back to back): an effective constant that puts the rule's optimum (B = 1 370 on that matrix) inside the measured flat
+    # minimum — 34.3 ms at B = 1 024, 36.6 ms at 2 048, against 53 ms at 256 and 52 ms at 4 096
+    'pmf_launch_s': (5e-6, 'EFFECTIVE, not measured on its own: profiles/pmf_bench_line.json (epoch per B)'),
+    # PK_PMF_MAX_BLOCKS of include/polara_hip.h (the stratum sums of an epoch's squared error sit in LDS)
+    'pmf_max_blocks': (4096, 'include/polara_hip.h'),
     # bus bandwidth of a ring exchange over xGMI, per rank — ASSUMED (7 links x ~153 GB/s peak; a ring is bound by one link
     # pair): never measured, there has been no multi-GPU box
     'xgmi_bus_Bps': (100e9, 'ASSUMED: no N > 1 run over RCCL exists (SCALE_r01..r05 skipped)'),

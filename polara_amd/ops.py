@@ -1913,6 +1913,89 @@ class HipOps:
                    'pk_lce_dots_f64')
         return out
 
+    # ---- Probabilistic matrix factorisation (csrc/pmf.hip) -----------------------------------------------------------
+    def pmf_max_rank(self):
+        return int(self.lib.pk_pmf_max_rank())
+
+    def pmf_plan(self, A, blocks):
+        """The blocked schedule of pmf.block_schedule for the entries of the canonical DeviceCSR `A` [n_users x n_items],
+        built on the device with integer arithmetic only (so that it equals the host plan element for element) and the
+        library's stable radix sort of (s * B + i, position) pairs.  Returns a dict: perm, block_ptr (int64), users, items
+        (int32) and vals (fp64) in schedule order, row_nnz / col_nnz (the entry counts as fp64), blocks, nnz, shape."""
+        n_users, n_items = A.shape
+        B, nnz = int(blocks), int(A.nnz)
+        if B < 1 or B > min(n_users, n_items):
+            raise ValueError('PMF: %d blocks for %d users and %d items (1 .. min of the two)' % (B, n_users, n_items))
+        if B > _lib.PK_PMF_MAX_BLOCKS:
+            raise ValueError('PMF: %d blocks, the library takes at most %d' % (B, _lib.PK_PMF_MAX_BLOCKS))
+        if nnz >= 2 ** 31:
+            raise ValueError('PMF: %d interactions, the schedule is indexed with 32 bits' % nnz)
+        dev = self.device
+        with self._timed('pmf_plan', (n_users, n_items, nnz, B)):
+            indptr = A.indptr[:n_users + 1]
+            items = A.indices[:nnz].to(torch.int64)
+            vals = A.values[:nnz].to(torch.float64)
+            if nnz and bool((vals == 0).any().item()):
+                raise ValueError('PMF: an interaction with feedback 0 (after summing duplicates)')
+            ucnt = indptr[1:] - indptr[:-1]
+            users = torch.repeat_interleave(torch.arange(n_users, dtype=torch.int64, device=dev), ucnt, output_size=nnz)
+            icnt = self.bincount(items, n_items) if nnz else torch.zeros(n_items, dtype=torch.int64, device=dev)
+            part = lambda cnt: torch.clamp((torch.cumsum(cnt, 0) - cnt) * B // max(nnz, 1), max=B - 1)
+            i, j = part(ucnt)[users], part(icnt)[items]
+            keys = (torch.remainder(j - i, B) * B + i).to(torch.int32).contiguous()
+            block_ptr = torch.zeros(B * B + 1, dtype=torch.int64, device=dev)
+            n1 = max(nnz, 1)
+            pos = torch.arange(n1, dtype=torch.int32, device=dev)
+            in_tmp = C.c_int32(0)
+            pos_tmp = torch.empty_like(pos)
+            if nnz:
+                block_ptr[1:] = torch.cumsum(self.bincount(keys, B * B), 0)
+                keys_tmp = torch.empty_like(keys)
+                bits = max(1, int(B * B - 1).bit_length())
+                work = self._work(self.lib.pk_radix_work_bytes(nnz))
+                _lib.check(self.lib.pk_radix_sort_pairs(self.stream(), nnz, 4, _ptr(keys), _ptr(pos), _ptr(keys_tmp), _ptr(pos_tmp),
+                                                        bits, _ptr(work), C.byref(in_tmp)), 'pk_radix_sort_pairs')
+            perm = (pos_tmp if in_tmp.value else pos)[:nnz].to(torch.int64)
+            return dict(blocks=B, nnz=nnz, shape=(n_users, n_items), perm=perm, block_ptr=block_ptr,
+                        users=users[perm].to(torch.int32).contiguous(), items=items[perm].to(torch.int32).contiguous(),
+                        vals=vals[perm].contiguous(), row_nnz=ucnt.to(torch.float64).contiguous(),
+                        col_nnz=icnt.to(torch.float64).contiguous())
+
+    _PMF_ADJUST = {None: 0, 'adagrad': 1, 'rmsprop': 2}
+
+    def pmf_epoch(self, plan, P, Q, eta, lambd, adjust=None, state=None, gamma=0.9, smoothing=1e-6):
+        """One SGD sweep over the plan's interactions (pk_pmf_epoch_f64: one launch per stratum and one for the squared
+        error), P [n_users x k] and Q [n_items x k] updated in place.  adjust: None, 'adagrad' or 'rmsprop' with
+        state = (SP, SQ) of the shapes of P and Q, zeroed by the caller before every epoch.  Returns a device tensor of one
+        double: the epoch's squared error."""
+        n_users, n_items = plan['shape']
+        k = int(P.shape[1])
+        if k < 1 or k > self.pmf_max_rank():
+            raise ValueError('PMF: rank %d outside 1..%d' % (k, self.pmf_max_rank()))
+        if adjust not in self._PMF_ADJUST:
+            raise ValueError('PMF: unknown gradient adjustment %r' % (adjust,))
+        if adjust and (state is None or len(state) != 2):
+            raise ValueError('PMF: the gradient adjustment %r needs state = (SP, SQ)' % adjust)
+        blocks = (P, Q) + (tuple(state) if adjust else ())
+        for X, n in zip(blocks, (n_users, n_items) * 2):
+            if X.dtype != torch.float64 or X.dim() != 2 or tuple(X.shape) != (n, k) or X.stride(1) != 1 or X.stride(0) < k:
+                raise ValueError('PMF: a block of shape %s, strides %s for [%d x %d] fp64 rows' % (tuple(X.shape), X.stride(), n, k))
+        B = int(plan['blocks'])
+        if plan['block_ptr'].numel() != B * B + 1 or plan['users'].numel() != plan['nnz'] or plan['row_nnz'].numel() != n_users \
+                or plan['col_nnz'].numel() != n_items:
+            raise ValueError('PMF: not a plan of pmf_plan')
+        SP, SQ = state if adjust else (None, None)
+        work = self.empty(int(self.lib.pk_pmf_work_doubles(B)))       # the block sums of the squared error
+        out = self.empty(1)
+        with self._timed('pmf_epoch', (plan['nnz'], k, B)):
+            _lib.check(self.lib.pk_pmf_epoch_f64(self.stream(), B, k, int(plan['nnz']), _ptr(plan['block_ptr']), _ptr(plan['users']),
+                                                 _ptr(plan['items']), _ptr(plan['vals']), _ptr(P), P.stride(0), _ptr(Q), Q.stride(0),
+                                                 _ptr(plan['row_nnz']), _ptr(plan['col_nnz']), float(eta), float(lambd),
+                                                 self._PMF_ADJUST[adjust], _ptr(SP), SP.stride(0) if adjust else 0, _ptr(SQ),
+                                                 SQ.stride(0) if adjust else 0, float(gamma), float(smoothing), _ptr(work), _ptr(out)),
+                       'pk_pmf_epoch_f64')
+        return out
+
     def dense_scores(self, V, E):
         n_rows, K = E.shape
         n_items = V.shape[0]
