@@ -663,6 +663,36 @@ int pk_spsp_topk(void *stream, int64_t n_rows, int64_t n_inner, int64_t n_cols, 
 int pk_spsp_rows_f64(void *stream, int64_t row0, int64_t n_rows, int64_t n_inner, int64_t n_cols, const int64_t *l_indptr_dev,
                      const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind, const int64_t *b_indptr_dev,
                      const int32_t *b_indices_dev, const double *b_values_dev, double *out_dev, int64_t ld);
+/* ---- row-wise sparse x sparse product with CSR output and the similarity epilogues (csrc/spgemm.hip) ----------------
+ * C = L . B over the operands of pk_spsp_topk, in its summation order, written as a canonical CSR (int64 indptr, int32
+ * indices strictly ascending per row, fp64 values).
+ *   op        PK_SPGEMM_OP_MUL: acc + v * b, separately rounded (bit-equal to SciPy's product); PK_SPGEMM_OP_MIN: acc + min(v, b).
+ *   stored    an entry whose sum is != 0 (-0 is not); with diag = 1 (n_rows == n_cols) entry (r, r) always, as 1.0.
+ *   epilogue  of a stored off-diagonal entry with sum s: PK_SPGEMM_EPI_NONE: s; PK_SPGEMM_EPI_JACCARD:
+ *             s / ((nf_cols[c] + nf_rows[r]) - s); PK_SPGEMM_EPI_WJACCARD (op = MIN): s / max_sum, max_sum added up as in the
+ *             reference's _jaccard_similarity_weighted_tri for the pair (i, j): over the features of j ascending, a matched
+ *             one adds max(dat_i, dat_j), an unmatched one dat_j, then the unmatched features of i ascending.
+ *             wj_rect = 0: i = min(r, c), j = max(r, c), both rows taken from the CSR f_* (n_rows == n_cols);
+ *             wj_rect = 1: j = row r of L, i = row c of f_*.  f_*: the column side's features by item (n_cols rows, sorted
+ *             columns, fp64); L's rows must be sorted too.
+ * pk_spgemm_count writes C.indptr (n_rows + 1) and keeps the offsets of every (row, window) in work; the caller reads
+ * nnz = indptr[n_rows], allocates and calls pk_spgemm_fill with the SAME operands, op, diag and work.  n_cols < 2^30. */
+#define PK_SPGEMM_OP_MUL 0
+#define PK_SPGEMM_OP_MIN 1
+#define PK_SPGEMM_EPI_NONE 0
+#define PK_SPGEMM_EPI_JACCARD 1
+#define PK_SPGEMM_EPI_WJACCARD 2
+int64_t pk_spgemm_work_bytes(int64_t n_rows, int64_t n_cols);
+int pk_spgemm_count(void *stream, int64_t n_rows, int64_t n_inner, int64_t n_cols, const int64_t *l_indptr_dev,
+                    const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind, const int64_t *b_indptr_dev,
+                    const int32_t *b_indices_dev, const double *b_values_dev, int32_t op, int32_t diag, int64_t *indptr_out_dev,
+                    void *work_dev);
+int pk_spgemm_fill(void *stream, int64_t n_rows, int64_t n_inner, int64_t n_cols, const int64_t *l_indptr_dev,
+                   const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind, const int64_t *b_indptr_dev,
+                   const int32_t *b_indices_dev, const double *b_values_dev, int32_t op, int32_t diag, int32_t epilogue,
+                   int32_t wj_rect, const double *nf_rows_dev, const double *nf_cols_dev, const int64_t *f_indptr_dev,
+                   const int32_t *f_indices_dev, const double *f_values_dev, const void *work_dev, int64_t nnz,
+                   int32_t *out_indices_dev, double *out_values_dev);
 /* ---- sampled-negatives evaluation (csrc/sampled.hip; models.py:1095-1183, lib/sparse.py::inner_product_at,
  * lib/sampler.py::mf_random_item_scoring) ------------------------------------------------------------------------------
  * Limits (host functions): the candidates per user the fused launch keeps in LDS, the largest rank, the largest sample. */

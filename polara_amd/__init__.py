@@ -95,6 +95,8 @@ _EXPORTS = {
     'LCEModel': 'lce', 'LCEModelItemColdStart': 'lce',
     'ProbabilisticMF': 'pmf',
     'SimilarityAggregation': 'simagg', 'SimilarityAggregationItemColdStart': 'simagg',
+    'cosine_similarity': 'similarity', 'cosine_tfidf_similarity': 'similarity', 'jaccard_similarity': 'similarity',
+    'jaccard_similarity_weighted': 'similarity', 'cross_similarity': 'similarity', 'combine_similarity': 'similarity',
     'ItemColdStartArrayData': 'data', 'ItemColdStartSimilarityArrayData': 'data',
     'ArrayData': 'data', 'ShardedArrayData': 'data',
     'RandomSampleEvaluationMixin': 'data', 'RandomSampleArrayData': 'data',

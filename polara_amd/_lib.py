@@ -142,6 +142,10 @@ PROTOTYPES = {
     'pk_spsp_topk_work_bytes': (_i64, [_i64, _i64, _i32]),
     'pk_spsp_topk': (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     'pk_spsp_rows_f64': (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _i64]),
+    'pk_spgemm_work_bytes': (_i64, [_i64, _i64]),
+    'pk_spgemm_count': (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    'pk_spgemm_fill': (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     'pk_candidates_fused_max': (_i32, []),
     'pk_candidates_max_rank': (_i32, []),
     'pk_sample_max_n': (_i32, []),

@@ -1647,6 +1647,56 @@ class HipOps:
                                                  _ptr(self._spsp_values(B)), _ptr(out), n_cols), 'pk_spsp_rows_f64')
         return out
 
+    # ---- sparse x sparse product with CSR output and the similarity epilogues (csrc/spgemm.hip) -------------------
+    SPGEMM_OPS = {'mul': 0, 'min': 1}
+    SPGEMM_EPILOGUES = {'none': 0, 'jaccard': 1, 'wjaccard': 2}
+
+    def spgemm_csr(self, L, B, op='mul', epilogue='none', diag=False, nf_rows=None, nf_cols=None, col_features=None,
+                   rectangular=False):
+        """The canonical DeviceCSR (fp64) of L B for the device CSR L (rows summed in their stored order) and the canonical
+        device CSR B: pk_spgemm_count (the entries of every (row, window), their scan: indptr) and pk_spgemm_fill (the
+        windows again, compacted).  An entry is stored when its sum is != 0; `diag` stores every (r, r) as 1.0.
+        epilogue 'jaccard' needs the fp64 entry counts `nf_rows`, `nf_cols` (host or device); 'wjaccard' needs op='min',
+        sorted rows in L and `col_features`, the DeviceCSR of the column side's features by item — `rectangular`: the pair
+        is walked with the row as j, else with j = max(r, c) (see include/polara_hip.h).  `build_stats`-style timings
+        go to the kernel timers as 'spgemm_count' and 'spgemm_fill'."""
+        from . import simagg
+        n_rows, n_inner, n_cols = simagg.check_shapes(L.shape, B.shape)
+        if op not in self.SPGEMM_OPS or epilogue not in self.SPGEMM_EPILOGUES:
+            raise ValueError('spgemm_csr: unknown op %r or epilogue %r' % (op, epilogue))
+
+        def vec(x, n, what):
+            if x is None:
+                return None
+            x = x if torch.is_tensor(x) else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64))
+            x = x.to(device=self.device, dtype=torch.float64).contiguous()
+            if x.numel() != n:
+                raise ValueError('spgemm_csr: %s has %d entries, %d expected' % (what, x.numel(), n))
+            return x
+        nf_r, nf_c = vec(nf_rows, n_rows, 'nf_rows'), vec(nf_cols, n_cols, 'nf_cols')
+        Fc = col_features
+        if Fc is not None and Fc.shape[0] != n_cols:
+            raise ValueError('spgemm_csr: col_features has %d rows, the product %d columns' % (Fc.shape[0], n_cols))
+        f_values = self._spsp_values(Fc) if Fc is not None else None
+        b_values = self._spsp_values(B)
+        head = (self.stream(), n_rows, n_inner, n_cols, _ptr(L.indptr), _ptr(L.indices), _ptr(L.values), L.val_kind,
+                _ptr(B.indptr), _ptr(B.indices), _ptr(b_values), self.SPGEMM_OPS[op], 1 if diag else 0)
+        indptr = torch.empty(n_rows + 1, dtype=torch.int64, device=self.device)
+        work = self._work(self.lib.pk_spgemm_work_bytes(n_rows, n_cols))
+        with self._timed('spgemm_count', (n_rows, n_cols, L.nnz)):
+            _lib.check(self.lib.pk_spgemm_count(*head, _ptr(indptr), _ptr(work)), 'pk_spgemm_count')
+        nnz = int(indptr[-1].item())
+        indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=self.device)[:nnz]
+        values = torch.empty(max(nnz, 1), dtype=torch.float64, device=self.device)[:nnz]
+        with self._timed('spgemm_fill', (n_rows, n_cols, nnz)):
+            _lib.check(self.lib.pk_spgemm_fill(*head, self.SPGEMM_EPILOGUES[epilogue], 1 if rectangular else 0, _ptr(nf_r),
+                                               _ptr(nf_c), _ptr(Fc.indptr) if Fc is not None else None,
+                                               _ptr(Fc.indices) if Fc is not None else None, _ptr(f_values), _ptr(work), nnz,
+                                               _ptr(indices), _ptr(values)), 'pk_spgemm_fill')
+        out = DeviceCSR.from_device(self, indptr, indices, values, (n_rows, n_cols))
+        out._nnz = nnz
+        return out
+
     # ---- sampled-negatives evaluation (csrc/sampled.hip) ---------------------------------------------------------
     def candidates_topk(self, P, V, cand, topk, want_scores=False):
         """int64 [n_users x topk] column POSITIONS of the best candidates of every user (and the fp64 scores

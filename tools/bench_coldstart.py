@@ -7,6 +7,7 @@ Prints ONE JSON line per model:
            share of the sweep's tiles scored, flagged queries, launches of a pass (library calls on the stream);
   queries: seconds of the pass's front end alone, E = (F_cold W) G (SpMM + small product), median of 50;
   cpu (with --cpu): seconds of the NumPy restatement of the same pass on this machine and the rows whose lists differ.
+--device-similarity builds S with polara_amd.similarity on the device instead of SciPy (the default).
 Timings are synchronised; nothing here is part of bench.py."""
 import json
 import os
@@ -54,7 +55,12 @@ def item_features(n_items, n_labels=3000, per_item=8, seed=7):
     return F
 
 
-def cosine(F):
+def cosine(F, ops=None):
+    """S by SciPy on the host (the default: earlier numbers stay comparable) or, given `ops` (--device-similarity), by
+    polara_amd.similarity.cosine_similarity on the device."""
+    if ops is not None:
+        from polara_amd.similarity import cosine_similarity
+        return cosine_similarity(F, ops=ops)
     Fn = sps.diags(1.0 / np.sqrt(np.asarray(F.sum(1)).ravel())) @ F
     S = (Fn @ Fn.T).tocsr()
     S.setdiag(1.0)
@@ -88,7 +94,7 @@ def run(ops, hybrid, u, i, v, n_users, n_items, F, rank, topk, cpu):
     Ft, Fc = F[train_ids].tocsr(), F[np.sort(cold_items)].tocsr()
     kw = dict(n_users=n_users, n_items=len(train_ids))
     if hybrid:
-        S = cosine(Ft)
+        S = cosine(Ft, ops if '--device-similarity' in sys.argv else None)
         rel = dict(relations_matrices={'itemid': S, 'userid': None}, relations_indices={'itemid': None, 'userid': None})
         data = ItemColdStartSimilarityArrayData(training, holdout, Ft, Fc, **rel, **kw)
         parent = HybridSVD(SimilarityArrayData(training, holdout=(np.arange(n_users), np.zeros(n_users, np.int64), np.ones(n_users)),

@@ -7,6 +7,7 @@ top-10, every user a test user, with S the cosine similarity of seeded sparse bi
   cpu (with --cpu): SciPy's cholesky of the same K on the host, and how many rows of a seeded 2 000-user sample are
        tie-aware identical to the restatement's lists (tests/hybrid_reference.py: T vr vl^T on the host) from the
        model's projectors.
+--device-similarity builds S with polara_amd.similarity on the device instead of SciPy (the default).
 Timings: the second of two identical calls, synchronised."""
 import json
 import os
@@ -37,13 +38,16 @@ def timed(fn):
     return out, time.perf_counter() - t0
 
 
-def item_similarity(n_items, n_features=2000, density=0.004, seed=7):
+def item_similarity(n_items, n_features=2000, density=0.004, seed=7, ops=None):
     rng = np.random.default_rng(seed)
     nnz = int(n_items * n_features * density)
     F = sps.csr_matrix((np.ones(nnz), (rng.integers(0, n_items, nnz), rng.integers(0, n_features, nnz))),
                        shape=(n_items, n_features))
     F = F + sps.csr_matrix((np.ones(n_items), (np.arange(n_items), rng.integers(0, n_features, n_items))), shape=F.shape)
     F.data[:] = 1.0
+    if ops is not None:              # --device-similarity: the same S by polara_amd.similarity on the device
+        from polara_amd.similarity import cosine_similarity
+        return cosine_similarity(F, ops=ops)
     Fn = sps.diags(1.0 / np.sqrt(np.asarray(F.sum(1)).ravel())) @ F
     S = (Fn @ Fn.T).tocsr()
     S.setdiag(1.0)
@@ -58,7 +62,7 @@ def main():
     n_users, n_items = (int(x) for x in csr['shape'])
     del csr
     rank, topk = 50, 10
-    S = item_similarity(n_items)
+    S = item_similarity(n_items, ops=ops if '--device-similarity' in sys.argv else None)
     out = dict(workload='ml20m', n_users=n_users, n_items=n_items, nnz=int(len(v)), s_nnz=int(S.nnz), rank=rank, topk=topk)
     perm = np.random.default_rng(0).permutation(n_items)
 

@@ -10,6 +10,7 @@ item, popularity-skewed: tools/bench_coldstart.py), topk 10.  Prints ONE JSON li
           cold items per second, pads;
   cpu (with --cpu): SciPy's product and a NumPy selection of a seeded sample of rows of both passes on the host (rows per
           second), and the number of sample rows whose device list equals the host's exactly.
+--device-similarity builds S with polara_amd.similarity on the device instead of SciPy (the default).
 Timings: the second of two identical calls (the first pays allocations and code loads), synchronised."""
 import json
 import os
@@ -66,7 +67,7 @@ def main():
     out = dict(workload='ml20m', n_users=n_users, n_items=n_items, nnz=int(len(v)), n_labels=int(F.shape[1]), topk=topk)
 
     # ---- SIM: every user a test user ------------------------------------------------------------------------------
-    S = cosine(F)
+    S = cosine(F, ops if '--device-similarity' in sys.argv else None)      # default: SciPy on the host, as before
     rel = dict(relations_matrices={'itemid': S, 'userid': None}, relations_indices={'itemid': None, 'userid': None})
     hold = (np.arange(n_users), np.zeros(n_users, np.int64), np.ones(n_users))
     data = SimilarityArrayData((u, i, v), n_users=n_users, n_items=n_items, holdout=hold, warm_start=False, **rel)
