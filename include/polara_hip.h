@@ -831,6 +831,33 @@ int pk_pmf_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, co
                      double smoothing, double *work_dev, double *sse_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Implicit ALS (csrc/ials.hip): the alternating least squares of Hu, Koren and Volinsky for a CSR of confidences C
+ * [n_rows x n_cols] (fp64 values, int64 row pointers, int32 column ids).  One half-step fixes Y [n_cols x rank] and solves
+ * for every row u
+ *     A_u = G + lambda I + sum_{i in row u} (c_ui - 1) y_i y_i^T,    b_u = sum_i c_ui y_i,    x_u = A_u^-1 b_u
+ * with G = Y^T Y from the caller (pk_gram_f64).  One workgroup per row, taken in the order row_order_dev lists them (a
+ * permutation of 0 .. n_rows - 1, longest rows first; NULL: ascending).  Everything is fp64.  The sum over a row runs in
+ * storage order in groups of four (v_mfma_f64_16x16x4_f64 over the lower-triangular 16 x 16 tiles, accumulators started from
+ * G + lambda I); b_u is summed entry after entry in storage order; A_u is factored by a right-looking Cholesky in LDS and
+ * solved by forward and back substitution.  The order of every summation depends on the row alone: equal inputs give equal
+ * bits, whatever the row order.  No atomics.  An empty row gives x_u = 0 exactly.
+ * info_dev: two int32 — the number of rows with a pivot that is not > 0 (NaN included) and the first such row (-1: none);
+ * the rows of X of those are written as zeros.  work_dev: pk_ials_work_bytes(n_rows, rank) bytes.  Column ids outside
+ * 0 .. n_cols - 1 contribute nothing.
+ * pk_ials_loss_nz_f64: out_dev[0] = sum over stored entries of c (1 - s)^2 - s^2 with s = x_u . y_i — the sparse term of
+ *     sum_all-pairs w (p - s)^2 + lambda (|X|^2 + |Y|^2) = tr(X^T X Y^T Y) + sparse term + lambda (tr X^T X + tr Y^T Y);
+ * one wave per row, terms added in storage order, row sums added in a fixed order. */
+int32_t pk_ials_max_rank(void);
+int64_t pk_ials_work_bytes(int64_t n_rows, int32_t rank);
+int pk_ials_half_step_f64(void *stream, int64_t n_rows, int64_t n_cols, int32_t rank, const int64_t *indptr_dev,
+                          const int32_t *indices_dev, const double *conf_dev, const int32_t *row_order_dev, const double *Y_dev,
+                          int64_t ldy, const double *G_dev, int64_t ldg, double lambda, double *X_dev, int64_t ldx,
+                          int32_t *info_dev, void *work_dev);
+int pk_ials_loss_nz_f64(void *stream, int64_t n_rows, int64_t n_cols, int32_t rank, const int64_t *indptr_dev,
+                        const int32_t *indices_dev, const double *conf_dev, const double *X_dev, int64_t ldx, const double *Y_dev,
+                        int64_t ldy, double *out_dev, void *work_dev);
+
+/* ------------------------------------------------------------------------------------------
  * K5.  Sparse tensor-times-matrix (CoFFee / HOOI).
  * Replaces numba `dttm_seq` / `dttm_par` (lib/sparse.py:203-234) called from `ttm3d_seq`
  * (lib/tensor.py:7-19):  res[i0, j, k] += val * u[i1, j] * v[i2, k].

@@ -173,6 +173,10 @@ PROTOTYPES = {
     'pk_pmf_work_doubles': (_i64, [_i32]),
     'pk_pmf_epoch_f64': (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _f64, _f64, _i32,
                                    _vp, _i64, _vp, _i64, _f64, _f64, _vp, _vp]),
+    'pk_ials_max_rank': (_i32, []),
+    'pk_ials_work_bytes': (_i64, [_i64, _i32]),
+    'pk_ials_half_step_f64': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _i64, _vp, _vp]),
+    'pk_ials_loss_nz_f64': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     'pk_clamp_min_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _f64]),
     'pk_ctx_create': (C.c_int, [_i32, C.POINTER(_vp)]),
     'pk_ctx_destroy': (None, [_vp]),

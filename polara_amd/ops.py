@@ -2046,6 +2046,114 @@ class HipOps:
                        'pk_pmf_epoch_f64')
         return out
 
+    # ---- Implicit ALS (csrc/ials.hip) ----------------------------------------------------------------------------------
+    def ials_max_rank(self):
+        return int(self.lib.pk_ials_max_rank())
+
+    def csr_values_host(self, A):
+        """the stored values of a DeviceCSR as a host fp64 array (storage order)"""
+        return self.to_host(A.values.to(torch.float64))
+
+    def csr_replace_values(self, A, values, drop_zeros=False):
+        """The DeviceCSR `A` with the host fp64 array `values` in place of its stored values (same pattern and plans);
+        drop_zeros: entries whose new value is exactly 0 leave the pattern (a new matrix when there are any)."""
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        if values.shape != (int(A.indices.numel()),):
+            raise ValueError('csr_replace_values: %s values for %d stored entries' % (values.shape, A.indices.numel()))
+        keep = values != 0 if drop_zeros else None
+        if keep is None or keep.all():
+            new = A.with_columns(A.indices, self.to_device(values))
+            new.val_kind = _lib.PK_VAL_F64
+            return new
+        csum = np.concatenate(([0], np.cumsum(keep, dtype=np.int64)))
+        indptr = csum[self.to_host(A.indptr)]
+        keep_dev = self.to_device(keep)
+        new = DeviceCSR.from_device(self, self.to_device(indptr), A.indices[keep_dev].contiguous(), self.to_device(values[keep]),
+                                    A.shape, A.split)
+        new._nnz = int(csum[-1])
+        new.sorted_cols = A.sorted_cols
+        return new
+
+    def _ials_row_order(self, Cm):
+        """int32 [n_rows] on the device: the rows of `Cm` by descending length, ties by row (the library's stable radix sort);
+        kept on the matrix"""
+        order = getattr(Cm, '_ials_order', None)
+        if order is None:
+            n = int(Cm.shape[0])
+            lengths = (Cm.indptr[1:n + 1] - Cm.indptr[:n]).to(torch.int32)
+            longest = int(lengths.max().item()) if n else 0
+            keys = (longest - lengths).contiguous()
+            pos = torch.arange(max(n, 1), dtype=torch.int32, device=self.device)[:n].contiguous()
+            if n > 1 and longest > 0:
+                keys_tmp, pos_tmp = torch.empty_like(keys), torch.empty_like(pos)
+                in_tmp = C.c_int32(0)
+                work = self._work(self.lib.pk_radix_work_bytes(n))
+                _lib.check(self.lib.pk_radix_sort_pairs(self.stream(), n, 4, _ptr(keys), _ptr(pos), _ptr(keys_tmp), _ptr(pos_tmp),
+                                                        max(1, longest.bit_length()), _ptr(work), C.byref(in_tmp)),
+                           'pk_radix_sort_pairs')
+                pos = pos_tmp if in_tmp.value else pos
+            order = Cm._ials_order = pos
+        return order
+
+    def _ials_check(self, Cm, X, Y, what):
+        k = int(Y.shape[1])
+        if k < 1 or k > self.ials_max_rank():
+            raise ValueError('iALS: rank %d outside 1..%d' % (k, self.ials_max_rank()))
+        for M, n in ((X, Cm.shape[0]), (Y, Cm.shape[1])):
+            if M is not None and (M.dtype != torch.float64 or M.dim() != 2 or tuple(M.shape) != (n, k) or M.stride(1) != 1
+                                  or M.stride(0) < k):
+                raise ValueError('iALS %s: a block of shape %s, strides %s for [%d x %d] fp64 rows'
+                                 % (what, tuple(M.shape), M.stride(), n, k))
+        return k
+
+    def ials_half_step(self, Cm, Y, regularization, out=None, G=None, row_order=None):
+        """One half-step of the alternating least squares (pk_ials_half_step_f64): for every row u of the DeviceCSR of
+        confidences `Cm` [n_rows x n_cols], x_u = (G + lambda I + sum_i (c_ui - 1) y_i y_i^T)^-1 sum_i c_ui y_i against the
+        fixed block Y [n_cols x k].  G = Y^T Y (computed by `gram` when None).  Returns X [n_rows x k] (`out` when given: a
+        view with a leading dimension is fine).  A row whose matrix is not positive definite raises a ValueError naming
+        how many there are and the first; their rows of X hold zeros.  row_order: int32 device permutation of the rows
+        (None: by descending length) — it changes which workgroup starts when, never a bit of the result."""
+        n_rows, n_cols = Cm.shape
+        k = self._ials_check(Cm, out, Y, 'half-step')
+        if G is None:
+            G = self.gram(Y)
+        if G.dtype != torch.float64 or tuple(G.shape) != (k, k) or G.stride(1) != 1:
+            raise ValueError('iALS half-step: G of shape %s for rank %d' % (tuple(G.shape), k))
+        X = self.empty(n_rows, k) if out is None else out
+        conf = Cm.values if Cm.values.dtype == torch.float64 else Cm.values.to(torch.float64)
+        order = self._ials_row_order(Cm) if row_order is None else row_order
+        if order.dtype != torch.int32 or order.numel() != n_rows or not order.is_contiguous():
+            raise ValueError('iALS half-step: row_order must be a contiguous int32 permutation of the %d rows' % n_rows)
+        info = torch.empty(2, dtype=torch.int32, device=self.device)
+        work = self._work(self.lib.pk_ials_work_bytes(n_rows, k))
+        with self._timed('ials_half_step', (n_rows, n_cols, int(Cm.indices.numel()), k)):
+            _lib.check(self.lib.pk_ials_half_step_f64(self.stream(), n_rows, n_cols, k, _ptr(Cm.indptr), _ptr(Cm.indices), _ptr(conf),
+                                                      _ptr(order), _ptr(Y), Y.stride(0), _ptr(G), G.stride(0), float(regularization),
+                                                      _ptr(X), X.stride(0), _ptr(info), _ptr(work)), 'pk_ials_half_step_f64')
+        bad, first = (int(v) for v in info.tolist())
+        if bad:
+            raise ValueError('iALS half-step: %d row(s) whose normal equations are not positive definite, the first is row %d '
+                             '(their factors are set to zero)' % (bad, first))
+        return X
+
+    def ials_loss(self, Cm, X, Y, regularization, GX=None, GY=None):
+        """The objective  sum over ALL pairs of w (p - x_u . y_i)^2 + lambda (|X|^2 + |Y|^2)  (w = c, p = 1 on the stored
+        entries of `Cm`; w = 1, p = 0 elsewhere) as a float:  tr(X^T X Y^T Y) + the sparse term (pk_ials_loss_nz_f64) +
+        lambda (tr X^T X + tr Y^T Y).  GX / GY: the Gram matrices when the caller has them."""
+        n_rows, n_cols = Cm.shape
+        k = self._ials_check(Cm, X, Y, 'loss')
+        GX = self.gram(X) if GX is None else GX
+        GY = self.gram(Y) if GY is None else GY
+        conf = Cm.values if Cm.values.dtype == torch.float64 else Cm.values.to(torch.float64)
+        out = self.empty(1)
+        work = self._work(self.lib.pk_ials_work_bytes(n_rows, k))
+        with self._timed('ials_loss', (n_rows, n_cols, int(Cm.indices.numel()), k)):
+            _lib.check(self.lib.pk_ials_loss_nz_f64(self.stream(), n_rows, n_cols, k, _ptr(Cm.indptr), _ptr(Cm.indices), _ptr(conf),
+                                                    _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), _ptr(out), _ptr(work)),
+                       'pk_ials_loss_nz_f64')
+        gx, gy = self.to_host(GX), self.to_host(GY)
+        return float((gx * gy).sum() + float(out[0].item()) + float(regularization) * (np.trace(gx) + np.trace(gy)))
+
     def dense_scores(self, V, E):
         n_rows, K = E.shape
         n_items = V.shape[0]

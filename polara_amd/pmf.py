@@ -18,6 +18,7 @@ import numpy as np
 
 from . import machine_model, scoring
 from .csr import coo_to_csr
+from .factor_serving import FactorQueriesMixin
 from .models import RecommenderModel
 
 ADJUSTERS = ('adagrad', 'rmsprop')      # optimize.py:73-86, with the reference's defaults below (its boilerplate passes the
@@ -160,7 +161,7 @@ def pmf_sgd(ops, matrix, rank, lrate, sigma, num_epochs, tol, adjust_gradient=No
     return P, Q
 
 
-class ProbabilisticMF(RecommenderModel):
+class ProbabilisticMF(FactorQueriesMixin, RecommenderModel):
     """models.py:728-787.  `factors` holds host arrays — users [n_users x k], items [n_items x k] — and the device copy of
     the user factors stays for the passes.  `blocks` (None: `default_blocks`) is the B of the blocked sweep; with blocks = 1
     the samples are swept in the reference's order.  A rank change invalidates the model."""
@@ -246,61 +247,3 @@ class ProbabilisticMF(RecommenderModel):
         self._factor_image = scoring.FactorImage(ops, Qs)
         self._factor_src = self.factors[itemid]
         self._test_dev = None
-
-    # ---- passes ------------------------------------------------------------------------------------------------------
-    def _user_factors_block(self):
-        """P [n_users x k] on the device: the block of the build, or an upload when `factors` was swapped"""
-        P = self.factors.get(self.data.fields.userid, None)
-        if P is None:
-            raise ValueError('%s: no user factors (build the model first)' % self.method)
-        kept = self._factors_dev
-        if kept is None or kept[0] is not P:
-            kept = self._factors_dev = (P, self.ops.to_device(np.ascontiguousarray(P, dtype=np.float64)))
-        return kept[1]
-
-    def _user_rows(self, users):
-        """rows `users` of P with an even leading dimension (what the sweep reads its queries' rows at)"""
-        ops = self.ops
-        P = self._user_factors_block()
-        k = int(P.shape[1])
-        block = ops.zeros(len(users), k + (k & 1))
-        block[:, :k] = P[ops.to_device(np.ascontiguousarray(users, dtype=np.int64))]
-        return block[:, :k]
-
-    def get_recommendations(self):
-        if self.data.warm_start:
-            raise NotImplementedError('%s has no warm start' % self.method)
-        if self.verify_integrity:
-            self.verify_data_integrity()
-        ops = self.ops
-        T, n_users, n_items = self._device_test_csr()
-        test_users = np.asarray(self._get_test_data()[2], dtype=np.int64)
-        if len(test_users) != n_users:
-            raise ValueError('%d test users, the test matrix has %d rows' % (len(test_users), n_users))
-        if n_users == 0:
-            return np.empty((0, self.topk), dtype=np.int64)
-        stats = {}
-        recs_dev = scoring.recommend(ops, self._item_factors_device(), T, self.topk, self.filter_seen,
-                                     stats=stats if self.collect_recommend_stats else None, queries=self._user_rows(test_users))
-        self.recommend_stats = stats
-        if hasattr(ops, 'ids_to_host'):
-            recs = ops.ids_to_host(recs_dev, self._item_inv)
-        else:
-            recs = ops.to_host(recs_dev)
-            recs = np.where(recs >= 0, self._item_inv[np.maximum(recs, 0)], -1).astype(np.int64)
-        self._recs_dev = (recs, recs_dev)
-        return recs
-
-    def slice_recommendations(self, test_data, shape, start, stop, test_users=None):
-        """models.py:779-787: the dense fp64 scores of test users [start, stop) against every item (external item order)
-        and the slice triplet."""
-        if test_users is None:
-            test_users = self._get_test_data()[2]
-        stop = min(stop, shape[0])
-        slice_data = self._slice_test_data(test_data, start, stop)
-        image = self._item_factors_device()
-        E = self._user_rows(np.asarray(test_users)[start:stop]).contiguous()
-        scores = self.ops.to_host(self.ops.dense_scores(image.V, E))
-        out = np.empty_like(scores)
-        out[:, self._item_inv] = scores
-        return out, slice_data
