@@ -323,6 +323,15 @@ int pk_score_candidates_rows_f32(void *stream, int64_t n_users, int64_t n_items,
                                  int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk /* 0 = auto */,
                                  const float *tile_bound_dev /* or NULL */, const uint32_t *seen_dense_dev,
                                  const int32_t *seen_skip_dev, int32_t dense_tiles);
+/* ... and the users' side of the pruning bound left in user_bound_out_dev (float [n_users], or NULL): bound_u above, an
+ * upper bound of ||E_u|| — four bytes per user, stored by the sweep's prologue, for pk_rescore_topk_rows_settle_f64. */
+int pk_score_candidates_rows_bound_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                                       const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
+                                       double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
+                                       const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits, float *cand_score_dev,
+                                       int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk /* 0 = auto */,
+                                       const float *tile_bound_dev /* or NULL */, const uint32_t *seen_dense_dev,
+                                       const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev);
 /* The pruned sweep in TWO PHASES (replaces the same reference lines: the chunk loop body of models.py:359-371, with
  * downvote_seen_items :494-519 and topsort :488-491 fused in).  A launch of the single sweep lasts as long as its slowest
  * wave — the groups of the heaviest users stay ~270 tiles in the sweep, everybody else 70-130 — so the catalogue is
@@ -355,6 +364,15 @@ int pk_score_two_phase_rows_f32(void *stream, int64_t n_users, int64_t n_items, 
                                 float *work_score_dev, int32_t *work_idx_dev, float *cand_score_dev, int32_t *cand_idx_dev,
                                 void *state_dev, int32_t tiles_per_chunk, const float *tile_bound_dev,
                                 const uint32_t *seen_dense_dev, const int32_t *seen_skip_dev, int32_t dense_tiles);
+/* ... and user_bound_out_dev as in pk_score_candidates_rows_bound_f32 */
+int pk_score_two_phase_rows_bound_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                                      const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
+                                      double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
+                                      const int32_t *seen_ntiles_dev, int32_t KC, int32_t head_tiles, int32_t splits,
+                                      float *work_score_dev, int32_t *work_idx_dev, float *cand_score_dev, int32_t *cand_idx_dev,
+                                      void *state_dev, int32_t tiles_per_chunk, const float *tile_bound_dev,
+                                      const uint32_t *seen_dense_dev, const int32_t *seen_skip_dev, int32_t dense_tiles,
+                                      float *user_bound_out_dev);
 /* Dense seen masks for the first dense_tiles tiles of the catalogue — where the sweep spends its time, and where a user
  * has a record in nearly every tile: dense_dev[(u / 32 * dense_tiles + tile) * 32 + u % 32] = the user's 32-bit mask in
  * that tile (one coalesced 128-byte load per tile and wave instead of a cursor walk with a scattered 8-byte load per
@@ -472,6 +490,37 @@ int pk_rescore_topk_rows_perm_f64(void *stream, int64_t n_rows, const int32_t *r
                              int64_t *out_idx_dev, double *out_score_dev, int32_t *flags_dev,
                              int32_t *flagged_list_dev, int32_t *flagged_count_dev, int32_t flagged_offset,
                              const float *item_norm_dev, const int64_t *out_perm_dev);
+/* ... and with the SETTLE TIER: user_norm_dev (float [n_users], or NULL = the call above) holds N_u >= ||E'_u||, the users'
+ * side of the sweep's pruning bound (pk_pack_frag_bound_f32's bound_dev, or what pk_score_*_rows_bound_f32 stored).  Active
+ * only on the first call over an approximate E — V32_dev and e_err_dev given, e_exact = 0, rows_dev = NULL.  The sweep's
+ * fp32 score of an item is within d_i = (B N_u + 2^-24 e_err[u]) n_i of its exact score, B = 3 * 2^-16 + (4 K + 10) * 2^-23,
+ * n_i = item_norm[i] or v_row_norm_max.  A user whose candidates, sorted by their sweep scores, keep more than d + d'
+ * between neighbours down to the (topk+1)-th, between the topk-th and every later entry, and between the topk-th and the
+ * bound on the items the sweep left out (tau_cert: d_topk + d at n = v_row_norm_max) is SETTLED: its ids are written in that
+ * order — the exact one — without gathering an item row or reading its row of E; flags[u] = 8 (above the mask 7 of the
+ * lists: such a user is on no list), its out_score row is not written.  Ties, unbounded lists and users with fewer than
+ * topk unseen items never settle and take the path of the call above, bit for bit.
+ * pk_set_option("rescore_settle", 0) switches the tier off in every call. */
+int pk_rescore_topk_rows_settle_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
+                             const int32_t *n_rows_dev, int64_t n_users, int64_t n_items,
+                             int32_t K, const double *V_dev, int64_t ldv,
+                             const float *V32_dev, int64_t ldv32,
+                             const double *E_dev, int64_t lde,
+                             const double *e_err_dev, int64_t e_err_ld, int32_t e_exact,
+                             const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
+                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
+                             double v_row_norm_max,
+                             int64_t *out_idx_dev, double *out_score_dev, int32_t *flags_dev,
+                             int32_t *flagged_list_dev, int32_t *flagged_count_dev, int32_t flagged_offset,
+                             const float *item_norm_dev, const int64_t *out_perm_dev, const float *user_norm_dev);
+/* The same pointer for a caller that keeps to the older entries above (a recorded call sequence that is fixed): the bound
+ * is left with the stream FOR ONE CALL.  The next call of pk_rescore_topk_rows_perm_f64 (or of an entry that forwards to it)
+ * on that stream takes it as its user_norm_dev if it is the call named — same n_users, same flags_dev — and drops it
+ * otherwise; the binding is gone afterwards either way, also when that call fails.  NULL clears a pending one.  Host-side
+ * bookkeeping (thread-safe), nothing is enqueued.  This is state between two calls: bind immediately in front of the call
+ * it is meant for, keep the array alive until that call is issued, and prefer pk_rescore_topk_rows_settle_f64, which takes
+ * the pointer as an argument, wherever the entry is free to choose. */
+int pk_rescore_bind_user_norm(void *stream, const float *user_norm_dev, int64_t n_users, const int32_t *flags_dev);
 int pk_zero_i32(void *stream, int32_t *p_dev, int32_t n);
 /* The re-do of flagged users without a host round trip: pk_flag_compact lists the users with (flags & mask) != 0
  * (list capacity n, *count_dev = list length), pk_fold_rows_f64 recomputes the listed rows of E = A_test V in fp64

@@ -77,6 +77,10 @@ PROTOTYPES = {
                                                _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32]),
     'pk_score_two_phase_rows_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _i32, _i32, _i32,
                                               _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32]),
+    'pk_score_candidates_rows_bound_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _i32, _i32,
+                                                     _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    'pk_score_two_phase_rows_bound_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _i32, _i32,
+                                                    _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
     'pk_score_two_phase_plan': (C.c_int, [_i64, _i64, _i32, _vp, _vp]),
     'pk_score_two_phase_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                          _i32, _vp, _vp, _vp, _vp, _i32]),
@@ -111,6 +115,9 @@ PROTOTYPES = {
                                            _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     'pk_rescore_topk_rows_perm_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
                                            _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    'pk_rescore_topk_rows_settle_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
+                                           _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    'pk_rescore_bind_user_norm': (C.c_int, [_vp, _vp, _i64, _vp]),
     'pk_zero_i32': (C.c_int, [_vp, _vp, _i32]),
     'pk_scatter_rows_i64': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     'pk_map_ids_i64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),

@@ -12,6 +12,8 @@
 #include "pk_common.h"
 #include <math.h>
 #include <stdlib.h>
+#include <mutex>
+#include <unordered_map>
 
 #define PK_IDX_NONE 0x7fffffff
 
@@ -174,6 +176,17 @@ __device__ __forceinline__ double pk_dot_f32row(const float *__restrict__ vr, co
     return s;
 }
 
+// The sweep's split-bf16 product (score.hip): |s32 - e.v| <= pk_sweep_err_coeff(K) |e||v| — operands split into two bf16
+// each, the lo.lo term dropped, fp32 conversion of the inputs, accumulation roundings.  ONE definition: the certification
+// against the sweep's threshold and the settle tier (below) both stand on it.
+__device__ __forceinline__ double pk_sweep_err_coeff(int K) {
+    return 3.0 * 1.52587890625e-05 + (double)(4 * K + 10) * 1.1920928955078125e-07;
+}
+
+// flags[u] of a user the settle tier finished (rescore_topk_kernel): above the mask 7 of the lists of users to re-do, so
+// nobody re-does them — the bit only lets a caller COUNT them afterwards (no counter in the kernel)
+#define PK_FLAG_SETTLED 8
+
 // LPC adjacent lanes own one candidate: they walk the candidate's item row in interleaved 16-byte pieces
 // (the candidates of a user are popular items, their rows sit in L2) against the user's E row with serial
 // fp64 FMA chains and add their LPC partial sums at the end (one or two lane exchanges); a segment of
@@ -195,7 +208,7 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
     const float *__restrict__ cand_score, const int32_t *__restrict__ cand_idx, int topk, double vmax,
     int64_t *__restrict__ out_idx, double *__restrict__ out_score, int32_t *__restrict__ flags,
     int32_t *__restrict__ flagged_list, int32_t *__restrict__ flagged_count, int32_t flagged_offset,
-    const float *__restrict__ item_norm, const int64_t *__restrict__ out_perm) {
+    const float *__restrict__ item_norm, const int64_t *__restrict__ out_perm, const float *__restrict__ user_norm) {
     constexpr int UPW = 64 / (SEG * LPC);
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -225,13 +238,62 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
         else if (li == -2) unbounded = true;
     }
 
+    const int64_t n_seen = seen_ptr ? (seen_ptr[urow + 1] - seen_ptr[urow]) : 0;
+    // first pass over an approximate E: the fp32 image of the item rows will do (half the lines per gathered
+    // row), its rounding joins delta below; exact E rows (second pass, or no approximation at all): fp64 rows
+    const bool use32 = (V32 != nullptr) && (e_err != nullptr) && !e_exact;
+
+    // ---- settle tier: users whose order the sweep's own scores already decide --------------------------------------
+    // Only the ORDER leaves an ids-only pass, and the sweep has scored these candidates with a product whose error is
+    // bounded: with N_u >= ||E'_u|| (user_norm: the users' side of the sweep's pruning bound) and n_i >= ||V_i||, every
+    // sweep score is within d_i = (B N_u + a_u) n_i of the exact score of the same item, B = pk_sweep_err_coeff(K),
+    // a_u = 2^-24 e_err[u] (what the approximate E hides).  Sorted by sweep score, the list is in its exact order — and
+    // its head is the exact top-k — once neighbours down to the (k+1)-th, the k-th against every later entry, and the k-th
+    // against the bound on the items the sweep left out (tau_cert, any norm up to vmax) are further apart than the two
+    // errors involved.  Such a user is SETTLED: no item row gathered, no fp64 chain, no read of its row of E.  Ties and
+    // near-ties never settle (gap <= bound) and take the path below unchanged, as do unbounded and few-unseen users.
+    const bool tier = use32 && user_norm != nullptr && rows == nullptr;     // the same for the whole launch
+    bool settled = false;
+    double ts = -INFINITY;
+    int ti = PK_IDX_NONE;
+    if (tier) {
+        if (idx >= 0) {
+            ts = (double)cand_score[((int64_t)(t / KC) * n_pad + user) * KC + (t % KC)];
+            ti = idx;
+        }
+        // (the sweep's lists are ordered by key-only flush sorts: out of order by 2^-16 relative, and S of them per user)
+        pk_bitonic_seg<SEG, LPC>(ts, ti, t);
+        const double c = pk_sweep_err_coeff(K) * (double)user_norm[user] +
+                         e_err[urow * e_err_ld] * 5.9604644775390625e-08 * (1.0 + 1e-6);
+        const double d_max = c * vmax;
+        double d_me = d_max;
+        if (item_norm && ti != PK_IDX_NONE) d_me = c * fmin(vmax, (double)item_norm[ti] * (1.0 + 1e-6));
+        const int nxt_lane = lane + LPC, k_lane = (ul * SEG + topk - 1) * LPC;
+        // (every lane takes part in the exchanges; the last slot of a segment then drops what it fetched from its neighbour)
+        const double s_nb = __shfl(ts, nxt_lane & 63, 64), d_nb = __shfl(d_me, nxt_lane & 63, 64);
+        const double s_next = (t + 1 < SEG) ? s_nb : -INFINITY;
+        const double d_next = (t + 1 < SEG) ? d_nb : d_max;
+        const double s_kk = __shfl(ts, k_lane, 64), d_kk = __shfl(d_me, k_lane, 64);
+        // (an empty slot holds -inf: below everything at any bound; a list shorter than topk compares -inf with -inf: NaN, open)
+        bool open = (t < topk) ? !(ts - s_next > d_me + d_next) : !(s_kk - ts > d_kk + d_me);
+        if (tau32 > -INFINITY) open = open || !(s_kk - (tau32 + fabs(tau32) * 3.0517578125e-05) > d_kk + d_max);
+        open = open || unbounded || (n_items - n_seen < topk) || !live;
+        const unsigned long long ob = __ballot(open);
+        const unsigned long long seg_mask = (SEG * LPC == 64) ? ~0ull : (((1ull << (SEG * LPC)) - 1ull) << (ul * SEG * LPC));
+        settled = (ob & seg_mask) == 0ull;
+    }
+    // a wave whose users are all settled (or beyond the end) goes round the scoring, the sort and the certification
+    const bool score_any = !tier || __ballot(live && !settled) != 0ull;
+    const int Ks = settled ? 0 : K;      // in a mixed wave the lanes of a settled user walk no row
+
+    double my_s = -INFINITY;
+    int my_i = PK_IDX_NONE;
+    int flag = 0;
+  if (score_any) {
     const double *vr = V + (int64_t)(idx >= 0 ? idx : 0) * ldv;
     const double *er = E + urow * lde;
     const bool vvec2 = (ldv & 1) == 0 && (((uintptr_t)V) & 15) == 0;
     const bool evec2 = (lde & 1) == 0 && (((uintptr_t)E) & 15) == 0;
-    // first pass over an approximate E: the fp32 image of the item rows will do (half the lines per gathered
-    // row), its rounding joins delta below; exact E rows (second pass, or no approximation at all): fp64 rows
-    const bool use32 = (V32 != nullptr) && (e_err != nullptr) && !e_exact;
     double e2, s;
     if constexpr (SCORE4) {
         static_assert(SEG * LPC == 64, "SCORE4: one user per wave");
@@ -243,25 +305,23 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
             const int c = 16 * j + (lane >> 2);                    // the candidate this lane quad scores in pass j
             const int cidx = __shfl(idx, c * LPC, 64);
             const int64_t row = cidx >= 0 ? cidx : 0;
-            const double sj = use32 ? pk_dot_f32row<4>(V32 + row * ldv32, er, K, q4, v32vec, &e2)
+            const double sj = use32 ? pk_dot_f32row<4>(V32 + row * ldv32, er, Ks, q4, v32vec, &e2)    // (one user per wave)
                                     : pk_dot_chains<4>(V + row * ldv, er, K, q4, vvec2, evec2, &e2);
             const double got = __shfl(sj, 4 * (t & 15), 64);       // candidate t was scored in pass t / 16
             if ((t >> 4) == j) s = got;
         }
     } else if (use32) {
         const bool v32vec = evec2 && (ldv32 & 3) == 0 && (((uintptr_t)V32) & 15) == 0;
-        s = pk_dot_f32row<LPC>(V32 + (int64_t)(idx >= 0 ? idx : 0) * ldv32, er, K, q, v32vec, &e2);
+        s = pk_dot_f32row<LPC>(V32 + (int64_t)(idx >= 0 ? idx : 0) * ldv32, er, Ks, q, v32vec, &e2);
     } else {
         s = pk_dot_chains<LPC>(vr, er, K, q, vvec2, evec2, &e2);
     }
     const double enorm = sqrt(e2);
-    double my_s = (idx >= 0) ? s : -INFINITY;
-    int my_i = (idx >= 0) ? idx : PK_IDX_NONE;
+    my_s = (idx >= 0) ? s : -INFINITY;
+    my_i = (idx >= 0) ? idx : PK_IDX_NONE;
     pk_bitonic_seg<SEG, LPC>(my_s, my_i, t);
 
-    // certification
-    int flag = 0;
-    const int64_t n_seen = seen_ptr ? (seen_ptr[urow + 1] - seen_ptr[urow]) : 0;
+    // certification (a settled user whose wave got here goes through it on empty sums: the outcome is replaced below)
     const double s_k = __shfl(my_s, (ul * SEG + topk - 1) * LPC, 64);
     // E given only approximately (fold-in against the fp32 image of V, scoring.py): ||E' - E|| <= 2^-24 e_err[u],
     // so every score here is within delta of the exact one and the ORDER is the exact order wherever
@@ -282,8 +342,9 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
         double d_me = delta;
         if (item_norm && my_i != PK_IDX_NONE && my_i >= 0) d_me = cu * fmin(vmax, (double)item_norm[my_i] * (1.0 + 1e-6));
         const int nxt_lane = lane + LPC;
-        const double s_next = (t + 1 < SEG) ? __shfl(my_s, nxt_lane & 63, 64) : -INFINITY;
-        const double d_next = (t + 1 < SEG) ? __shfl(d_me, nxt_lane & 63, 64) : delta;
+        const double s_nb = __shfl(my_s, nxt_lane & 63, 64), d_nb = __shfl(d_me, nxt_lane & 63, 64);   // (all lanes exchange)
+        const double s_next = (t + 1 < SEG) ? s_nb : -INFINITY;
+        const double d_next = (t + 1 < SEG) ? d_nb : delta;
         const bool close = (t < topk) && !(my_s - s_next > d_me + d_next);
         const unsigned long long cb = __ballot(close);
         const unsigned long long seg_mask = (SEG * LPC == 64) ? ~0ull : (((1ull << (SEG * LPC)) - 1ull) << (ul * SEG * LPC));
@@ -297,7 +358,7 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
     } else if (tau32 > -INFINITY) {
         // the sweep's split-bf16 product (score.hip): |s32 - e.v| <= (3 * 2^-16 + (4 K + 10) * 2^-23) |e||v| — operands
         // split into two bf16 each, the lo.lo term dropped, fp32 conversion of the inputs, accumulation roundings
-        const double bound = (3.0 * 1.52587890625e-05 + (double)(4 * K + 10) * 1.1920928955078125e-07) * enorm * vmax;
+        const double bound = pk_sweep_err_coeff(K) * enorm * vmax;
         // the candidate sweep orders scores that agree to 2^-16 relative arbitrarily (key-only flush sorts,
         // score.hip): a non-candidate may exceed the KC-th candidate by that much
         const double tau_cert = tau32 + fabs(tau32) * 3.0517578125e-05;
@@ -306,25 +367,64 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
         if (bound > 0.0 && !(s_k - tau_cert > bound + slack))
             flag |= (!e_exact && delta > 0.0 && s_k - tau_cert > bound + delta) ? 4 : 1;
     }
+  }
+    if (settled) {      // the sweep's order is the exact one: flag bits 1, 2, 4 clear, the user is on no list
+        my_s = ts;
+        my_i = ti;
+        flag = PK_FLAG_SETTLED;
+    }
     if (live && q == 0 && t < topk) {
         // out_perm: the list goes straight to the caller's row of this user (scoring.recommend sweeps the users in activity
         // order); scores and flags stay in sweep order
         const int64_t irow = out_perm ? out_perm[user] : user;
         out_idx[irow * topk + t] = (my_i == PK_IDX_NONE) ? -1 : (int64_t)my_i;
-        if (out_score) out_score[user * topk + t] = my_s;
+        if (out_score && !settled) out_score[user * topk + t] = my_s;     // (a settled user has no re-computed scores)
     }
     if (live && q == 0 && t == 0) {
         flags[user] = flag;
         // the list of the users to re-do, built where the flag is: what a separate compaction pass over the flags (two
         // more launches per list) did.  The order of the list is arbitrary either way — every listed user is re-done on
         // its own rows — so the atomic counter costs no determinism of the results.
-        if (flag && flagged_list) flagged_list[atomicAdd(flagged_count, 1)] = flagged_offset + (int32_t)user;
+        if ((flag & 7) && flagged_list) flagged_list[atomicAdd(flagged_count, 1)] = flagged_offset + (int32_t)user;
     }
 }
 
+// user_norm_dev (float [n_users], may be NULL = tier off): upper bounds of ||E_u|| — the users' side of the sweep's pruning
+// bound (pk_pack_frag_bound_f32's, or what pk_score_*_rows_bound_f32 stored).  On the first pass over an approximate E
+// (V32_dev, e_err_dev, !e_exact, no row list) the users whose order the sweep's scores already decide are SETTLED: ids
+// written, flags[u] = 8, no out_score row, on no list (see the kernel).  pk_set_option("rescore_settle", 0) switches it off.
 // out_perm_dev (int64 [n_users], may be NULL): the out_idx row of user u is written to row out_perm[u] (out_score and flags
 // rows stay where they are) — the pass then needs no scatter of its lists at the end
-extern "C" int pk_rescore_topk_rows_perm_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
+//
+// The same pointer for a caller that keeps to the older entries of the family (a host layer whose recorded call sequence is
+// fixed): pk_rescore_bind_user_norm(stream, p, n_users, flags_dev) leaves p with the stream FOR ONE CALL — the next call of
+// an older entry on that stream takes it as its user_norm_dev if it is the call named (same n_users, same flags_dev) and
+// drops it otherwise; either way the binding is gone afterwards, also when that call fails its argument checks.  Host-side
+// bookkeeping only (a mutex and a map by stream handle): nothing is enqueued, captures and replays see two ordinary calls.
+// What is left of the hazard of state between calls: a binding whose call never comes stays until the next older-entry
+// call on the stream, which drops it unless it writes the same flags buffer for the same number of users — bind
+// immediately in front of the call, and pass the pointer to pk_rescore_topk_rows_settle_f64 wherever the entry is free.
+namespace {
+struct NormBinding { const float *ptr; int64_t n_users; const int32_t *flags; };
+std::mutex g_norm_mu;
+std::unordered_map<void *, NormBinding> g_norm_bound;
+}
+extern "C" int pk_rescore_bind_user_norm(void *stream, const float *user_norm_dev, int64_t n_users, const int32_t *flags_dev) {
+    std::lock_guard<std::mutex> lock(g_norm_mu);
+    if (user_norm_dev) g_norm_bound[stream] = NormBinding{user_norm_dev, n_users, flags_dev};
+    else g_norm_bound.erase(stream);
+    return PK_OK;
+}
+static const float *pk_take_user_norm(void *stream, int64_t n_users, const int32_t *flags_dev) {
+    std::lock_guard<std::mutex> lock(g_norm_mu);
+    const auto it = g_norm_bound.find(stream);
+    if (it == g_norm_bound.end()) return nullptr;
+    const NormBinding nb = it->second;
+    g_norm_bound.erase(it);
+    return (nb.n_users == n_users && nb.flags == flags_dev) ? nb.ptr : nullptr;
+}
+
+extern "C" int pk_rescore_topk_rows_settle_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
                                             const int32_t *n_rows_dev, int64_t n_users,
                                             int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
                                             const float *V32_dev, int64_t ldv32,
@@ -334,7 +434,9 @@ extern "C" int pk_rescore_topk_rows_perm_f64(void *stream, int64_t n_rows, const
                                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
                                             double v_row_norm_max, int64_t *out_idx_dev, double *out_score_dev,
                                             int32_t *flags_dev, int32_t *flagged_list_dev, int32_t *flagged_count_dev,
-                                            int32_t flagged_offset, const float *item_norm_dev, const int64_t *out_perm_dev) {
+                                            int32_t flagged_offset, const float *item_norm_dev, const int64_t *out_perm_dev,
+                                            const float *user_norm_dev) {
+    if (user_norm_dev && !pk_option("rescore_settle", 1)) user_norm_dev = nullptr;
     PK_REQUIRE((flagged_list_dev == nullptr) == (flagged_count_dev == nullptr), "pk_rescore_topk_f64: flagged list without its counter");
     PK_REQUIRE(n_users >= 1 && K >= 1 && K <= 256 && ldv >= K && lde >= K, "pk_rescore_topk_f64: bad sizes");
     PK_REQUIRE(n_rows >= 0 && n_rows <= n_users, "pk_rescore_topk_f64: bad row count");
@@ -351,7 +453,7 @@ extern "C" int pk_rescore_topk_rows_perm_f64(void *stream, int64_t n_rows, const
                        dim3(256), 0, pk_stream(stream), n_rows, rows_dev, n_rows_dev, n_users, n_items, K, V_dev, ldv, V32_dev, ldv32, E_dev, lde, \
                        e_err_dev, e_err_ld, e_exact, seen_ptr_dev, KC, splits, cand_score_dev, cand_idx_dev, topk, v_row_norm_max,   \
                        out_idx_dev, out_score_dev, flags_dev, flagged_list_dev, flagged_count_dev, flagged_offset, item_norm_dev, \
-                       out_perm_dev)
+                       out_perm_dev, user_norm_dev)
     if (seg == 16) {
         if (lpc_req == 1) PK_RESCORE(16, 1);
         else if (lpc_req == 4) PK_RESCORE(16, 4);
@@ -369,6 +471,23 @@ extern "C" int pk_rescore_topk_rows_perm_f64(void *stream, int64_t n_rows, const
 #undef PK_RESCORE_X
     PK_CHECK_LAUNCH("rescore_topk_kernel");
     return PK_OK;
+}
+
+extern "C" int pk_rescore_topk_rows_perm_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
+                                            const int32_t *n_rows_dev, int64_t n_users,
+                                            int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
+                                            const float *V32_dev, int64_t ldv32,
+                                            const double *E_dev, int64_t lde, const double *e_err_dev,
+                                            int64_t e_err_ld, int32_t e_exact,
+                                            const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
+                                            const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
+                                            double v_row_norm_max, int64_t *out_idx_dev, double *out_score_dev,
+                                            int32_t *flags_dev, int32_t *flagged_list_dev, int32_t *flagged_count_dev,
+                                            int32_t flagged_offset, const float *item_norm_dev, const int64_t *out_perm_dev) {
+    return pk_rescore_topk_rows_settle_f64(stream, n_rows, rows_dev, n_rows_dev, n_users, n_items, K, V_dev, ldv, V32_dev, ldv32, E_dev,
+                                           lde, e_err_dev, e_err_ld, e_exact, seen_ptr_dev, KC, splits, cand_score_dev, cand_idx_dev, topk,
+                                           v_row_norm_max, out_idx_dev, out_score_dev, flags_dev, flagged_list_dev, flagged_count_dev,
+                                           flagged_offset, item_norm_dev, out_perm_dev, pk_take_user_norm(stream, n_users, flags_dev));
 }
 
 extern "C" int pk_rescore_topk_rows_norms_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,

@@ -188,6 +188,8 @@ struct UserRows {
     const double *extra;
     int64_t extra_ld;
     double extra_scale;
+    float *bound_out;   // float [n_users] or NULL: the sweep leaves `bound` there, four bytes per user — an upper bound of ||E_u||
+                        // for the settle tier of the re-scoring kernel (rescore.hip), which must not read the row to get one
 };
 
 // DENSE: the instance that reads them (the other one is the kernel as it was: in the throughput-bound regimes — full
@@ -304,6 +306,8 @@ __global__ __launch_bounds__(256) void score_candidates_kernel(
             double b = sqrt(ss) * (1.0 + 1e-6);
             if (rows.extra) b += rows.extra_scale * rows.extra[user * rows.extra_ld];
             en_rows = (float)(b * (1.0 + 1e-7));         // the conversion rounds to nearest: keep it an upper bound
+            // (every launch of a pass computes the same value: the first one of split 0 stores it, one lane per user)
+            if (rows.bound_out && chunk_begin == 0 && hi == 0 && (!STRIDED || blockIdx.y == 0)) rows.bound_out[user] = en_rows;
         }
     } else {
 #pragma unroll
@@ -1458,7 +1462,7 @@ static int pk_sweep_launches(hipStream_t st, int64_t n_users, int64_t n_items, i
                              const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits, int32_t total_slots,
                              float *cand_score_dev, int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
                              const float *user_bound_dev, const float *tile_bound_dev, SeenDense dense, SweepPhase ph,
-                             UserRows rows = UserRows{nullptr, 0, 0, nullptr, 0, 0.0}) {
+                             UserRows rows = UserRows{nullptr, 0, 0, nullptr, 0, 0.0, nullptr}) {
     const int kq = pk_pack_kq(K);
     const int nstep = pk_nstep(K);
     const int64_t groups = pk_ceil_div(n_users, 32);
@@ -1539,7 +1543,7 @@ static int pk_score_candidates_impl(const char *who, void *stream, int64_t n_use
     return pk_sweep_launches(pk_stream(stream), n_users, n_items, (int)pk_ceil_div(n_items, 32), K, Vp_dev, Ep_dev,
                              seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, splits, splits, cand_score_dev, cand_idx_dev,
                              state_dev, tiles_per_chunk, user_bound_dev, tile_bound_dev, dense, SweepPhase{0, 0, nullptr, 0},
-                             rows ? *rows : UserRows{nullptr, 0, 0, nullptr, 0, 0.0});
+                             rows ? *rows : UserRows{nullptr, 0, 0, nullptr, 0, 0.0, nullptr});
 }
 
 extern "C" int pk_score_candidates_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K,
@@ -1560,6 +1564,21 @@ extern "C" int pk_score_candidates_f32(void *stream, int64_t n_users, int64_t n_
 // 1: this library's sweeps take the users' side from the rows of E (pk_score_*_rows_f32); a probe build of the experiment tree says 0
 extern "C" int pk_sweep_takes_rows(void) { return 1; }
 
+// user_bound_out_dev (float [n_users], may be NULL): the users' side of the pruning bound as the sweep computed it, for
+// pk_rescore_topk_rows_settle_f64
+extern "C" int pk_score_candidates_rows_bound_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                                                  const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
+                                                  double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
+                                                  const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits, float *cand_score_dev,
+                                                  int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
+                                                  const float *tile_bound_dev, const uint32_t *seen_dense_dev,
+                                                  const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev) {
+    const UserRows rows{E_dev, lde, K, extra_dev, extra_ld, extra_scale, user_bound_out_dev};
+    return pk_score_candidates_impl("pk_score_candidates_rows_f32", stream, n_users, n_items, K, Vp_dev, nullptr, &rows,
+                                    seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, splits, cand_score_dev, cand_idx_dev,
+                                    state_dev, tiles_per_chunk, nullptr, tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles);
+}
+
 extern "C" int pk_score_candidates_rows_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
                                             const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
                                             double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
@@ -1567,10 +1586,10 @@ extern "C" int pk_score_candidates_rows_f32(void *stream, int64_t n_users, int64
                                             int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
                                             const float *tile_bound_dev, const uint32_t *seen_dense_dev,
                                             const int32_t *seen_skip_dev, int32_t dense_tiles) {
-    const UserRows rows{E_dev, lde, K, extra_dev, extra_ld, extra_scale};
-    return pk_score_candidates_impl("pk_score_candidates_rows_f32", stream, n_users, n_items, K, Vp_dev, nullptr, &rows,
-                                    seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, splits, cand_score_dev, cand_idx_dev,
-                                    state_dev, tiles_per_chunk, nullptr, tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles);
+    return pk_score_candidates_rows_bound_f32(stream, n_users, n_items, K, Vp_dev, E_dev, lde, extra_dev, extra_ld, extra_scale,
+                                              seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, splits, cand_score_dev, cand_idx_dev,
+                                              state_dev, tiles_per_chunk, tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles,
+                                              nullptr);
 }
 
 // ---- two-phase sweep -------------------------------------------------------------------------------------------------
@@ -1715,7 +1734,7 @@ static int pk_score_two_phase_impl(const char *who, void *stream, int64_t n_user
                                  seen_tiles_dev, seen_ntiles_dev, state_dev, user_bound_dev, tile_bound_dev,
                                  seen_dense_dev, seen_skip_dev, dense_tiles, rows_in);
     if (rc != PK_OK) return rc;
-    const UserRows rows = rows_in ? *rows_in : UserRows{nullptr, 0, 0, nullptr, 0, 0.0};
+    const UserRows rows = rows_in ? *rows_in : UserRows{nullptr, 0, 0, nullptr, 0, 0.0, nullptr};
     const int n_tiles = (int)pk_ceil_div(n_items, 32);
     PK_REQUIRE((user_bound_dev || rows_in) && tile_bound_dev, "%s: needs the pruning bounds", who);
     PK_REQUIRE(KC >= 1 && KC <= 64 && splits >= 1 && (splits + 1) * KC <= 256 && head_tiles >= 1 && head_tiles < n_tiles,
@@ -1766,6 +1785,21 @@ extern "C" int pk_score_two_phase_f32(void *stream, int64_t n_users, int64_t n_i
 }
 
 // the two-phase sweep with the users' side from the rows of E (see pk_score_candidates_rows_f32)
+extern "C" int pk_score_two_phase_rows_bound_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                                                 const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
+                                                 double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
+                                                 const int32_t *seen_ntiles_dev, int32_t KC, int32_t head_tiles, int32_t splits,
+                                                 float *work_score_dev, int32_t *work_idx_dev, float *cand_score_dev,
+                                                 int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
+                                                 const float *tile_bound_dev, const uint32_t *seen_dense_dev,
+                                                 const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev) {
+    const UserRows rows{E_dev, lde, K, extra_dev, extra_ld, extra_scale, user_bound_out_dev};
+    return pk_score_two_phase_impl("pk_score_two_phase_rows_f32", stream, n_users, n_items, K, Vp_dev, nullptr, &rows, seen_ptr_dev,
+                                   seen_tiles_dev, seen_ntiles_dev, KC, head_tiles, splits, work_score_dev, work_idx_dev,
+                                   cand_score_dev, cand_idx_dev, state_dev, tiles_per_chunk, nullptr, tile_bound_dev,
+                                   seen_dense_dev, seen_skip_dev, dense_tiles);
+}
+
 extern "C" int pk_score_two_phase_rows_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
                                            const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
                                            double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
@@ -1774,11 +1808,10 @@ extern "C" int pk_score_two_phase_rows_f32(void *stream, int64_t n_users, int64_
                                            int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
                                            const float *tile_bound_dev, const uint32_t *seen_dense_dev,
                                            const int32_t *seen_skip_dev, int32_t dense_tiles) {
-    const UserRows rows{E_dev, lde, K, extra_dev, extra_ld, extra_scale};
-    return pk_score_two_phase_impl("pk_score_two_phase_rows_f32", stream, n_users, n_items, K, Vp_dev, nullptr, &rows, seen_ptr_dev,
-                                   seen_tiles_dev, seen_ntiles_dev, KC, head_tiles, splits, work_score_dev, work_idx_dev,
-                                   cand_score_dev, cand_idx_dev, state_dev, tiles_per_chunk, nullptr, tile_bound_dev,
-                                   seen_dense_dev, seen_skip_dev, dense_tiles);
+    return pk_score_two_phase_rows_bound_f32(stream, n_users, n_items, K, Vp_dev, E_dev, lde, extra_dev, extra_ld, extra_scale,
+                                             seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, head_tiles, splits, work_score_dev,
+                                             work_idx_dev, cand_score_dev, cand_idx_dev, state_dev, tiles_per_chunk, tile_bound_dev,
+                                             seen_dense_dev, seen_skip_dev, dense_tiles, nullptr);
 }
 
 // eager load of this translation unit's code object (pk_warm_up, api.cpp): the runtime loads a code object at the first

@@ -1286,10 +1286,11 @@ class HipOps:
         return _ptr(E), E.stride(0), _ptr(extra), int(e_ld), float(scale if extra is not None else 0.0)
 
     def score_candidates(self, Vp, Ep, n_users, n_items, K, seen_ptr, seen_idx, KC, splits=1, tiles_per_chunk=0,
-                         user_bound=None, tile_bound=None, seen_tiles=None, seen_dense=None, E_rows=None):
+                         user_bound=None, tile_bound=None, seen_tiles=None, seen_dense=None, E_rows=None, bound_out=None):
         """E_rows = (E fp64 [n_users x >= K], extra column or None, extra_scale): the users' fragments and pruning bounds are
         built inside the sweep (pk_score_candidates_rows_f32; Ep and user_bound are not used, tile_bound alone switches the
-        pruning on)."""
+        pruning on).  bound_out (float32 [n_users], E_rows only): the sweep stores the users' bounds there
+        (pk_score_candidates_rows_bound_f32) — what `rescore_topk` takes as `user_norm`."""
         n_pad = -(-n_users // 32) * 32
         need = self.lib.pk_score_state_bytes(n_users, splits)
         if self._score_states is None:
@@ -1308,13 +1309,16 @@ class HipOps:
                 dense, skip, dtiles = seen_dense
         if E_rows is not None:
             ep, lde, xp, xld, xs = self._rows_args(E_rows, K)
+            args = (self.stream(), n_users, n_items, K, _ptr(Vp), ep, lde, xp, xld, xs, _ptr(seen_ptr), _ptr(tiles), _ptr(ntiles),
+                    KC, splits, _ptr(cs), _ptr(ci), _ptr(self._score_state), tiles_per_chunk or self.score_tiles_per_chunk,
+                    _ptr(tile_bound), _ptr(dense), _ptr(skip), int(dtiles))
             with self._timed('score_candidates', (n_users, n_items, K)):
-                _lib.check(self.lib.pk_score_candidates_rows_f32(self.stream(), n_users, n_items, K, _ptr(Vp), ep, lde, xp, xld, xs,
-                                                                 _ptr(seen_ptr), _ptr(tiles), _ptr(ntiles), KC, splits,
-                                                                 _ptr(cs), _ptr(ci), _ptr(self._score_state),
-                                                                 tiles_per_chunk or self.score_tiles_per_chunk,
-                                                                 _ptr(tile_bound), _ptr(dense), _ptr(skip), int(dtiles)),
-                           'pk_score_candidates_rows_f32')
+                if bound_out is None:
+                    _lib.check(self.lib.pk_score_candidates_rows_f32(*args), 'pk_score_candidates_rows_f32')
+                else:
+                    assert bound_out.dtype == torch.float32 and bound_out.is_contiguous() and bound_out.numel() == n_users
+                    _lib.check(self.lib.pk_score_candidates_rows_bound_f32(*args, _ptr(bound_out)),
+                               'pk_score_candidates_rows_bound_f32')
             return cs, ci
         with self._timed('score_candidates', (n_users, n_items, K)):
             _lib.check(self.lib.pk_score_candidates_f32(self.stream(), n_users, n_items, K, _ptr(Vp), _ptr(Ep),
@@ -1334,9 +1338,10 @@ class HipOps:
         return int(h.value), int(s.value)
 
     def score_two_phase(self, Vp, Ep, n_users, n_items, K, seen_ptr, KC, head_tiles, splits, user_bound, tile_bound,
-                        seen_tiles=None, seen_dense=None, tiles_per_chunk=0, E_rows=None):
+                        seen_tiles=None, seen_dense=None, tiles_per_chunk=0, E_rows=None, bound_out=None):
         """The pruned candidate sweep in two phases (pk_score_two_phase_f32): head sweep, `splits` sweeps of the tail from
-        the head's thresholds, merge.  Returns the merged (scores, ids) [n_pad x KC] — a single list per user."""
+        the head's thresholds, merge.  Returns the merged (scores, ids) [n_pad x KC] — a single list per user.
+        bound_out: as in `score_candidates`."""
         n_pad = -(-n_users // 32) * 32
         total = splits + 1
         need = self.lib.pk_score_state_bytes(n_users, total)
@@ -1358,14 +1363,16 @@ class HipOps:
                 dense, skip, dtiles = seen_dense
         if E_rows is not None:
             ep, lde, xp, xld, xs = self._rows_args(E_rows, K)
+            args = (self.stream(), n_users, n_items, K, _ptr(Vp), ep, lde, xp, xld, xs, _ptr(seen_ptr), _ptr(tiles), _ptr(ntiles),
+                    KC, int(head_tiles), int(splits), _ptr(ws), _ptr(wi), _ptr(cs), _ptr(ci), _ptr(self._score_state),
+                    tiles_per_chunk or self.score_tiles_per_chunk, _ptr(tile_bound), _ptr(dense), _ptr(skip), int(dtiles))
             with self._timed('score_candidates', (n_users, n_items, K)):
-                _lib.check(self.lib.pk_score_two_phase_rows_f32(self.stream(), n_users, n_items, K, _ptr(Vp), ep, lde, xp, xld, xs,
-                                                                _ptr(seen_ptr), _ptr(tiles), _ptr(ntiles), KC, int(head_tiles),
-                                                                int(splits), _ptr(ws), _ptr(wi), _ptr(cs), _ptr(ci),
-                                                                _ptr(self._score_state),
-                                                                tiles_per_chunk or self.score_tiles_per_chunk,
-                                                                _ptr(tile_bound), _ptr(dense), _ptr(skip), int(dtiles)),
-                           'pk_score_two_phase_rows_f32')
+                if bound_out is None:
+                    _lib.check(self.lib.pk_score_two_phase_rows_f32(*args), 'pk_score_two_phase_rows_f32')
+                else:
+                    assert bound_out.dtype == torch.float32 and bound_out.is_contiguous() and bound_out.numel() == n_users
+                    _lib.check(self.lib.pk_score_two_phase_rows_bound_f32(*args, _ptr(bound_out)),
+                               'pk_score_two_phase_rows_bound_f32')
             return cs, ci
         with self._timed('score_candidates', (n_users, n_items, K)):
             _lib.check(self.lib.pk_score_two_phase_f32(self.stream(), n_users, n_items, K, _ptr(Vp), _ptr(Ep), _ptr(seen_ptr),
@@ -1385,7 +1392,7 @@ class HipOps:
 
     def rescore_topk(self, V, E, n_items, seen_ptr, KC, cs, ci, topk, vmax, want_scores=True, splits=1, out=None,
                      rows=None, n_rows_dev=None, e_err=None, e_exact=False, v32=None, flagged=None, item_norm=None,
-                     out_perm=None):
+                     out_perm=None, user_norm=None):
         """Exact fp64 re-scoring + certification.  rows (int32 tensor): only these users are re-done (outputs
         are still indexed by user: pass the full-size `out`); e_err: per-user error weight of an approximate E
         (flags bit 4 = not certified at that accuracy); v32: fp32 image of V [n_items x >= K], gathered instead
@@ -1393,7 +1400,10 @@ class HipOps:
         the rows' norms (the order of two entries is then certified against their own norms).  flagged = (list int32, count int32[1],
         offset): every user that ends up flagged is appended to that device-side list as offset + user while the
         kernel runs (the counter is the caller's to zero: `zero_counters`).  out_perm (int64 [n_users]): the id list of user
-        u goes to row out_perm[u] of out_idx (scores and flags stay at row u)."""
+        u goes to row out_perm[u] of out_idx (scores and flags stay at row u).  user_norm (float32 [n_users]): upper bounds
+        of the norms of the rows of E — the users' side of the sweep's pruning bound; on a first pass over an approximate E
+        (v32 and e_err given, no rows, not e_exact) the users whose order the sweep's own scores decide are then settled
+        without re-scoring (pk_rescore_topk_rows_settle_f64: flags = 8, no score row; `settled_users` counts them)."""
         assert V.stride(1) == 1 and E.stride(1) == 1
         assert v32 is None or (v32.dtype == torch.float32 and v32.stride(1) == 1 and v32.shape[1] >= E.shape[1])
         n_users, K = E.shape
@@ -1413,12 +1423,27 @@ class HipOps:
                     V.stride(0), _ptr(v32), 0 if v32 is None else v32.stride(0), _ptr(E), E.stride(0), _ptr(e_err), e_ld,
                     1 if e_exact else 0, _ptr(seen_ptr), KC, splits, _ptr(cs), _ptr(ci), topk, float(vmax),
                     _ptr(out_idx), _ptr(out_s), _ptr(flags), _ptr(fl), _ptr(fc), int(fo), _ptr(item_norm))
-            if out_perm is None:
+            assert out_perm is None or (out_perm.dtype == torch.int64 and out_perm.is_contiguous() and out_perm.numel() == n_users)
+            if user_norm is not None:
+                assert user_norm.dtype == torch.float32 and user_norm.is_contiguous() and user_norm.numel() == n_users
+            if user_norm is not None and out_perm is None:
+                _lib.check(self.lib.pk_rescore_topk_rows_settle_f64(*args, None, _ptr(user_norm)),
+                           'pk_rescore_topk_rows_settle_f64')
+            elif out_perm is None:
                 _lib.check(self.lib.pk_rescore_topk_rows_norms_f64(*args), 'pk_rescore_topk_rows_norms_f64')
             else:
-                assert out_perm.dtype == torch.int64 and out_perm.is_contiguous() and out_perm.numel() == n_users
+                # the producer-order pass keeps its recorded sequence of entries (two `_perm` re-scorings): the norm bounds
+                # travel with the stream to the call behind them (pk_rescore_bind_user_norm)
+                if user_norm is not None:
+                    _lib.check(self.lib.pk_rescore_bind_user_norm(self.stream(), _ptr(user_norm), n_users, _ptr(flags)),
+                               'pk_rescore_bind_user_norm')
                 _lib.check(self.lib.pk_rescore_topk_rows_perm_f64(*args, _ptr(out_perm)), 'pk_rescore_topk_rows_perm_f64')
         return out_idx, out_s, flags
+
+    @staticmethod
+    def settled_users(flags):
+        """users of a `rescore_topk(..., user_norm=)` call that its settle tier finished (flag bit 8): a host read"""
+        return int((flags & 8).ne(0).sum().item())
 
     def zero_counters(self, n):
         """int32 [n] device counters, zeroed by a kernel on the current stream (one launch for all the lists of a pass)"""

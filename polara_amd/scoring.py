@@ -249,6 +249,7 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
     flags = torch.empty(n_users, dtype=torch.int32, device=E.device)
 
     refolded = []                        # device counters of the users re-done with an exact fold-in
+    settled = []                         # flags of the batches whose first re-scoring ran the settle tier (statistics only)
     # The lists of users to re-do are built by the re-scoring kernel itself, where the flags are (ops.rescore_topk
     # `flagged`): counter 0 belongs to the pass's final list (users for the exact-row kernel, global ids, every batch
     # appends), counter 1 + b to batch b's re-fold list.  One launch zeroes them all; the flag compactions (two launches
@@ -285,11 +286,21 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
         rows_kw = {}
         # (pruned passes: they are ONE launch; a full sweep is cut into item chunks and every launch would rebuild the
         # fragments — S-1M unpruned: 39.1 -> 39.7 ms — so it keeps the packed copy)
+        # The users' side of that bound is also an upper bound of ||E'_u||: the first re-scoring settles, from the sweep's own
+        # scores, the users whose order they already decide (ops.rescore_topk `user_norm`) — the sweep stores it when it
+        # builds it itself
+        settle = approx_fold_in and fused_lists and hasattr(ops, 'settled_users')
+        un = None
         if SWEEP_FROM_ROWS and prune and hasattr(ops, 'sweep_takes_rows') and ops.sweep_takes_rows(Eb):
             Ep = ub = None
             rows_kw = {'E_rows': (Eb, w, 1.2e-7)}
+            if settle:
+                un = torch.empty(nb, dtype=torch.float32, device=E.device)
+                rows_kw['bound_out'] = un
         else:
             Ep, ub = ops.pack_frag_bound(Eb, extra=w, extra_scale=1.2e-7)
+            if settle:
+                un = ub
         if not prune:
             ub = None
         sp = seen_ptr[u0:u1 + 1] if filter_seen else None
@@ -318,7 +329,10 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
             first = to_final
         ops.rescore_topk(factors.V, Eb, n_items, sp, KC, cs, ci, topk, factors.vmax, want_scores=True,
                          splits=splits, out=outs, e_err=w, v32=factors.V32x if approx_fold_in else None, **perm_kw, **(
-                             {'flagged': first, 'item_norm': factors.vnorm if approx_fold_in else None} if fused_lists else {}))
+                             {'flagged': first, 'item_norm': factors.vnorm if approx_fold_in else None} if fused_lists else {}),
+                         **({'user_norm': un} if un is not None else {}))
+        if un is not None and stats is not None:
+            settled.append(outs[2])
         if approx_fold_in:
             # every flagged user — order not certified at the accuracy of the approximate fold-in (bit 4), or
             # bound for the exact-row kernel anyway (bits 1, 2), which must not see an approximate E — gets its
@@ -392,6 +406,7 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
     if stats is not None:
         stats['flagged_users'] = int(cnt.item())
         stats['refolded_users'] = int(sum(int(c.item()) for c in refolded))
+        stats['settled_users'] = int(sum(ops.settled_users(f) for f in settled))     # (nobody rewrites a settled user's flag)
         stats['approx_fold_in'] = bool(approx_fold_in)
         stats['candidate_capacity'] = KC
         stats['item_splits'] = splits
