@@ -134,10 +134,19 @@ class ItemColdStartRecommenderMixin:
         stats = {}
         recs_dev = scoring.recommend_dense(ops, image, E, self.topk, stats=stats if self.collect_recommend_stats else None)
         self.recommend_stats = stats
-        if hasattr(ops, 'ids_to_host'):
-            return ops.ids_to_host(recs_dev, order)          # catalogue positions -> training user ids on the device
-        recs = ops.to_host(recs_dev)
-        return np.where(recs >= 0, order[np.maximum(recs, 0)], -1).astype(np.int64)
+        return self._external_ids(recs_dev, order)          # catalogue positions -> training user ids
+
+    def slice_recommendations(self, cold_item_meta=None, start=0, stop=None):
+        """coldstart/models.py:133-146, 209-222: the dense fp64 scores of cold items [start, stop) against every training
+        user (in user id order).  Kept for consumers of score blocks; `get_recommendations` does not go through here."""
+        n_cold = self._cold_shape()[0]
+        stop = n_cold if stop is None else min(stop, n_cold)
+        image, order = self._user_factors_device()
+        E = self._cold_queries_device()[start:stop].contiguous()
+        scores = self.ops.to_host(self.ops.dense_scores(image.V, E))
+        out = np.empty_like(scores)
+        out[:, order] = scores
+        return out
 
 
 class ItemColdStartSVDModelMixin:
@@ -226,9 +235,7 @@ class ItemColdStartSVDModelMixin:
         self.update_item_features_transform()
 
     def build(self, *args, **kwargs):
-        if self.comm.world > 1:
-            raise NotImplementedError('%s: multi-process builds are not supported (comm.world = %d)'
-                                      % (self.method, self.comm.world))
+        self._require_single_process_build()
         kwargs.pop('return_factors', None)
         super().build(*args, return_factors=True, **kwargs)
         self.prepare_item_features_transformation()
@@ -239,7 +246,6 @@ class ItemColdStartSVDModelMixin:
     def _user_factors_device(self):
         """(FactorImage of U diag(sigma) by descending row norm, host int64 order: catalogue position -> training user).
         Belongs to ONE pair of arrays of `factors`: rebuilt after a rank truncation or when a consumer swaps `factors`."""
-        import torch
         U = self.factors.get(self.data.fields.userid, None)
         sigma = self.factors.get('singular_values', None)
         if U is None or sigma is None:
@@ -258,12 +264,7 @@ class ItemColdStartSVDModelMixin:
         else:
             Ud = ops.to_device(np.ascontiguousarray(U, dtype=np.float64))
         X = (Ud * ops.to_device(np.asarray(sigma, dtype=np.float64))[None, :]).contiguous()
-        if hasattr(ops, 'norm_order'):
-            order_dev, _, Xs = ops.norm_order(X)        # rows by descending norm, ties by id: sort and gather on the device
-            order = ops.to_host(order_dev).astype(np.int64)
-        else:
-            order = np.argsort(-np.linalg.norm(ops.to_host(X), axis=1), kind='stable').astype(np.int64)
-            Xs = X[torch.from_numpy(order)].contiguous()
+        order, Xs = self._rows_by_norm(X)
         del X
         image = scoring.FactorImage(ops, Xs)
         self._user_image = (U, sigma, image, order)
@@ -299,18 +300,6 @@ class ItemColdStartSVDModelMixin:
         if F.shape[1] != Wd.shape[0]:
             raise ValueError('cold item features over %d labels, the embeddings over %d' % (F.shape[1], Wd.shape[0]))
         return self.ops.coldstart_queries(F, Wd, Gd)
-
-    def slice_recommendations(self, cold_item_meta=None, start=0, stop=None):
-        """coldstart/models.py:209-222: the dense fp64 scores of cold items [start, stop) against every training user (in
-        user id order).  Kept for consumers of score blocks; `get_recommendations` does not go through here."""
-        n_cold = self._cold_shape()[0]
-        stop = n_cold if stop is None else min(stop, n_cold)
-        image, order = self._user_factors_device()
-        E = self._cold_queries_device()[start:stop].contiguous()
-        scores = self.ops.to_host(self.ops.dense_scores(image.V, E))
-        out = np.empty_like(scores)
-        out[:, order] = scores
-        return out
 
 
 class SVDModelItemColdStart(ItemColdStartEvaluationMixin, ItemColdStartRecommenderMixin, ItemColdStartSVDModelMixin, SVDModel):

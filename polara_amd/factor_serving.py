@@ -1,13 +1,35 @@
-"""Serving for models that carry explicit user factors (ProbabilisticMF, ImplicitALS): the rows of the user factors go into
-the scoring pass as ready-made queries (`scoring.recommend(queries=...)`), and `slice_recommendations` is the dense product of
-those rows with the item factors.  The model provides `factors` ({userid: host array, itemid: host array}), `_factors_dev`
-((host user factors, their device copy) or None), `_item_inv` and the item image of `_item_factors_device`."""
+"""Serving for models that carry explicit user factors (ProbabilisticMF, ImplicitALS, LCEModel): the rows of the user factors
+go into the scoring pass as ready-made queries (`scoring.recommend(queries=...)`), and `slice_recommendations` is the dense
+product of those rows with the item factors.  The model provides `_rank`, `factors` ({userid: host array, itemid: host
+array}), `_factors_dev` ((host user factors, their device copy, then what `_extra_factors_device` names) or None),
+`_item_inv` and the item image of `_item_factors_device`."""
 import numpy as np
 
 from . import scoring
 
 
 class FactorQueriesMixin:
+    @property
+    def rank(self):
+        return self._rank
+
+    @rank.setter
+    def rank(self, new_value):
+        # the factors of these models are not nested: no truncation, a rank change invalidates the model
+        if new_value != self._rank:
+            self._rank = new_value
+            self._is_ready = False
+            self._recommendations = None
+            self._factor_image = None
+
+    def _training_device_csr(self):
+        """what these models factorise: the training matrix in the data's own item order"""
+        return self._data_order_training_csr()
+
+    def _extra_factors_device(self):
+        """uploads of further `factors` that stay on the device with the user factors (the tail of `_factors_dev`)"""
+        return ()
+
     def _user_factors_block(self):
         """P [n_users x k] on the device: the block of the build, or an upload when `factors` was swapped"""
         P = self.factors.get(self.data.fields.userid, None)
@@ -15,7 +37,8 @@ class FactorQueriesMixin:
             raise ValueError('%s: no user factors (build the model first)' % self.method)
         kept = self._factors_dev
         if kept is None or kept[0] is not P:
-            kept = self._factors_dev = (P, self.ops.to_device(np.ascontiguousarray(P, dtype=np.float64)))
+            kept = self._factors_dev = (P, self.ops.to_device(np.ascontiguousarray(P, dtype=np.float64)),
+                                        *self._extra_factors_device())
         return kept[1]
 
     def _user_rows(self, users):
@@ -51,11 +74,7 @@ class FactorQueriesMixin:
         recs_dev = scoring.recommend(ops, self._item_factors_device(), T, self.topk, self.filter_seen,
                                      stats=stats if self.collect_recommend_stats else None, queries=self._test_queries(test_users))
         self.recommend_stats = stats
-        if hasattr(ops, 'ids_to_host'):
-            recs = ops.ids_to_host(recs_dev, self._item_inv)
-        else:
-            recs = ops.to_host(recs_dev)
-            recs = np.where(recs >= 0, self._item_inv[np.maximum(recs, 0)], -1).astype(np.int64)
+        recs = self._external_ids(recs_dev, self._item_inv)
         self._recs_dev = (recs, recs_dev)
         return recs
 

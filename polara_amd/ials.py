@@ -14,7 +14,6 @@ from timeit import default_timer as timer
 
 import numpy as np
 
-from . import scoring
 from .factor_serving import FactorQueriesMixin
 from .models import RecommenderModel
 
@@ -92,18 +91,6 @@ class ImplicitALS(FactorQueriesMixin, RecommenderModel):
         self._factors_dev = None
         self._items_dev = None
 
-    @property
-    def rank(self):
-        return self._rank
-
-    @rank.setter
-    def rank(self, new_value):
-        if new_value != self._rank:
-            self._rank = new_value
-            self._is_ready = False
-            self._recommendations = None
-            self._factor_image = None
-
     @staticmethod
     def confidence(values, alpha=1, weight=None, epsilon=1, dtype='double'):
         """the wrapper's generic confidence: alpha * weight(values / epsilon), or alpha * values / epsilon without a weight"""
@@ -111,16 +98,6 @@ class ImplicitALS(FactorQueriesMixin, RecommenderModel):
         if weight is not None:
             scaled = weight(scaled)
         return (alpha * scaled).astype(dtype)
-
-    def _training_device_csr(self):
-        """The training matrix [n_users x n_items] as a device CSR in the data's own item order (COO -> CSR on the device)."""
-        from .data import ArrayData
-        if getattr(type(self.data), 'to_coo', None) is ArrayData.to_coo:
-            rows, cols, val, shp = self.data.matrix_triplets(feedback_threshold=self.feedback_threshold)
-        else:
-            idx, val, shp = self.data.to_coo(tensor_mode=False, feedback_threshold=self.feedback_threshold)
-            rows, cols = idx[:, 0], idx[:, 1]
-        return self.ops.csr_from_coo(rows, cols, np.asarray(val, dtype=np.float64), shp)
 
     def _confidence_csr(self, A):
         """`A` with `confidence` applied to its stored values — on the host: `weight_func` is any callable and the result is
@@ -137,9 +114,7 @@ class ImplicitALS(FactorQueriesMixin, RecommenderModel):
         return ops.csr_replace_values(A, conf, drop_zeros=True)
 
     def build(self):
-        if self.comm.world > 1:
-            raise NotImplementedError('%s: multi-process builds are not supported (comm.world = %d)'
-                                      % (self.method, self.comm.world))
+        self._require_single_process_build()
         ops = self.ops
         rank = int(self.rank)
         if rank < 1 or rank > ops.ials_max_rank():
@@ -156,19 +131,7 @@ class ImplicitALS(FactorQueriesMixin, RecommenderModel):
         self.factors = {userid: ops.to_host(X), itemid: ops.to_host(Y)}
         self._factors_dev = (self.factors[userid], X)
         self._items_dev = (self.factors[itemid], Y, None)
-        # serving index: the catalogue in descending-norm order of the rows of Y (the pruning bound of the sweep)
-        if hasattr(ops, 'norm_order'):
-            order_dev, _, Ys = ops.norm_order(Y)
-            order = ops.to_host(order_dev).astype(np.int64)
-        else:
-            order = np.argsort(-np.linalg.norm(self.factors[itemid], axis=1), kind='stable').astype(np.int64)
-            Ys = ops.to_device(np.ascontiguousarray(self.factors[itemid][order]))
-        self._item_inv = np.ascontiguousarray(order)
-        self._item_rank = np.empty_like(order)
-        self._item_rank[order] = np.arange(len(order), dtype=order.dtype)
-        self._factor_image = scoring.FactorImage(ops, Ys)
-        self._factor_src = self.factors[itemid]
-        self._test_dev = None
+        self._set_item_serving_index(Y)
 
     # ---- warm start: the fold-in ----------------------------------------------------------------------------------------
     def _item_factors_block(self):

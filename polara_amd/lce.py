@@ -14,6 +14,7 @@ import numpy as np
 from . import scoring
 from .coldstart import (ItemColdStartEvaluationMixin, ItemColdStartRecommenderMixin, ItemColdStartSVDModelMixin,
                         _frame_data, check_image_memory, stack_features)
+from .factor_serving import FactorQueriesMixin
 from .models import RecommenderModel
 
 FLOOR = 1e-10           # the reference's np.maximum(., 1e-10) under every division
@@ -138,7 +139,7 @@ def local_collective_embeddings(ops, Xs, Xu, A, k, alpha=0.1, beta=0.05, lamb=1,
     return W, HuT, HsT
 
 
-class LCEModel(RecommenderModel):
+class LCEModel(FactorQueriesMixin, RecommenderModel):
     """hybrid/models.py:120-225.  `factors` holds host arrays like everywhere else — users [n_users x k], items
     [n_items x k], f'{itemid}_features' [n_labels x k] — and the device copies of the user and feature factors stay for
     the passes.  A rank change invalidates the model: LCE factors are not nested, there is no truncation.
@@ -170,18 +171,6 @@ class LCEModel(RecommenderModel):
     def _clean_metadata(self):
         self.item_features_labels = None
         self._factors_dev = None
-
-    @property
-    def rank(self):
-        return self._rank
-
-    @rank.setter
-    def rank(self, new_value):
-        if new_value != self._rank:
-            self._rank = new_value
-            self._is_ready = False
-            self._recommendations = None
-            self._factor_image = None
 
     def encode_item_features(self):
         """The one-hot matrix of the (training) items in the model's item order [n_items x n_labels] (SciPy CSR); a data
@@ -220,20 +209,8 @@ class LCEModel(RecommenderModel):
         self.graph_time.append(timer() - start)
         return A
 
-    def _training_device_csr(self):
-        """The training matrix [n_users x n_items] as a device CSR in the data's own item order (COO -> CSR on the device)."""
-        from .data import ArrayData
-        if getattr(type(self.data), 'to_coo', None) is ArrayData.to_coo:
-            rows, cols, val, shp = self.data.matrix_triplets(feedback_threshold=self.feedback_threshold)
-        else:
-            idx, val, shp = self.data.to_coo(tensor_mode=False, feedback_threshold=self.feedback_threshold)
-            rows, cols = idx[:, 0], idx[:, 1]
-        return self.ops.csr_from_coo(rows, cols, np.asarray(val, dtype=np.float64), shp)
-
     def build(self):
-        if self.comm.world > 1:
-            raise NotImplementedError('%s: multi-process builds are not supported (comm.world = %d)'
-                                      % (self.method, self.comm.world))
+        self._require_single_process_build()
         if self.item_features is None:
             raise ValueError('%s needs item features: pass item_features= or use a data object that has them' % self.method)
         ops = self.ops
@@ -254,79 +231,11 @@ class LCEModel(RecommenderModel):
         userid, itemid = self.data.fields.userid, self.data.fields.itemid
         self.factors = {userid: ops.to_host(HuT), itemid: ops.to_host(W), f'{itemid}_features': ops.to_host(HsT)}
         self._factors_dev = (self.factors[userid], HuT, HsT)
-        # serving index: the catalogue in descending-norm order of the rows of W (the pruning bound of the sweep)
-        if hasattr(ops, 'norm_order'):
-            order_dev, _, Ws = ops.norm_order(W)
-            order = ops.to_host(order_dev).astype(np.int64)
-        else:
-            order = np.argsort(-np.linalg.norm(self.factors[itemid], axis=1), kind='stable').astype(np.int64)
-            Ws = ops.to_device(np.ascontiguousarray(self.factors[itemid][order]))
-        self._item_inv = np.ascontiguousarray(order)
-        self._item_rank = np.empty_like(order)
-        self._item_rank[order] = np.arange(len(order), dtype=order.dtype)
-        self._factor_image = scoring.FactorImage(ops, Ws)
-        self._factor_src = self.factors[itemid]
-        self._test_dev = None
+        self._set_item_serving_index(W)
 
-    # ---- passes ------------------------------------------------------------------------------------------------------
-    def _user_factors_block(self):
-        """HuT [n_users x k] on the device: the block of the build, or an upload when `factors` was swapped"""
-        Hu = self.factors.get(self.data.fields.userid, None)
-        if Hu is None:
-            raise ValueError('%s: no user factors (build the model first)' % self.method)
-        kept = self._factors_dev
-        if kept is None or kept[0] is not Hu:
-            kept = self._factors_dev = (Hu, self.ops.to_device(np.ascontiguousarray(Hu, dtype=np.float64)),
-                                        self.ops.to_device(np.ascontiguousarray(self.factors[f'{self.data.fields.itemid}_features'],
-                                                                                dtype=np.float64)))
-        return kept[1]
-
-    def _user_rows(self, users):
-        """rows `users` of HuT with an even leading dimension (what the sweep reads its queries' rows at)"""
-        ops = self.ops
-        HuT = self._user_factors_block()
-        k = int(HuT.shape[1])
-        block = ops.zeros(len(users), k + (k & 1))
-        block[:, :k] = HuT[ops.to_device(np.ascontiguousarray(users, dtype=np.int64))]
-        return block[:, :k]
-
-    def get_recommendations(self):
-        if self.data.warm_start:
-            raise NotImplementedError('%s has no warm start' % self.method)
-        if self.verify_integrity:
-            self.verify_data_integrity()
-        ops = self.ops
-        T, n_users, n_items = self._device_test_csr()
-        test_users = np.asarray(self._get_test_data()[2], dtype=np.int64)
-        if len(test_users) != n_users:
-            raise ValueError('%d test users, the test matrix has %d rows' % (len(test_users), n_users))
-        if n_users == 0:
-            return np.empty((0, self.topk), dtype=np.int64)
-        stats = {}
-        recs_dev = scoring.recommend(ops, self._item_factors_device(), T, self.topk, self.filter_seen,
-                                     stats=stats if self.collect_recommend_stats else None, queries=self._user_rows(test_users))
-        self.recommend_stats = stats
-        if hasattr(ops, 'ids_to_host'):
-            recs = ops.ids_to_host(recs_dev, self._item_inv)
-        else:
-            recs = ops.to_host(recs_dev)
-            recs = np.where(recs >= 0, self._item_inv[np.maximum(recs, 0)], -1).astype(np.int64)
-        self._recs_dev = (recs, recs_dev)
-        return recs
-
-    def slice_recommendations(self, test_data, shape, start, stop, test_users=None):
-        """hybrid/models.py:217-225: the dense fp64 scores of test users [start, stop) against every item (external item
-        order) and the slice triplet."""
-        if test_users is None:
-            test_users = self._get_test_data()[2]
-        stop = min(stop, shape[0])
-        slice_data = self._slice_test_data(test_data, start, stop)
-        image = self._item_factors_device()
-        E = self._user_rows(np.asarray(test_users)[start:stop]).contiguous()
-        scores = self.ops.to_host(self.ops.dense_scores(image.V, E))
-        out = np.empty_like(scores)
-        out[:, self._item_inv] = scores
-        return out, slice_data
+    def _extra_factors_device(self):
+        HsT = self.factors[f'{self.data.fields.itemid}_features']
+        return (self.ops.to_device(np.ascontiguousarray(HsT, dtype=np.float64)),)
 
 
 class LCEModelItemColdStart(ItemColdStartEvaluationMixin, ItemColdStartRecommenderMixin, LCEModel):
@@ -366,7 +275,6 @@ class LCEModelItemColdStart(ItemColdStartEvaluationMixin, ItemColdStartRecommend
 
     def _user_factors_device(self):
         """(FactorImage of HuT by descending row norm, host int64 order: catalogue position -> training user)"""
-        import torch
         Hu = self.factors.get(self.data.fields.userid, None)
         if Hu is None:
             raise ValueError('%s: no user factors (build the model first)' % self.method)
@@ -376,13 +284,7 @@ class LCEModelItemColdStart(ItemColdStartEvaluationMixin, ItemColdStartRecommend
         ops = self.ops
         if hasattr(ops, 'free_bytes'):
             check_image_memory(Hu.shape[0], Hu.shape[1], ops.free_bytes())
-        X = self._user_factors_block()
-        if hasattr(ops, 'norm_order'):
-            order_dev, _, Xs = ops.norm_order(X)
-            order = ops.to_host(order_dev).astype(np.int64)
-        else:
-            order = np.argsort(-np.linalg.norm(ops.to_host(X), axis=1), kind='stable').astype(np.int64)
-            Xs = X[torch.from_numpy(order)].contiguous()
+        order, Xs = self._rows_by_norm(self._user_factors_block())
         image = scoring.FactorImage(ops, Xs)
         self._user_image = (Hu, image, order)
         return image, order
@@ -402,15 +304,3 @@ class LCEModelItemColdStart(ItemColdStartEvaluationMixin, ItemColdStartRecommend
         if F.shape[1] != HsT.shape[0]:
             raise ValueError('cold item features over %d labels, the embeddings over %d' % (F.shape[1], HsT.shape[0]))
         return ops.clamp_min(ops.coldstart_queries(F, HsT, cached[1]), 0.0)
-
-    def slice_recommendations(self, cold_item_meta=None, start=0, stop=None):
-        """coldstart/models.py:133-146: the dense fp64 scores of cold items [start, stop) against every training user (in
-        user id order)."""
-        n_cold = self._cold_shape()[0]
-        stop = n_cold if stop is None else min(stop, n_cold)
-        image, order = self._user_factors_device()
-        E = self._cold_queries_device()[start:stop].contiguous()
-        scores = self.ops.to_host(self.ops.dense_scores(image.V, E))
-        out = np.empty_like(scores)
-        out[:, order] = scores
-        return out

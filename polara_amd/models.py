@@ -182,6 +182,25 @@ class RecommenderModel:
         m = csr_matrix((values, indices, indptr), shape=shp)
         return m if sparse_format == 'csr' else m.asformat(sparse_format)
 
+    def _training_triplets(self):
+        """(rows, cols, values, shape) of the training matrix above `feedback_threshold`: our own data object (to_coo not
+        overridden) hands out its columns as they lie, any other one its stacked index."""
+        from .data import ArrayData
+        if getattr(type(self.data), 'to_coo', None) is ArrayData.to_coo:
+            return self.data.matrix_triplets(feedback_threshold=self.feedback_threshold)
+        idx, val, shp = self.data.to_coo(tensor_mode=False, feedback_threshold=self.feedback_threshold)
+        return idx[:, 0], idx[:, 1], val, shp
+
+    def _data_order_training_csr(self):
+        """The training matrix [n_users x n_items] as a device CSR in the data's own item order (COO -> CSR on the device)."""
+        rows, cols, val, shp = self._training_triplets()
+        return self.ops.csr_from_coo(rows, cols, np.asarray(val, dtype=np.float64), shp)
+
+    def _require_single_process_build(self):
+        if self.comm.world > 1:
+            raise NotImplementedError('%s: multi-process builds are not supported (comm.world = %d)'
+                                      % (self.method, self.comm.world))
+
     def _tensor_mode(self):
         try:
             return self.factors.get(self.data.fields.feedback, None) is not None
@@ -281,6 +300,38 @@ class RecommenderModel:
             self._factor_image = scoring.FactorImage(self.ops, self.ops.to_device(v))
             self._factor_src = src
         return self._factor_image
+
+    def _rows_by_norm(self, X):
+        """(host int64 order: position -> row, the rows of the device fp64 block X in that order): by descending row norm,
+        ties by index — sort and gather on the device where the backend has them."""
+        ops = self.ops
+        if hasattr(ops, 'norm_order'):
+            order_dev, _, Xs = ops.norm_order(X)
+            return ops.to_host(order_dev).astype(np.int64), Xs
+        order = np.argsort(-np.linalg.norm(ops.to_host(X), axis=1), kind='stable').astype(np.int64)
+        return order, X[ops.to_device(order)].contiguous()
+
+    def _set_item_serving_index(self, Q_dev):
+        """Serving index of a model whose `factors` hold the item factors Q in the data's item order: the catalogue in
+        descending-norm order of the rows of Q (the pruning bound of the sweep).  Called after `factors` was assigned."""
+        order, Qs = self._rows_by_norm(Q_dev)
+        self._item_inv = np.ascontiguousarray(order)
+        self._item_rank = np.empty_like(order)
+        self._item_rank[order] = np.arange(len(order), dtype=order.dtype)
+        self._factor_image = scoring.FactorImage(self.ops, Qs)
+        self._factor_src = self.factors[self.data.fields.itemid]
+        self._test_dev = None
+
+    def _external_ids(self, recs_dev, table):
+        """The device lists as a host int64 array, positions renamed through `table` (host int64 array: position -> id,
+        None: as they are); pads (-1) stay."""
+        ops = self.ops
+        if hasattr(ops, 'ids_to_host'):
+            return ops.ids_to_host(recs_dev, table)     # renamed on the device, one transfer into pinned memory
+        recs = ops.to_host(recs_dev)
+        if table is None:
+            return recs
+        return np.where(recs >= 0, table[np.maximum(recs, 0)], -1).astype(np.int64)
 
     def _test_weights(self, test_data):
         """Per-entry fold-in coefficients; None = the feedback values themselves."""
@@ -396,13 +447,7 @@ class RecommenderModel:
         if hi > lo:
             recs_dev = scoring.recommend(ops, self._item_factors_device(), T, self.topk, self.filter_seen,
                                          stats=stats if self.collect_recommend_stats else None)
-            if hasattr(ops, 'ids_to_host'):
-                # internal positions -> external item ids on the device, one transfer into pinned memory
-                recs = ops.ids_to_host(recs_dev, self._item_inv)
-            else:
-                recs = ops.to_host(recs_dev)
-                if self._item_inv is not None:   # internal positions -> external item ids
-                    recs = np.where(recs >= 0, self._item_inv[np.maximum(recs, 0)], -1).astype(np.int64)
+            recs = self._external_ids(recs_dev, self._item_inv)     # internal positions -> external item ids
         else:
             recs = np.empty((0, self.topk), dtype=np.int64)
         self.recommend_stats = stats
@@ -659,14 +704,7 @@ class SVDModel(RecommenderModel):
             return A
         # COO -> CSR, per-item counts and the renaming into the internal (popularity) order all run on the device
         # (csrc/ingest.hip): the index array of `to_coo` goes up as it is
-        from .data import ArrayData
-        if getattr(type(self.data), 'to_coo', None) is ArrayData.to_coo:   # our own data object (to_coo not overridden): the
-            # columns as they lie, no stacked index
-            rows, cols, val, shp = self.data.matrix_triplets(feedback_threshold=self.feedback_threshold)
-        else:
-            idx, val, shp = self.data.to_coo(tensor_mode=False, feedback_threshold=self.feedback_threshold)
-            rows, cols = idx[:, 0], idx[:, 1]
-        A = self.ops.csr_from_coo(rows, cols, val, shp)
+        A = self.ops.csr_from_coo(*self._training_triplets())
         self._item_rank, self._item_inv, _, rank_dev = self.ops.item_order(A, self.comm if self._presharded() else None)
         return self.ops.csr_relabel_cols(A, rank_dev)
 
@@ -1036,15 +1074,6 @@ class _DenseItemModel(RecommenderModel):
             raise NotImplementedError('%s: multi-process scoring is not supported (comm.world = %d)'
                                       % (type(self).__name__, self.comm.world))
 
-    def _training_coo(self):
-        from .data import ArrayData
-        if getattr(type(self.data), 'to_coo', None) is ArrayData.to_coo:
-            rows, cols, val, shp = self.data.matrix_triplets(feedback_threshold=self.feedback_threshold)
-        else:
-            idx, val, shp = self.data.to_coo(tensor_mode=False, feedback_threshold=self.feedback_threshold)
-            rows, cols = idx[:, 0], idx[:, 1]
-        return rows, cols, val, shp
-
     def get_recommendations(self):
         from . import i2i
         if self.verify_integrity:
@@ -1059,7 +1088,37 @@ class _DenseItemModel(RecommenderModel):
 
 class _SparseScoresMixin:
     """`downvote_seen_items` and `get_topk_elements` that also take the SciPy score matrices of a sparse branch
-    (CooccurrenceModel, SimilarityAggregation: what their `slice_recommendations` returns without `dense_output`)."""
+    (CooccurrenceModel, SimilarityAggregation: what their `slice_recommendations` returns without `dense_output`), and the
+    two entry points those models share.  A model provides `_score`, `_implicit_values` (the host counterpart of its
+    `_test_values`) and `_slice_scores` (the host score block of a slice's device CSR)."""
+
+    def recommend_with_scores(self):
+        """(lists, their fp64 scores) of every test user, both host arrays (pads: item -1, score 0)."""
+        if not self._is_ready:
+            self.build()
+        self._single_process()
+        from . import i2i
+        T, n_users, n_items = self._device_test_csr()
+        i2i.check_topk(self.topk, n_items, self._topk_limit)
+        recs, scores = self._score(T, n_items, want_scores=True)
+        return self.ops.to_host(recs), self.ops.to_host(scores)
+
+    def slice_recommendations(self, test_data, shape, start, stop, test_users=None):
+        """models.py:716-725, hybrid/models.py:39-44: the scores of test users [start, stop) — a dense ndarray
+        (dense_output) or a SciPy CSR with explicit zeros removed — and the slice triplet.  The product runs on the device."""
+        from scipy.sparse import csr_matrix
+        stop = min(stop, shape[0])
+        users, items, fdbk = self._slice_test_data(test_data, start, stop)
+        vals = np.asarray(fdbk, dtype=np.float64)
+        if self.implicit:
+            vals = self._implicit_values(vals)
+        indptr, indices, values = scoring.test_csr_from_triplet((users, items, vals), (stop - start, shape[1]), None)
+        T = self.ops.csr(indptr, indices, values, (stop - start, shape[1]))
+        scores = np.ascontiguousarray(self._slice_scores(T, shape[1]))
+        if not self.dense_output:
+            scores = csr_matrix(scores)
+            scores.eliminate_zeros()
+        return scores, (users, items, fdbk)
 
     def downvote_seen_items(self, recs, idx_seen):
         """models.py:494-519.  A SciPy matrix (sparse branch): the seen entries become 0 and leave the matrix, IN PLACE
@@ -1132,7 +1191,7 @@ class CooccurrenceModel(_SparseScoresMixin, _DenseItemModel):
         self._single_process()
         ops = self.ops
         self._i2i = None
-        rows, cols, val, shp = self._training_coo()
+        rows, cols, val, shp = self._training_triplets()
         A = ops.csr_from_coo(rows, cols, val, shp)
         if self.implicit:
             A = A.with_columns(A.indices, torch.sign(A.values))
@@ -1152,34 +1211,10 @@ class CooccurrenceModel(_SparseScoresMixin, _DenseItemModel):
                                          sparse=not self.dense_output, want_scores=want_scores)
         return (recs, scores) if want_scores else recs
 
-    def recommend_with_scores(self):
-        """(lists, their fp64 scores) of every test user, both host arrays (pads: item -1, score 0)."""
-        if not self._is_ready:
-            self.build()
-        self._single_process()
-        from . import i2i
-        T, n_users, n_items = self._device_test_csr()
-        i2i.check_topk(self.topk, n_items, self._topk_limit)
-        recs, scores = self._score(T, n_items, want_scores=True)
-        return self.ops.to_host(recs), self.ops.to_host(scores)
+    _implicit_values = staticmethod(np.sign)
 
-    def slice_recommendations(self, test_data, shape, start, stop, test_users=None):
-        """models.py:716-725: the scores of test users [start, stop) — a dense ndarray (dense_output) or a SciPy CSR with
-        explicit zeros removed — and the slice triplet.  The product runs on the device (pk_spmm_csr_ex over C's image)."""
-        from scipy.sparse import csr_matrix
-        stop = min(stop, shape[0])
-        users, items, fdbk = self._slice_test_data(test_data, start, stop)
-        vals = np.asarray(fdbk, dtype=np.float64)
-        if self.implicit:
-            vals = np.sign(vals)
-        indptr, indices, values = scoring.test_csr_from_triplet((users, items, vals), (stop - start, shape[1]), None)
-        T = self.ops.csr(indptr, indices, values, (stop - start, shape[1]))
-        scores = self.ops.to_host(self.ops.spmm(T, self._i2i))[:, :shape[1]]
-        scores = np.ascontiguousarray(scores)
-        if not self.dense_output:
-            scores = csr_matrix(scores)
-            scores.eliminate_zeros()
-        return scores, (users, items, fdbk)
+    def _slice_scores(self, T, n_items):
+        return self.ops.to_host(self.ops.spmm(T, self._i2i))[:, :n_items]      # pk_spmm_csr_ex over C's image
 
 
 class PopularityModel(_DenseItemModel):

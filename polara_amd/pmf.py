@@ -16,7 +16,7 @@ from timeit import default_timer as timer
 
 import numpy as np
 
-from . import machine_model, scoring
+from . import machine_model
 from .csr import coo_to_csr
 from .factor_serving import FactorQueriesMixin
 from .models import RecommenderModel
@@ -188,32 +188,8 @@ class ProbabilisticMF(FactorQueriesMixin, RecommenderModel):
     def _clean_metadata(self):
         self._factors_dev = None
 
-    @property
-    def rank(self):
-        return self._rank
-
-    @rank.setter
-    def rank(self, new_value):
-        if new_value != self._rank:
-            self._rank = new_value
-            self._is_ready = False
-            self._recommendations = None
-            self._factor_image = None
-
-    def _training_device_csr(self):
-        """The training matrix [n_users x n_items] as a device CSR in the data's own item order (COO -> CSR on the device)."""
-        from .data import ArrayData
-        if getattr(type(self.data), 'to_coo', None) is ArrayData.to_coo:
-            rows, cols, val, shp = self.data.matrix_triplets(feedback_threshold=self.feedback_threshold)
-        else:
-            idx, val, shp = self.data.to_coo(tensor_mode=False, feedback_threshold=self.feedback_threshold)
-            rows, cols = idx[:, 0], idx[:, 1]
-        return self.ops.csr_from_coo(rows, cols, np.asarray(val, dtype=np.float64), shp)
-
     def build(self, adjust_gradient=None, adjustment_params=None):
-        if self.comm.world > 1:
-            raise NotImplementedError('%s: multi-process builds are not supported (comm.world = %d)'
-                                      % (self.method, self.comm.world))
+        self._require_single_process_build()
         if self.optimizer is not pmf_sgd:
             raise NotImplementedError('%s: the optimizer %r is not implemented (only the device sweep, polara_amd.pmf.pmf_sgd)'
                                       % (self.method, getattr(self.optimizer, '__name__', self.optimizer)))
@@ -234,16 +210,4 @@ class ProbabilisticMF(FactorQueriesMixin, RecommenderModel):
         userid, itemid = self.data.fields.userid, self.data.fields.itemid
         self.factors = {userid: ops.to_host(P), itemid: ops.to_host(Q)}
         self._factors_dev = (self.factors[userid], P)
-        # serving index: the catalogue in descending-norm order of the rows of Q (the pruning bound of the sweep)
-        if hasattr(ops, 'norm_order'):
-            order_dev, _, Qs = ops.norm_order(Q)
-            order = ops.to_host(order_dev).astype(np.int64)
-        else:
-            order = np.argsort(-np.linalg.norm(self.factors[itemid], axis=1), kind='stable').astype(np.int64)
-            Qs = ops.to_device(np.ascontiguousarray(self.factors[itemid][order]))
-        self._item_inv = np.ascontiguousarray(order)
-        self._item_rank = np.empty_like(order)
-        self._item_rank[order] = np.arange(len(order), dtype=order.dtype)
-        self._factor_image = scoring.FactorImage(ops, Qs)
-        self._factor_src = self.factors[itemid]
-        self._test_dev = None
+        self._set_item_serving_index(Q)

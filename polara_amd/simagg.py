@@ -10,7 +10,7 @@ from timeit import default_timer as timer
 
 import numpy as np
 
-from . import i2i, scoring
+from . import i2i
 from .coldstart import ItemColdStartEvaluationMixin
 from .models import RecommenderModel, _DenseItemModel, _setting, _SparseScoresMixin
 
@@ -135,32 +135,12 @@ class SimilarityAggregation(_SparseScoresMixin, _DenseItemModel):
                                           sparse=not self.dense_output, want_scores=want_scores)
         return (recs, scores) if want_scores else recs
 
-    def recommend_with_scores(self):
-        """(lists, their fp64 scores) of every test user, both host arrays (pads: item -1, score 0)."""
-        if not self._is_ready:
-            self.build()
-        self._single_process()
-        T, n_users, n_items = self._device_test_csr()
-        i2i.check_topk(self.topk, n_items, self._topk_limit)
-        recs, scores = self._score(T, n_items, want_scores=True)
-        return self.ops.to_host(recs), self.ops.to_host(scores)
+    @staticmethod
+    def _implicit_values(vals):
+        return (vals != 0).astype(np.float64)
 
-    def slice_recommendations(self, test_data, shape, start, stop, test_users=None):
-        """hybrid/models.py:39-44: the scores of test users [start, stop) — a dense ndarray (dense_output) or a SciPy CSR
-        with zeros removed — and the slice triplet.  The product runs on the device (pk_spsp_rows_f64)."""
-        from scipy.sparse import csr_matrix
-        stop = min(stop, shape[0])
-        users, items, fdbk = self._slice_test_data(test_data, start, stop)
-        vals = np.asarray(fdbk, dtype=np.float64)
-        if self.implicit:
-            vals = (vals != 0).astype(np.float64)
-        indptr, indices, values = scoring.test_csr_from_triplet((users, items, vals), (stop - start, shape[1]), None)
-        T = self.ops.csr(indptr, indices, values, (stop - start, shape[1]))
-        scores = np.ascontiguousarray(self.ops.to_host(self.ops.spsp_rows(T, self._operand())))
-        if not self.dense_output:
-            scores = csr_matrix(scores)
-            scores.eliminate_zeros()
-        return scores, (users, items, fdbk)
+    def _slice_scores(self, T, n_items):
+        return self.ops.to_host(self.ops.spsp_rows(T, self._operand()))         # pk_spsp_rows_f64
 
 
 class SimilarityAggregationItemColdStart(ItemColdStartEvaluationMixin, RecommenderModel):

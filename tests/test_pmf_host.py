@@ -384,3 +384,69 @@ def test_the_library_states_its_bounds_without_a_device():
     rc = lib.pk_pmf_epoch_f64(None, _lib.PK_PMF_MAX_BLOCKS + 1, 10, 0, None, None, None, None, None, 0, None, 0, None, None, 0.1, 0.5,
                               0, None, 0, None, 0, 0.9, 1e-6, None, None)
     assert rc == -1 and b'blocks' in lib.pk_last_error()
+
+
+# ---- the model layer these models share (models.RecommenderModel, factor_serving, coldstart) -------------------------------
+def test_the_shared_serving_code_has_one_implementation():
+    import polara_amd
+    from polara_amd.coldstart import ItemColdStartRecommenderMixin, SVDModelItemColdStart
+    from polara_amd.factor_serving import FactorQueriesMixin
+    for cls in (polara_amd.LCEModel, polara_amd.ProbabilisticMF, polara_amd.ImplicitALS):
+        for name in ('get_recommendations', 'slice_recommendations', '_user_rows', 'rank'):
+            assert getattr(cls, name) is getattr(FactorQueriesMixin, name), (cls.__name__, name)
+    cold = polara_amd.LCEModelItemColdStart
+    assert cold.get_recommendations is ItemColdStartRecommenderMixin.get_recommendations
+    assert cold.slice_recommendations is ItemColdStartRecommenderMixin.slice_recommendations
+    assert SVDModelItemColdStart.slice_recommendations is ItemColdStartRecommenderMixin.slice_recommendations
+    assert polara_amd.CooccurrenceModel.recommend_with_scores is polara_amd.SimilarityAggregation.recommend_with_scores
+
+
+def _small_lce():
+    import lce_reference
+    m = lce_reference.model_for(load_golden('lce_std'), lce_reference.LCENumpyOps())
+    m.max_iterations = 2
+    return m
+
+
+def _small_pmf():
+    m = ref.model_for(load_golden('pmf_std'), ref.PMFNumpyOps())
+    m.num_epochs = 2
+    return m
+
+
+def _small_ials():
+    import ials_reference
+    return ials_reference.model_for(ials_reference.model_case('r7'), ials_reference.IALSNumpyOps())
+
+
+@pytest.mark.parametrize('make, extra', [(_small_lce, 1), (_small_pmf, 0), (_small_ials, 0)])
+def test_swapped_factors_are_uploaded_again_and_a_rank_change_invalidates(make, extra):
+    m = make()
+    m.build()
+    recs = m.get_recommendations().copy()
+    userid, itemid = m.data.fields.userid, m.data.fields.itemid
+    kept = m._factors_dev
+    m.factors = {k: v.copy() for k, v in m.factors.items()}
+    assert np.array_equal(m.get_recommendations(), recs)
+    assert m._factors_dev is not kept and m._factors_dev[0] is m.factors[userid] and len(m._factors_dev) == 2 + extra
+    assert np.array_equal(m.ops.to_host(m._factors_dev[1]), m.factors[userid])
+    if extra:
+        assert np.array_equal(m.ops.to_host(m._factors_dev[2]), m.factors[f'{itemid}_features'])
+    assert m._is_ready and m._factor_image is not None
+    m.rank = m.rank + 1
+    assert m._is_ready is False and m._factor_image is None
+
+
+def test_rows_by_norm_is_the_stable_argsort_of_the_row_norms():
+    X = np.random.RandomState(5).standard_normal((37, 5))
+    X[30] = X[5]                    # two rows of equal norm
+    X[20] = 0.
+    norms = np.linalg.norm(X, axis=1)
+    assert norms[30] == norms[5] and norms[20] == 0.
+    m = _small_pmf()
+    assert not hasattr(m.ops, 'norm_order')                 # the double: the host statement of HipOps.norm_order
+    order, Xs = m._rows_by_norm(m.ops.to_device(X))
+    assert isinstance(order, np.ndarray) and order.dtype == np.int64
+    assert np.array_equal(order, np.argsort(-norms, kind='stable')) and order[-1] == 20
+    assert list(order).index(5) + 1 == list(order).index(30)            # ties by index
+    assert np.array_equal(m.ops.to_host(Xs), X[order])
