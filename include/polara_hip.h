@@ -880,6 +880,48 @@ int pk_pmf_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, co
                      double smoothing, double *work_dev, double *sse_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Bayesian personalised ranking (csrc/bpr.hip): LearnBPR (Rendle et al., 2009) with rank k plus an item bias, fp64.
+ * P [n_users x (k + 1)]: column k is the constant 1 and is never written.  Q [n_items x (k + 1)]: column k is the bias.
+ * The positives are the stored entries of the training CSR (entry e = its position in storage), in the SCHEDULE order of
+ * PMF above — with the items cut into parts along the epoch's item order pi (polara_amd/bpr.py): part c of the items is
+ * item_order[item_ptr[c] .. item_ptr[c + 1]], and item_part[i] is the part of item i.  perm[p] is the entry at position p.
+ *   Negatives (pk_bpr_draw_negatives, one thread per position):  mix64 = the splitmix64 output function,
+ *     h = mix64(seed * 2^32 + epoch);  for t = 0 .. PK_BPR_DRAWS - 1:
+ *       w = mix64(h + 4 * e + t) >> 32;   x = (w * n_c) >> 32  (64-bit; n_c = the size of the positive's item part c);
+ *       j = item_order[item_ptr[c] + x];  the first j that is not in row u of the CSR (binary search on its sorted
+ *       columns) is the negative.  neg[p] = -1 when all draws are seen items: the sample is skipped.
+ *   A block is swept sequentially by one group of w lanes, w = the smallest of 16, 32, 64 that is >= k + 1; lane c holds
+ *   column c.  Per sample (u, i, j) in IEEE fp64 without contraction, the division correctly rounded:
+ *     d[c]  = Qi[c] - Qj[c]                                     (c = 0..k; 0 beyond)
+ *     x     = halving tree over P[u][c] * d[c] as in PMF above
+ *     z     = sigm(x) = 1 / (1 + exp(x)), by the sequence below
+ *     P[u][c] <- P[u][c] + lr * (z * d[c] - reg * P[u][c])      (c < k)
+ *     Qi[c]   <- Qi[c] + lr * (z * P_old[u][c] - reg * Qi[c])   (c <= k)
+ *     Qj[c]   <- Qj[c] - lr * (z * P_old[u][c] + reg * Qj[c])   (c <= k)
+ *     correct += (x > 0);  trained += 1.   A skipped sample loads and stores nothing and counts as skipped.
+ *   A row stays in registers while the next sample of the block uses it again: the user row, and either item row in
+ *   either role.  Counts are 64-bit integers per block, added per stratum and then per epoch: counts_dev[0..2] =
+ *   trained, skipped, correct.  No atomics.
+ *   sigm(x):  a = -|x|, raised to -750 when below (a NaN stays);  n = floor(a * 0x1.71547652b82fep+0 + 0.5);
+ *     r = (a - n * 0x1.62e42feep-1) - n * 0x1.a39ef35793c76p-33;  T = Horner form of sum_{m = 0..13} r^m / m! with the
+ *     doubles nearest to 1 / m!;  e = ldexp(T, n);  sigm = 1 / (1 + e) for x <= 0 (and NaN), e / (1 + e) for x > 0.
+ *     pk_bpr_sigmoid_f64 is this function alone, elementwise.
+ * work_dev: pk_bpr_work_bytes(blocks) bytes.  The kernels trust the plan (indices in range, block_ptr ascending). */
+#define PK_BPR_DRAWS 4
+int32_t pk_bpr_max_rank(void);
+int64_t pk_bpr_work_bytes(int32_t blocks);
+int pk_bpr_sigmoid_f64(void *stream, int64_t n, const double *x_dev, double *out_dev);
+int pk_bpr_draw_negatives(void *stream, int64_t nnz, int64_t n_users, int64_t n_items, int32_t blocks,
+                          const int32_t *users_dev, const int32_t *items_dev, const int64_t *perm_dev,
+                          const int32_t *item_order_dev, const int32_t *item_part_dev, const int64_t *item_ptr_dev,
+                          const int64_t *indptr_dev, const int32_t *indices_dev, uint32_t seed, uint32_t epoch,
+                          int32_t *neg_dev);
+int pk_bpr_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, const int64_t *block_ptr_dev,
+                     const int32_t *users_dev, const int32_t *items_dev, const int32_t *neg_dev, double *P_dev, int64_t ldp,
+                     double *Q_dev, int64_t ldq, double learning_rate, double regularization, void *work_dev,
+                     int64_t *counts_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Implicit ALS (csrc/ials.hip): the alternating least squares of Hu, Koren and Volinsky for a CSR of confidences C
  * [n_rows x n_cols] (fp64 values, int64 row pointers, int32 column ids).  One half-step fixes Y [n_cols x rank] and solves
  * for every row u

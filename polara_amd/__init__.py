@@ -7,6 +7,7 @@
     from polara_amd import LCEModel, LCEModelItemColdStart          # Local Collective Embeddings, standard and item cold start
     from polara_amd import ProbabilisticMF                          # PMF trained by a blocked SGD sweep
     from polara_amd import ImplicitALS                              # iALS / WRMF: alternating least squares, exact per-row solves
+    from polara_amd import ImplicitBPR                              # BPR-MF: pairwise ranking by a blocked triplet sweep
     from polara_amd import SVDModelSampled, RandomSampleArrayData   # sampled-negatives evaluation (1 holdout + n unseen items)
     from polara_amd import ArrayData, ShardedArrayData              # NumPy / on-disk data providers
 
@@ -96,6 +97,7 @@ _EXPORTS = {
     'LCEModel': 'lce', 'LCEModelItemColdStart': 'lce',
     'ProbabilisticMF': 'pmf',
     'ImplicitALS': 'ials',
+    'ImplicitBPR': 'bpr',
     'SimilarityAggregation': 'simagg', 'SimilarityAggregationItemColdStart': 'simagg',
     'cosine_similarity': 'similarity', 'cosine_tfidf_similarity': 'similarity', 'jaccard_similarity': 'similarity',
     'jaccard_similarity_weighted': 'similarity', 'cross_similarity': 'similarity', 'combine_similarity': 'similarity',

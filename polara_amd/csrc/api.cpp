@@ -86,6 +86,7 @@ extern "C" int pk_device_info(int device, char *name, int name_len, int *cu_coun
 // one model paid for eleven of those loads inside its first (and only) build — the reference's `svds` call has no such
 // first-call cost (models.py:843-844; tools/timing.py:20-34 times the single call).  pk_warm_up loads them all at once,
 // on the current device; the host layer calls it when a context / HipOps object is created.
+hipError_t pk_tu_load_bpr();
 hipError_t pk_tu_load_dense();
 hipError_t pk_tu_load_driver();
 hipError_t pk_tu_load_eigh();
@@ -107,7 +108,7 @@ hipError_t pk_tu_load_spmm();
 hipError_t pk_tu_load_ttm();
 
 extern "C" int pk_warm_up(void) {
-    hipError_t (*const loaders[])() = {pk_tu_load_dense, pk_tu_load_driver, pk_tu_load_eigh, pk_tu_load_eigh_top, pk_tu_load_evalmetrics, pk_tu_load_foldq, pk_tu_load_hybrid, pk_tu_load_i2i, pk_tu_load_ials, pk_tu_load_ingest, pk_tu_load_lce, pk_tu_load_pmf, pk_tu_load_rescore, pk_tu_load_sampled, pk_tu_load_score, pk_tu_load_simagg, pk_tu_load_spgemm, pk_tu_load_spmm, pk_tu_load_ttm};
+    hipError_t (*const loaders[])() = {pk_tu_load_bpr, pk_tu_load_dense, pk_tu_load_driver, pk_tu_load_eigh, pk_tu_load_eigh_top, pk_tu_load_evalmetrics, pk_tu_load_foldq, pk_tu_load_hybrid, pk_tu_load_i2i, pk_tu_load_ials, pk_tu_load_ingest, pk_tu_load_lce, pk_tu_load_pmf, pk_tu_load_rescore, pk_tu_load_sampled, pk_tu_load_score, pk_tu_load_simagg, pk_tu_load_spgemm, pk_tu_load_spmm, pk_tu_load_ttm};
     for (auto f : loaders) {
         const hipError_t e = f();
         if (e != hipSuccess) {

@@ -1992,6 +1992,49 @@ class HipOps:
     def pmf_max_rank(self):
         return int(self.lib.pk_pmf_max_rank())
 
+    def _block_schedule(self, A, blocks, what, item_order=None):
+        """The one copy of the blocked schedule (pmf.block_schedule) behind pmf_plan and bpr_plan, built on the device with
+        integer arithmetic only and the library's stable radix sort of (s * B + i, position) pairs.  item_order (a device
+        int64 permutation of the items, None: the identity): the items are cut into parts along it.  Returns (users, items,
+        ucnt, icnt — int64, canonical order —, perm, block_ptr, the item parts along the order [n_items] int64)."""
+        n_users, n_items = A.shape
+        B, nnz = int(blocks), int(A.nnz)
+        if B < 1 or B > min(n_users, n_items):
+            raise ValueError('%s: %d blocks for %d users and %d items (1 .. min of the two)' % (what, B, n_users, n_items))
+        if B > _lib.PK_PMF_MAX_BLOCKS:
+            raise ValueError('%s: %d blocks, the library takes at most %d' % (what, B, _lib.PK_PMF_MAX_BLOCKS))
+        if nnz >= 2 ** 31:
+            raise ValueError('%s: %d interactions, the schedule is indexed with 32 bits' % (what, nnz))
+        dev = self.device
+        indptr = A.indptr[:n_users + 1]
+        items = A.indices[:nnz].to(torch.int64)
+        ucnt = indptr[1:] - indptr[:-1]
+        users = torch.repeat_interleave(torch.arange(n_users, dtype=torch.int64, device=dev), ucnt, output_size=nnz)
+        icnt = self.bincount(items, n_items) if nnz else torch.zeros(n_items, dtype=torch.int64, device=dev)
+        part = lambda cnt: torch.clamp((torch.cumsum(cnt, 0) - cnt) * B // max(nnz, 1), max=B - 1)
+        if item_order is None:
+            ordered_parts = ipart = part(icnt)
+        else:
+            ordered_parts = part(icnt[item_order])
+            ipart = torch.empty_like(ordered_parts)
+            ipart[item_order] = ordered_parts
+        i, j = part(ucnt)[users], ipart[items]
+        keys = (torch.remainder(j - i, B) * B + i).to(torch.int32).contiguous()
+        block_ptr = torch.zeros(B * B + 1, dtype=torch.int64, device=dev)
+        n1 = max(nnz, 1)
+        pos = torch.arange(n1, dtype=torch.int32, device=dev)
+        in_tmp = C.c_int32(0)
+        pos_tmp = torch.empty_like(pos)
+        if nnz:
+            block_ptr[1:] = torch.cumsum(self.bincount(keys, B * B), 0)
+            keys_tmp = torch.empty_like(keys)
+            bits = max(1, int(B * B - 1).bit_length())
+            work = self._work(self.lib.pk_radix_work_bytes(nnz))
+            _lib.check(self.lib.pk_radix_sort_pairs(self.stream(), nnz, 4, _ptr(keys), _ptr(pos), _ptr(keys_tmp), _ptr(pos_tmp),
+                                                    bits, _ptr(work), C.byref(in_tmp)), 'pk_radix_sort_pairs')
+        perm = (pos_tmp if in_tmp.value else pos)[:nnz].to(torch.int64)
+        return users, items, ucnt, icnt, perm, block_ptr, ordered_parts
+
     def pmf_plan(self, A, blocks):
         """The blocked schedule of pmf.block_schedule for the entries of the canonical DeviceCSR `A` [n_users x n_items],
         built on the device with integer arithmetic only (so that it equals the host plan element for element) and the
@@ -1999,38 +2042,11 @@ class HipOps:
         (int32) and vals (fp64) in schedule order, row_nnz / col_nnz (the entry counts as fp64), blocks, nnz, shape."""
         n_users, n_items = A.shape
         B, nnz = int(blocks), int(A.nnz)
-        if B < 1 or B > min(n_users, n_items):
-            raise ValueError('PMF: %d blocks for %d users and %d items (1 .. min of the two)' % (B, n_users, n_items))
-        if B > _lib.PK_PMF_MAX_BLOCKS:
-            raise ValueError('PMF: %d blocks, the library takes at most %d' % (B, _lib.PK_PMF_MAX_BLOCKS))
-        if nnz >= 2 ** 31:
-            raise ValueError('PMF: %d interactions, the schedule is indexed with 32 bits' % nnz)
-        dev = self.device
         with self._timed('pmf_plan', (n_users, n_items, nnz, B)):
-            indptr = A.indptr[:n_users + 1]
-            items = A.indices[:nnz].to(torch.int64)
+            users, items, ucnt, icnt, perm, block_ptr, _ = self._block_schedule(A, B, 'PMF')
             vals = A.values[:nnz].to(torch.float64)
             if nnz and bool((vals == 0).any().item()):
                 raise ValueError('PMF: an interaction with feedback 0 (after summing duplicates)')
-            ucnt = indptr[1:] - indptr[:-1]
-            users = torch.repeat_interleave(torch.arange(n_users, dtype=torch.int64, device=dev), ucnt, output_size=nnz)
-            icnt = self.bincount(items, n_items) if nnz else torch.zeros(n_items, dtype=torch.int64, device=dev)
-            part = lambda cnt: torch.clamp((torch.cumsum(cnt, 0) - cnt) * B // max(nnz, 1), max=B - 1)
-            i, j = part(ucnt)[users], part(icnt)[items]
-            keys = (torch.remainder(j - i, B) * B + i).to(torch.int32).contiguous()
-            block_ptr = torch.zeros(B * B + 1, dtype=torch.int64, device=dev)
-            n1 = max(nnz, 1)
-            pos = torch.arange(n1, dtype=torch.int32, device=dev)
-            in_tmp = C.c_int32(0)
-            pos_tmp = torch.empty_like(pos)
-            if nnz:
-                block_ptr[1:] = torch.cumsum(self.bincount(keys, B * B), 0)
-                keys_tmp = torch.empty_like(keys)
-                bits = max(1, int(B * B - 1).bit_length())
-                work = self._work(self.lib.pk_radix_work_bytes(nnz))
-                _lib.check(self.lib.pk_radix_sort_pairs(self.stream(), nnz, 4, _ptr(keys), _ptr(pos), _ptr(keys_tmp), _ptr(pos_tmp),
-                                                        bits, _ptr(work), C.byref(in_tmp)), 'pk_radix_sort_pairs')
-            perm = (pos_tmp if in_tmp.value else pos)[:nnz].to(torch.int64)
             return dict(blocks=B, nnz=nnz, shape=(n_users, n_items), perm=perm, block_ptr=block_ptr,
                         users=users[perm].to(torch.int32).contiguous(), items=items[perm].to(torch.int32).contiguous(),
                         vals=vals[perm].contiguous(), row_nnz=ucnt.to(torch.float64).contiguous(),
@@ -2069,6 +2085,94 @@ class HipOps:
                                                  self._PMF_ADJUST[adjust], _ptr(SP), SP.stride(0) if adjust else 0, _ptr(SQ),
                                                  SQ.stride(0) if adjust else 0, float(gamma), float(smoothing), _ptr(work), _ptr(out)),
                        'pk_pmf_epoch_f64')
+        return out
+
+    # ---- Bayesian personalised ranking (csrc/bpr.hip) -------------------------------------------------------------------
+    def bpr_max_rank(self):
+        return int(self.lib.pk_bpr_max_rank())
+
+    def bpr_plan(self, A, blocks, item_order=None):
+        """The schedule of one BPR epoch (bpr.block_schedule) for the stored entries of the canonical DeviceCSR `A`
+        [n_users x n_items]: PMF's schedule with the items cut into parts along `item_order` (a host permutation of the
+        items; None: the identity).  Returns a dict: perm (the canonical index of every position), block_ptr, item_ptr (int64),
+        users, items (the schedule's, int32), item_order, item_part (int32), matrix, blocks, nnz, shape."""
+        n_users, n_items = A.shape
+        B, nnz = int(blocks), int(A.nnz)
+        if not getattr(A, 'sorted_cols', True):
+            raise ValueError('BPR: the training matrix must be canonical (sorted columns)')
+        if item_order is None:
+            order = torch.arange(n_items, dtype=torch.int64, device=self.device)
+        else:
+            host = np.ascontiguousarray(item_order, dtype=np.int64)
+            if host.shape != (n_items,) or not np.array_equal(np.sort(host), np.arange(n_items)):
+                raise ValueError('BPR: item_order is not a permutation of the %d items' % n_items)
+            order = self.to_device(host)
+        with self._timed('bpr_plan', (n_users, n_items, nnz, B)):
+            users, items, _, _, perm, block_ptr, ordered_parts = self._block_schedule(A, B, 'BPR', None if item_order is None else order)
+            item_ptr = torch.zeros(B + 1, dtype=torch.int64, device=self.device)
+            item_ptr[1:] = torch.cumsum(self.bincount(ordered_parts, B), 0)
+            item_part = torch.empty(n_items, dtype=torch.int32, device=self.device)
+            item_part[order] = ordered_parts.to(torch.int32)
+            return dict(blocks=B, nnz=nnz, shape=(n_users, n_items), perm=perm.contiguous(), block_ptr=block_ptr, item_ptr=item_ptr,
+                        users=users[perm].to(torch.int32).contiguous(), items=items[perm].to(torch.int32).contiguous(),
+                        item_order=order.to(torch.int32).contiguous(), item_part=item_part, matrix=A)
+
+    @staticmethod
+    def _bpr_check_plan(plan):
+        B = int(plan['blocks'])
+        n_items = plan['shape'][1]
+        if plan['block_ptr'].numel() != B * B + 1 or plan['item_ptr'].numel() != B + 1 or plan['users'].numel() != plan['nnz'] \
+                or plan['items'].numel() != plan['nnz'] or plan['perm'].numel() != plan['nnz'] \
+                or plan['item_order'].numel() != n_items or plan['item_part'].numel() != n_items:
+            raise ValueError('BPR: not a plan of bpr_plan')
+        return B
+
+    def bpr_draw_negatives(self, plan, seed, epoch):
+        """int32 [nnz] (device): the negative of every position of the plan's schedule, -1 where all PK_BPR_DRAWS draws were
+        seen items (pk_bpr_draw_negatives; the stream is spelled out in include/polara_hip.h)."""
+        B = self._bpr_check_plan(plan)
+        seed, epoch = int(seed), int(epoch)
+        if not (0 <= seed < 2 ** 32 and 0 <= epoch < 2 ** 32):
+            raise ValueError('BPR: seed %d and epoch %d must fit 32 unsigned bits' % (seed, epoch))
+        n_users, n_items = plan['shape']
+        A, nnz = plan['matrix'], int(plan['nnz'])
+        neg = torch.empty(max(nnz, 1), dtype=torch.int32, device=self.device)[:nnz]
+        with self._timed('bpr_draw_negatives', (nnz, B)):
+            _lib.check(self.lib.pk_bpr_draw_negatives(self.stream(), nnz, n_users, n_items, B, _ptr(plan['users']), _ptr(plan['items']),
+                                                      _ptr(plan['perm']), _ptr(plan['item_order']), _ptr(plan['item_part']),
+                                                      _ptr(plan['item_ptr']), _ptr(A.indptr), _ptr(A.indices), seed, epoch, _ptr(neg)),
+                       'pk_bpr_draw_negatives')
+        return neg
+
+    def bpr_epoch(self, plan, neg, P, Q, learning_rate, regularization):
+        """One LearnBPR sweep over the plan's positives with the negatives `neg` (pk_bpr_epoch_f64: one launch per stratum and
+        one for the counters), P [n_users x (k + 1)] (column k: the constant 1) and Q [n_items x (k + 1)] (column k: the bias)
+        updated in place.  Returns a device tensor of three int64: trained, skipped, correct."""
+        n_users, n_items = plan['shape']
+        k = int(P.shape[1]) - 1
+        if k < 1 or k > self.bpr_max_rank():
+            raise ValueError('BPR: rank %d outside 1..%d' % (k, self.bpr_max_rank()))
+        for X, n in zip((P, Q), (n_users, n_items)):
+            if X.dtype != torch.float64 or X.dim() != 2 or tuple(X.shape) != (n, k + 1) or X.stride(1) != 1 or X.stride(0) < k + 1:
+                raise ValueError('BPR: a block of shape %s, strides %s for [%d x %d] fp64 rows' % (tuple(X.shape), X.stride(), n, k + 1))
+        B = self._bpr_check_plan(plan)
+        if neg.dtype != torch.int32 or neg.dim() != 1 or neg.numel() != plan['nnz'] or (neg.numel() and neg.stride(0) != 1):
+            raise ValueError('BPR: the negatives must be int32 [%d] (bpr_draw_negatives)' % plan['nnz'])
+        work = self._work(self.lib.pk_bpr_work_bytes(B))              # the counters of every block
+        out = torch.empty(3, dtype=torch.int64, device=self.device)
+        with self._timed('bpr_epoch', (plan['nnz'], k, B)):
+            _lib.check(self.lib.pk_bpr_epoch_f64(self.stream(), B, k, int(plan['nnz']), _ptr(plan['block_ptr']), _ptr(plan['users']),
+                                                 _ptr(plan['items']), _ptr(neg), _ptr(P), P.stride(0), _ptr(Q), Q.stride(0),
+                                                 float(learning_rate), float(regularization), _ptr(work), _ptr(out)),
+                       'pk_bpr_epoch_f64')
+        return out
+
+    def bpr_sigmoid(self, x):
+        """1 / (1 + exp(x)) elementwise by the sweep's own sequence of IEEE operations (pk_bpr_sigmoid_f64)"""
+        if x.dtype != torch.float64 or not x.is_contiguous():
+            raise ValueError('BPR: the sigmoid takes a contiguous fp64 tensor')
+        out = torch.empty_like(x)
+        _lib.check(self.lib.pk_bpr_sigmoid_f64(self.stream(), x.numel(), _ptr(x), _ptr(out)), 'pk_bpr_sigmoid_f64')
         return out
 
     # ---- Implicit ALS (csrc/ials.hip) ----------------------------------------------------------------------------------
