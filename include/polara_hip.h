@@ -880,6 +880,38 @@ int pk_pmf_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, co
                      double smoothing, double *work_dev, double *sse_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Kernelized probabilistic matrix factorisation (csrc/kpmf.hip).  Replaces `generalized_sgd_sweep` as
+ * `kernelized_pmf_sgd` drives it (lib/optimize.py:258-301: the transform `sparse_kernel_update`).  Everything is PMF
+ * above — schedule, lane groups, halving tree, lambdas, adjusters, squared error — except the two gradients:
+ *     off_p = (+0.0 + Ku[e1] * X(j1)) + Ku[e2] * X(j2) + ...   over the stored entries e of row m of Ku WITHOUT its diagonal,
+ *                                                             in storage order, every product and every sum rounded
+ *     X(j)  = P[j]       (live)  if user_part[j] == I          (I, J: the user part and the item part of the sample's block;
+ *           = P_snap[j]          otherwise                      block i of stratum s has I = i, J = (i + s) mod B)
+ *     kp    = off_p + du[m] * (pm + pm)                        du[m]: the diagonal of row m (0.0 when none is stored); the
+ *                                                             reference's diagonal term is value * (P[m] + pm)
+ *     gp    = err * qn - kp * rl
+ *     kq, gq likewise with Ki, item_part, J, Q, Q_snap, di and cl.
+ * P_snap / Q_snap [n x rank, leading dimensions of their own] hold P and Q as they stood when the stratum began: the entry
+ * copies both blocks before the first stratum and after every stratum (so they equal P and Q when the epoch ends).  Rows of
+ * a block's own parts are written by that block alone during the stratum and the block is swept serially, so their live
+ * value is well defined; every other row comes from the snapshot, so no block reads what another is writing.  With B = 1
+ * every row is live and the sweep is the reference's; with B > 1 the neighbour rows of the regulariser (and nothing else)
+ * are stale by at most one stratum.  off_p is computed once per run of samples that share the user.
+ * k*_ptr_dev [n + 1] int64, k*_idx_dev int32 (sorted within a row, no diagonal), k*_val_dev, k*_diag_dev [n] fp64;
+ * *_part_dev [n] int32: the part of every user / item in the schedule.  The kernel trusts the plan and the kernel matrices
+ * (indices in range). */
+int pk_kpmf_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, int64_t n_users, int64_t n_items,
+                      const int64_t *block_ptr_dev, const int32_t *users_dev, const int32_t *items_dev,
+                      const double *vals_dev, double *P_dev, int64_t ldp, double *Q_dev, int64_t ldq,
+                      const double *row_nnz_dev, const double *col_nnz_dev, const int32_t *user_part_dev,
+                      const int32_t *item_part_dev, const int64_t *ku_ptr_dev, const int32_t *ku_idx_dev,
+                      const double *ku_val_dev, const double *ku_diag_dev, const int64_t *ki_ptr_dev,
+                      const int32_t *ki_idx_dev, const double *ki_val_dev, const double *ki_diag_dev,
+                      double *P_snap_dev, int64_t ldps, double *Q_snap_dev, int64_t ldqs, double eta, double lambd,
+                      int32_t adjust, double *SP_dev, int64_t ldsp, double *SQ_dev, int64_t ldsq, double gamma,
+                      double smoothing, double *work_dev, double *sse_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Bayesian personalised ranking (csrc/bpr.hip): LearnBPR (Rendle et al., 2009) with rank k plus an item bias, fp64.
  * P [n_users x (k + 1)]: column k is the constant 1 and is never written.  Q [n_items x (k + 1)]: column k is the bias.
  * The positives are the stored entries of the training CSR (entry e = its position in storage), in the SCHEDULE order of

@@ -180,6 +180,9 @@ PROTOTYPES = {
     'pk_pmf_work_doubles': (_i64, [_i32]),
     'pk_pmf_epoch_f64': (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _f64, _f64, _i32,
                                    _vp, _i64, _vp, _i64, _f64, _f64, _vp, _vp]),
+    'pk_kpmf_epoch_f64': (C.c_int, [_vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f64, _f64, _i32, _vp, _i64, _vp,
+                                    _i64, _f64, _f64, _vp, _vp]),
     'pk_bpr_max_rank': (_i32, []),
     'pk_bpr_work_bytes': (_i64, [_i32]),
     'pk_bpr_sigmoid_f64': (C.c_int, [_vp, _i64, _vp, _vp]),

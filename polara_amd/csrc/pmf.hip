@@ -8,51 +8,7 @@
 // every product and sum below is rounded on its own, as NumPy rounds them (the library is built with contraction on)
 #pragma clang fp contract(off)
 
-#define PMF_MAX_RANK 64
-#define PMF_THREADS 64              // one wave per workgroup: a block's sweep is a chain of dependent loads, so the waves of
-                                    // a stratum are spread over as many SIMDs as there are
-
-struct PmfArgs {
-    int B, rank;
-    const int64_t *block_ptr;
-    const int32_t *users, *items;
-    const double *vals;
-    double *P, *Q;
-    int64_t ldp, ldq;
-    const double *rnnz, *cnnz;
-    double eta, lambd;
-    double *SP, *SQ;
-    int64_t ldsp, ldsq;
-    double gamma, one_minus_gamma, smoothing;
-    double *block_sse;
-};
-
-// the halving tree of polara_hip.h on a xor butterfly: every lane of the group ends with the same bits (a + b == b + a)
-template <int W>
-__device__ __forceinline__ double pmf_group_sum(double v) {
-    if constexpr (W >= 64) v = v + pk_lane_xor<32>(v);
-    if constexpr (W >= 32) v = v + pk_lane_xor<16>(v);
-    v = v + pk_lane_xor<8>(v);
-    v = v + pk_lane_xor<4>(v);
-    v = v + pk_lane_xor<2>(v);
-    v = v + pk_lane_xor<1>(v);
-    return v;
-}
-
-template <int ADJ>
-__device__ __forceinline__ double pmf_adjust(double g, double &s, const PmfArgs &a) {
-    if constexpr (ADJ == PK_PMF_ADJUST_NONE) {
-        return g;
-    } else {
-        double u;
-        if constexpr (ADJ == PK_PMF_ADJUST_ADAGRAD)
-            u = s + g * g;
-        else
-            u = a.gamma * s + a.one_minus_gamma * (g * g);
-        s = u;
-        return g / sqrt(a.smoothing + u);
-    }
-}
+#include "pmf_common.h"               // after the pragma: the shared helpers are compiled without contraction too
 
 // W lanes per block, 64 / W blocks per wave.  The loop runs to the longest block of the wave with every lane active (the
 // butterfly reads its neighbours); a group past the end of its block computes on zeros and stores nothing.  Sample t + 1's
@@ -155,6 +111,10 @@ __global__ __launch_bounds__(256) void pmf_sse_kernel(int B, const double *__res
     }
 }
 
+void pmf_launch_sse(hipStream_t st, int blocks, const double *block_sse_dev, double *sse_dev) {
+    hipLaunchKernelGGL(pmf_sse_kernel, dim3(1), dim3(256), 0, st, blocks, block_sse_dev, sse_dev);
+}
+
 extern "C" int32_t pk_pmf_max_rank(void) { return PMF_MAX_RANK; }
 extern "C" int64_t pk_pmf_work_doubles(int32_t blocks) { return (int64_t)(blocks < 1 ? 1 : blocks) * (blocks < 1 ? 1 : blocks); }
 
@@ -204,7 +164,7 @@ extern "C" int pk_pmf_epoch_f64(void *stream, int32_t blocks, int32_t rank, int6
             pmf_launch<64>(st, adjust, grid, a, s);
         PK_CHECK_LAUNCH("pmf_stratum_kernel");
     }
-    hipLaunchKernelGGL(pmf_sse_kernel, dim3(1), dim3(256), 0, st, (int)blocks, (const double *)work_dev, sse_dev);
+    pmf_launch_sse(st, (int)blocks, work_dev, sse_dev);
     PK_CHECK_LAUNCH("pmf_sse_kernel");
     return PK_OK;
 }

@@ -1992,6 +1992,11 @@ class HipOps:
     def pmf_max_rank(self):
         return int(self.lib.pk_pmf_max_rank())
 
+    @staticmethod
+    def _schedule_parts(cnt, B, nnz):
+        """pmf._parts on the device: the part of every user (item) from its entry counts (int64), integers only"""
+        return torch.clamp((torch.cumsum(cnt, 0) - cnt) * B // max(nnz, 1), max=B - 1)
+
     def _block_schedule(self, A, blocks, what, item_order=None):
         """The one copy of the blocked schedule (pmf.block_schedule) behind pmf_plan and bpr_plan, built on the device with
         integer arithmetic only and the library's stable radix sort of (s * B + i, position) pairs.  item_order (a device
@@ -2011,7 +2016,7 @@ class HipOps:
         ucnt = indptr[1:] - indptr[:-1]
         users = torch.repeat_interleave(torch.arange(n_users, dtype=torch.int64, device=dev), ucnt, output_size=nnz)
         icnt = self.bincount(items, n_items) if nnz else torch.zeros(n_items, dtype=torch.int64, device=dev)
-        part = lambda cnt: torch.clamp((torch.cumsum(cnt, 0) - cnt) * B // max(nnz, 1), max=B - 1)
+        part = lambda cnt: self._schedule_parts(cnt, B, nnz)
         if item_order is None:
             ordered_parts = ipart = part(icnt)
         else:
@@ -2085,6 +2090,69 @@ class HipOps:
                                                  self._PMF_ADJUST[adjust], _ptr(SP), SP.stride(0) if adjust else 0, _ptr(SQ),
                                                  SQ.stride(0) if adjust else 0, float(gamma), float(smoothing), _ptr(work), _ptr(out)),
                        'pk_pmf_epoch_f64')
+        return out
+
+    # ---- Kernelized probabilistic matrix factorisation (csrc/kpmf.hip) ------------------------------------------------------
+    def kpmf_plan(self, A, blocks, Ku, Ki):
+        """pmf_plan(A, blocks) plus what the kernelized sweep reads: user_part / item_part (int32: the part of every user and
+        item in the schedule) and, for the kernel matrices Ku [n_users x n_users] and Ki [n_items x n_items] (SciPy sparse,
+        made canonical here), their off-diagonal CSR (ku_ptr int64, ku_idx int32, ku_val fp64) and their diagonal (ku_diag
+        fp64, 0 where none is stored); likewise ki_*.  Everything on the device."""
+        from . import kpmf
+        plan = self.pmf_plan(A, blocks)
+        n_users, n_items = plan['shape']
+        B, nnz = plan['blocks'], plan['nnz']
+        with self._timed('kpmf_plan', (n_users, n_items, nnz, B)):
+            plan['user_part'] = self._schedule_parts(plan['row_nnz'].to(torch.int64), B, nnz).to(torch.int32).contiguous()
+            plan['item_part'] = self._schedule_parts(plan['col_nnz'].to(torch.int64), B, nnz).to(torch.int32).contiguous()
+            for side, K, n in (('ku', Ku, n_users), ('ki', Ki, n_items)):
+                ptr, idx, val, diag = kpmf.split_kernel(K, n)
+                plan[side + '_ptr'], plan[side + '_idx'] = self.to_device(ptr), self.to_device(idx)
+                plan[side + '_val'], plan[side + '_diag'] = self.to_device(val), self.to_device(diag)
+        return plan
+
+    def kpmf_epoch(self, plan, P, Q, eta, lambd, adjust=None, state=None, gamma=0.9, smoothing=1e-6, snapshots=None):
+        """One kernelized SGD sweep over the plan's interactions (pk_kpmf_epoch_f64: per stratum one launch of the sweep and
+        one that refreshes the snapshots, and one for the squared error), P and Q updated in place.  adjust / state as in
+        pmf_epoch.  snapshots = (P_snap, Q_snap) of the shapes of P and Q (leading dimensions of their own; allocated here
+        when None): whatever they hold is overwritten, and they equal P and Q when the epoch ends.  Returns a device tensor
+        of one double: the epoch's squared error."""
+        n_users, n_items = plan['shape']
+        k = int(P.shape[1])
+        if k < 1 or k > self.pmf_max_rank():
+            raise ValueError('KPMF: rank %d outside 1..%d' % (k, self.pmf_max_rank()))
+        if adjust not in self._PMF_ADJUST:
+            raise ValueError('KPMF: unknown gradient adjustment %r' % (adjust,))
+        if adjust and (state is None or len(state) != 2):
+            raise ValueError('KPMF: the gradient adjustment %r needs state = (SP, SQ)' % adjust)
+        if snapshots is None:
+            snapshots = (self.empty(n_users, k), self.empty(n_items, k))
+        if len(snapshots) != 2:
+            raise ValueError('KPMF: snapshots = (P_snap, Q_snap)')
+        blocks = (P, Q) + tuple(snapshots) + (tuple(state) if adjust else ())
+        for X, n in zip(blocks, (n_users, n_items) * 3):
+            if X.dtype != torch.float64 or X.dim() != 2 or tuple(X.shape) != (n, k) or X.stride(1) != 1 or X.stride(0) < k:
+                raise ValueError('KPMF: a block of shape %s, strides %s for [%d x %d] fp64 rows' % (tuple(X.shape), X.stride(), n, k))
+        B = int(plan['blocks'])
+        if 'ku_ptr' not in plan or plan['block_ptr'].numel() != B * B + 1 or plan['users'].numel() != plan['nnz'] \
+                or plan['row_nnz'].numel() != n_users or plan['col_nnz'].numel() != n_items \
+                or plan['user_part'].numel() != n_users or plan['item_part'].numel() != n_items \
+                or plan['ku_ptr'].numel() != n_users + 1 or plan['ki_ptr'].numel() != n_items + 1 \
+                or plan['ku_diag'].numel() != n_users or plan['ki_diag'].numel() != n_items:
+            raise ValueError('KPMF: not a plan of kpmf_plan')
+        SP, SQ = state if adjust else (None, None)
+        PS, QS = snapshots
+        work = self.empty(int(self.lib.pk_pmf_work_doubles(B)))       # the block sums of the squared error
+        out = self.empty(1)
+        with self._timed('kpmf_epoch', (plan['nnz'], k, B)):
+            _lib.check(self.lib.pk_kpmf_epoch_f64(
+                self.stream(), B, k, int(plan['nnz']), n_users, n_items, _ptr(plan['block_ptr']), _ptr(plan['users']),
+                _ptr(plan['items']), _ptr(plan['vals']), _ptr(P), P.stride(0), _ptr(Q), Q.stride(0), _ptr(plan['row_nnz']),
+                _ptr(plan['col_nnz']), _ptr(plan['user_part']), _ptr(plan['item_part']), _ptr(plan['ku_ptr']), _ptr(plan['ku_idx']),
+                _ptr(plan['ku_val']), _ptr(plan['ku_diag']), _ptr(plan['ki_ptr']), _ptr(plan['ki_idx']), _ptr(plan['ki_val']),
+                _ptr(plan['ki_diag']), _ptr(PS), PS.stride(0), _ptr(QS), QS.stride(0), float(eta), float(lambd),
+                self._PMF_ADJUST[adjust], _ptr(SP), SP.stride(0) if adjust else 0, _ptr(SQ), SQ.stride(0) if adjust else 0,
+                float(gamma), float(smoothing), _ptr(work), _ptr(out)), 'pk_kpmf_epoch_f64')
         return out
 
     # ---- Bayesian personalised ranking (csrc/bpr.hip) -------------------------------------------------------------------

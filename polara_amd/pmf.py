@@ -9,8 +9,9 @@ permuted list of interactions (`block_schedule`), and B = 1 is the reference's o
 the samples — another, equally valid, SGD trajectory; `blocks` is a parameter of the model like `seed`.
 
 The sweep itself is csrc/pmf.hip (one launch per stratum, one double — the epoch's squared error — read back per epoch).
-Single process.  Not here: KernelizedPMF (its transform reads other rows of P and Q, so the blocks of a stratum are no longer
-independent) and the `adam` adjustment (`beta ** t` per row is not correctly rounded on either side)."""
+Single process.  KernelizedPMF — its transform reads other rows of P and Q, so the blocks of a stratum are no longer
+independent — is polara_amd/kpmf.py, on this module's schedule and epoch loop.  Not here: the `adam` adjustment
+(`beta ** t` per row is not correctly rounded on either side)."""
 import math
 from timeit import default_timer as timer
 
@@ -83,7 +84,7 @@ def schedule_stats(block_ptr, blocks):
                 longest_block=int(lengths.max()) if len(lengths) else 0)
 
 
-def adjuster_name(adjust_gradient):
+def adjuster_name(adjust_gradient, what='PMF'):
     """None, 'adagrad' or 'rmsprop' of what `build` was given: None, one of the names, or a callable called so (the
     reference's function objects; its `identity` is None).  Everything else is not implemented, and says what was asked."""
     if adjust_gradient is None:
@@ -93,8 +94,8 @@ def adjuster_name(adjust_gradient):
         return name
     if name == 'identity' and callable(adjust_gradient):
         return None
-    raise NotImplementedError('PMF: the gradient adjustment %r is not implemented (None, %s)'
-                              % (name if name is not None else adjust_gradient, ', '.join(repr(a) for a in ADJUSTERS)))
+    raise NotImplementedError('%s: the gradient adjustment %r is not implemented (None, %s)'
+                              % (what, name if name is not None else adjust_gradient, ', '.join(repr(a) for a in ADJUSTERS)))
 
 
 def initial_factors(n_users, n_items, rank, seed=None):
@@ -105,30 +106,31 @@ def initial_factors(n_users, n_items, rank, seed=None):
     return P0, Q0
 
 
-def pmf_sgd(ops, matrix, rank, lrate, sigma, num_epochs, tol, adjust_gradient=None, adjustment_params=None, seed=None,
-            verbose=False, iter_errors=None, iter_time=None, blocks=None, init=None, stats=None, comm=None):
-    """simple_pmf_sgd / mf_sgd_boilerplate (optimize.py:158-250) on the device.  matrix: the training matrix
-    [n_users x n_items] as an ops-level CSR (canonical: its entries in storage order are the reference's interactions).
-    Returns the DEVICE blocks (P, Q).  `adjustment_params` is accepted and unused, as in the reference, whose boilerplate
-    replaces it by the zeroed state before every epoch.  init = (P0, Q0) host arrays instead of the seeded draw."""
+def sgd_epochs(ops, what, matrix, rank, lrate, sigma, num_epochs, tol, make_plan, run_epoch, adjust_gradient=None, seed=None,
+               verbose=False, iter_errors=None, iter_time=None, blocks=None, init=None, stats=None, comm=None):
+    """mf_sgd_boilerplate (optimize.py:158-220) on the device, shared by the sweeps that differ in their plan and their
+    epoch alone (pmf_sgd here, kpmf.kernelized_pmf_sgd): the checks, the initial factors, the adjuster's state zeroed before
+    every epoch, one host read per epoch, the stopping rule.  make_plan(blocks) -> plan; run_epoch(plan, P, Q, lrate, lambd,
+    adjust, state) -> a device tensor of one double.  `what` names the model in the messages.  Returns the DEVICE blocks
+    (P, Q)."""
     if comm is not None and getattr(comm, 'world', 1) > 1:
-        raise NotImplementedError('PMF: multi-process builds are not supported (comm.world = %d)' % comm.world)
-    adjust = adjuster_name(adjust_gradient)
+        raise NotImplementedError('%s: multi-process builds are not supported (comm.world = %d)' % (what, comm.world))
+    adjust = adjuster_name(adjust_gradient, what)
     n_users, n_items = (int(x) for x in matrix.shape)
     rank = int(rank)
     if rank < 1 or rank > ops.pmf_max_rank():
-        raise ValueError('PMF: rank %d outside 1..%d' % (rank, ops.pmf_max_rank()))
+        raise ValueError('%s: rank %d outside 1..%d' % (what, rank, ops.pmf_max_rank()))
     if blocks is None:
         blocks = default_blocks(matrix.nnz, n_users, n_items)
     start = timer()
-    plan = ops.pmf_plan(matrix, blocks)
+    plan = make_plan(blocks)
     plan_time = timer() - start
     if init is None:
         init = initial_factors(n_users, n_items, rank, seed)
     P0, Q0 = (np.asarray(a, dtype=np.float64) for a in init)
     if P0.shape != (n_users, rank) or Q0.shape != (n_items, rank):
-        raise ValueError('PMF: initial factors of shapes %s, %s for (%d x %d), (%d x %d)'
-                         % (P0.shape, Q0.shape, n_users, rank, n_items, rank))
+        raise ValueError('%s: initial factors of shapes %s, %s for (%d x %d), (%d x %d)'
+                         % (what, P0.shape, Q0.shape, n_users, rank, n_items, rank))
     P, Q = ops.to_device(np.ascontiguousarray(P0)), ops.to_device(np.ascontiguousarray(Q0))
     state = (ops.empty(n_users, rank), ops.empty(n_items, rank)) if adjust else None
     lambd = 0.5 * sigma ** 2
@@ -141,7 +143,7 @@ def pmf_sgd(ops, matrix, rank, lrate, sigma, num_epochs, tol, adjust_gradient=No
         if state is not None:
             state[0].zero_()
             state[1].zero_()
-        sse = ops.pmf_epoch(plan, P, Q, lrate, lambd, adjust=adjust, state=state, gamma=RMSPROP_GAMMA, smoothing=SMOOTHING)
+        sse = run_epoch(plan, P, Q, lrate, lambd, adjust, state)
         new_err = float(sse[0].item())                      # the epoch's one host read
         training_time.append(timer() - start)
         epochs += 1
@@ -159,6 +161,19 @@ def pmf_sgd(ops, matrix, rank, lrate, sigma, num_epochs, tol, adjust_gradient=No
     if stats is not None:
         stats.update(schedule_stats(ops.to_host(plan['block_ptr']), plan['blocks']), epochs=epochs, plan_time=plan_time)
     return P, Q
+
+
+def pmf_sgd(ops, matrix, rank, lrate, sigma, num_epochs, tol, adjust_gradient=None, adjustment_params=None, seed=None,
+            verbose=False, iter_errors=None, iter_time=None, blocks=None, init=None, stats=None, comm=None):
+    """simple_pmf_sgd / mf_sgd_boilerplate (optimize.py:158-250) on the device.  matrix: the training matrix
+    [n_users x n_items] as an ops-level CSR (canonical: its entries in storage order are the reference's interactions).
+    Returns the DEVICE blocks (P, Q).  `adjustment_params` is accepted and unused, as in the reference, whose boilerplate
+    replaces it by the zeroed state before every epoch.  init = (P0, Q0) host arrays instead of the seeded draw."""
+    def run_epoch(plan, P, Q, eta, lambd, adjust, state):
+        return ops.pmf_epoch(plan, P, Q, eta, lambd, adjust=adjust, state=state, gamma=RMSPROP_GAMMA, smoothing=SMOOTHING)
+    return sgd_epochs(ops, 'PMF', matrix, rank, lrate, sigma, num_epochs, tol, lambda b: ops.pmf_plan(matrix, b), run_epoch,
+                      adjust_gradient=adjust_gradient, seed=seed, verbose=verbose, iter_errors=iter_errors, iter_time=iter_time,
+                      blocks=blocks, init=init, stats=stats, comm=comm)
 
 
 class ProbabilisticMF(FactorQueriesMixin, RecommenderModel):
@@ -188,22 +203,28 @@ class ProbabilisticMF(FactorQueriesMixin, RecommenderModel):
     def _clean_metadata(self):
         self._factors_dev = None
 
+    _device_optimizer = staticmethod(pmf_sgd)
+
+    def _solve(self, ops, train, **config):
+        """the optimizer's call: (P, Q) on the device"""
+        return pmf_sgd(ops, train, self.rank, self.learn_rate, self.sigma, self.num_epochs, self.tolerance, **config)
+
     def build(self, adjust_gradient=None, adjustment_params=None):
         self._require_single_process_build()
-        if self.optimizer is not pmf_sgd:
-            raise NotImplementedError('%s: the optimizer %r is not implemented (only the device sweep, polara_amd.pmf.pmf_sgd)'
-                                      % (self.method, getattr(self.optimizer, '__name__', self.optimizer)))
-        adjuster_name(adjust_gradient)                          # refused before any work
+        if self.optimizer is not self._device_optimizer:
+            raise NotImplementedError('%s: the optimizer %r is not implemented (only the device sweep, polara_amd.%s.%s)'
+                                      % (self.method, getattr(self.optimizer, '__name__', self.optimizer),
+                                         self._device_optimizer.__module__.rsplit('.', 1)[-1], self._device_optimizer.__name__))
+        adjuster_name(adjust_gradient, self.method)             # refused before any work
         ops = self.ops
         train = self._training_device_csr()
         self.rmse_history = []
         self.iterations_time = []
         stats = {}
         start = timer()
-        P, Q = pmf_sgd(ops, train, self.rank, self.learn_rate, self.sigma, self.num_epochs, self.tolerance,
-                       adjust_gradient=adjust_gradient, adjustment_params=adjustment_params, seed=self.seed,
-                       verbose=self.show_rmse, iter_errors=self.rmse_history, iter_time=self.iterations_time,
-                       blocks=self.blocks, stats=stats)
+        P, Q = self._solve(ops, train, adjust_gradient=adjust_gradient, adjustment_params=adjustment_params, seed=self.seed,
+                           verbose=self.show_rmse, iter_errors=self.rmse_history, iter_time=self.iterations_time,
+                           blocks=self.blocks, stats=stats)
         ops.synchronize()
         self._track(start)
         self.build_stats = stats
