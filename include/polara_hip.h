@@ -332,6 +332,34 @@ int pk_score_candidates_rows_bound_f32(void *stream, int64_t n_users, int64_t n_
                                        int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk /* 0 = auto */,
                                        const float *tile_bound_dev /* or NULL */, const uint32_t *seen_dense_dev,
                                        const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev);
+/* ... and the settle rule of the first re-scoring (pk_rescore_topk_rows_settle_f64) applied where a group of 32 users LEAVES the
+ * sweep, to the final sorted lists the wave still holds: single sweep (one list per user), KC = 16 or 32, pruning bound and
+ * error weights (extra_dev) required.  A user whose order the sweep's own scores decide is SETTLED: its topk ids go to row u
+ * of out_idx (row out_perm[u] when given), flags[u] = 8, and its row of cand_score / cand_idx is NOT written (stale).  Every
+ * other user keeps its candidate row and is appended to open_list (int32 [n_users], arbitrary order) behind the device
+ * counter open_count, which the caller zeroes in front of the sweep (pk_zero_i32, or pk_fold_q20_zero).  The first re-scoring
+ * then takes open_list / open_count as its row list; the settled set, the flags and the lists are those of the tier in the
+ * re-scoring kernel.  pk_sweep_settles(KC): 1 when a host layer should take this route — KC fits and the options
+ * "sweep_settle" and "rescore_settle" (pk_set_option, default 1) are on; the entry itself settles whenever it is called. */
+typedef struct PkSweepSettle {
+    int32_t topk;
+    double vmax;                 /* v_row_norm_max of the re-scoring entries */
+    const float *item_norm;      /* float [n_items] upper bounds of the item rows' norms, or NULL */
+    int64_t *out_idx;            /* [n_users x topk] */
+    const int64_t *out_perm;     /* [n_users] or NULL */
+    int32_t *flags;              /* [n_users] */
+    int32_t *open_list;          /* [n_users] */
+    int32_t *open_count;         /* [1], zero at the start of the sweep */
+} PkSweepSettle;
+int pk_sweep_settles(int32_t KC);
+int pk_score_candidates_rows_settle_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                                        const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
+                                        double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
+                                        const int32_t *seen_ntiles_dev, int32_t KC, float *cand_score_dev,
+                                        int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk /* 0 = auto */,
+                                        const float *tile_bound_dev, const uint32_t *seen_dense_dev,
+                                        const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev /* or NULL */,
+                                        const PkSweepSettle *settle);
 /* The pruned sweep in TWO PHASES (replaces the same reference lines: the chunk loop body of models.py:359-371, with
  * downvote_seen_items :494-519 and topsort :488-491 fused in).  A launch of the single sweep lasts as long as its slowest
  * wave — the groups of the heaviest users stay ~270 tiles in the sweep, everybody else 70-130 — so the catalogue is

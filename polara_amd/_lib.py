@@ -15,6 +15,13 @@ PK_PMF_MAX_BLOCKS = 4096      # include/polara_hip.h
 
 _vp, _i32, _i64, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 
+
+class PkSweepSettle(C.Structure):
+    """the settle block of pk_score_candidates_rows_settle_f32 (include/polara_hip.h)"""
+    _fields_ = [('topk', _i32), ('vmax', _f64), ('item_norm', _vp), ('out_idx', _vp), ('out_perm', _vp), ('flags', _vp),
+                ('open_list', _vp), ('open_count', _vp)]
+
+
 # name -> (restype, argtypes); mirrors include/polara_hip.h one to one
 PROTOTYPES = {
     'pk_last_error': (C.c_char_p, []),
@@ -79,6 +86,9 @@ PROTOTYPES = {
                                               _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32]),
     'pk_score_candidates_rows_bound_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _i32, _i32,
                                                      _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    'pk_sweep_settles': (C.c_int, [_i32]),
+    'pk_score_candidates_rows_settle_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _i32,
+                                                      _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, C.POINTER(PkSweepSettle)]),
     'pk_score_two_phase_rows_bound_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _i32, _i32,
                                                     _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
     'pk_score_two_phase_plan': (C.c_int, [_i64, _i64, _i32, _vp, _vp]),

@@ -18,7 +18,7 @@ extern "C" const char *pk_last_error(void) { return g_err; }
 namespace {
 struct Option { const char *name; std::atomic<int> value; std::atomic<bool> set; };
 Option g_options[] = {{"score_boot_tiles", {0}, {false}}, {"score_head_tiles", {0}, {false}}, {"score_phase2_splits", {0}, {false}},
-                      {"rescore_settle", {0}, {false}}};
+                      {"rescore_settle", {0}, {false}}, {"sweep_settle", {0}, {false}}};
 }
 int pk_option(const char *name, int dflt) {
     for (auto &o : g_options)

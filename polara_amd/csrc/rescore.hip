@@ -10,43 +10,11 @@
 // provably the exact one, else the user is flagged and re-done by score_exact_rows (all items,
 // fp64, two-class key = the reference's downvote_seen_items semantics, models.py:510-519).
 #include "pk_common.h"
+#include "pk_settle.h"   // pk_bitonic_seg, pk_sweep_err_coeff, PK_FLAG_SETTLED: shared with the sweep's exit (score.hip)
 #include <math.h>
 #include <stdlib.h>
 #include <mutex>
 #include <unordered_map>
-
-#define PK_IDX_NONE 0x7fffffff
-
-__device__ __forceinline__ bool pk_before64(double ka, int va, double kb, int vb) {
-    return (ka > kb) || (ka == kb && va < vb);
-}
-
-// bitonic sort (descending by pk_before64) inside aligned segments of SEG lanes, one (key, val) per lane
-// LPC: lanes per element (the LPC adjacent lanes of a candidate hold identical copies and perform identical
-// exchanges, so the network runs on all lanes with partners LPC * J lanes away)
-template <int SEG, int K, int J, int LPC>
-__device__ __forceinline__ void pk_bitonic_seg_merge(double &key, int &val, int t) {
-    const double ok = pk_lane_xor<J * LPC>(key);
-    const int ov = pk_lane_xor<J * LPC>(val);
-    const bool lower = (t & J) == 0;
-    const bool desc = (t & K) == 0;   // t < SEG: the last level (K == SEG) is descending everywhere
-    const bool want_first = (lower == desc);
-    const bool other_first = pk_before64(ok, ov, key, val);
-    if (want_first == other_first) {
-        key = ok;
-        val = ov;
-    }
-    if constexpr (J > 1) pk_bitonic_seg_merge<SEG, K, (J >> 1), LPC>(key, val, t);
-}
-template <int SEG, int K, int LPC>
-__device__ __forceinline__ void pk_bitonic_seg_levels(double &key, int &val, int t) {
-    if constexpr (K > 2) pk_bitonic_seg_levels<SEG, (K >> 1), LPC>(key, val, t);
-    pk_bitonic_seg_merge<SEG, K, (K >> 1), LPC>(key, val, t);
-}
-template <int SEG, int LPC>
-__device__ __forceinline__ void pk_bitonic_seg(double &key, int &val, int t) {
-    pk_bitonic_seg_levels<SEG, SEG, LPC>(key, val, t);
-}
 
 // ---- the ONE summation order of every exact fp64 score in this file ---------------------------------
 // The K products are dealt to four chains by element PAIR: pair p = (2p, 2p+1) goes to chain p & 3, each
@@ -176,17 +144,6 @@ __device__ __forceinline__ double pk_dot_f32row(const float *__restrict__ vr, co
     return s;
 }
 
-// The sweep's split-bf16 product (score.hip): |s32 - e.v| <= pk_sweep_err_coeff(K) |e||v| — operands split into two bf16
-// each, the lo.lo term dropped, fp32 conversion of the inputs, accumulation roundings.  ONE definition: the certification
-// against the sweep's threshold and the settle tier (below) both stand on it.
-__device__ __forceinline__ double pk_sweep_err_coeff(int K) {
-    return 3.0 * 1.52587890625e-05 + (double)(4 * K + 10) * 1.1920928955078125e-07;
-}
-
-// flags[u] of a user the settle tier finished (rescore_topk_kernel): above the mask 7 of the lists of users to re-do, so
-// nobody re-does them — the bit only lets a caller COUNT them afterwards (no counter in the kernel)
-#define PK_FLAG_SETTLED 8
-
 // LPC adjacent lanes own one candidate: they walk the candidate's item row in interleaved 16-byte pieces
 // (the candidates of a user are popular items, their rows sit in L2) against the user's E row with serial
 // fp64 FMA chains and add their LPC partial sums at the end (one or two lane exchanges); a segment of
@@ -263,11 +220,10 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
         }
         // (the sweep's lists are ordered by key-only flush sorts: out of order by 2^-16 relative, and S of them per user)
         pk_bitonic_seg<SEG, LPC>(ts, ti, t);
-        const double c = pk_sweep_err_coeff(K) * (double)user_norm[user] +
-                         e_err[urow * e_err_ld] * 5.9604644775390625e-08 * (1.0 + 1e-6);
+        const double c = pk_settle_coeff(K, user_norm[user], e_err[urow * e_err_ld]);
         const double d_max = c * vmax;
         double d_me = d_max;
-        if (item_norm && ti != PK_IDX_NONE) d_me = c * fmin(vmax, (double)item_norm[ti] * (1.0 + 1e-6));
+        if (item_norm && ti != PK_IDX_NONE) d_me = pk_settle_item_err(c, vmax, item_norm[ti]);
         const int nxt_lane = lane + LPC, k_lane = (ul * SEG + topk - 1) * LPC;
         // (every lane takes part in the exchanges; the last slot of a segment then drops what it fetched from its neighbour)
         const double s_nb = __shfl(ts, nxt_lane & 63, 64), d_nb = __shfl(d_me, nxt_lane & 63, 64);
@@ -276,7 +232,7 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
         const double s_kk = __shfl(ts, k_lane, 64), d_kk = __shfl(d_me, k_lane, 64);
         // (an empty slot holds -inf: below everything at any bound; a list shorter than topk compares -inf with -inf: NaN, open)
         bool open = (t < topk) ? !(ts - s_next > d_me + d_next) : !(s_kk - ts > d_kk + d_me);
-        if (tau32 > -INFINITY) open = open || !(s_kk - (tau32 + fabs(tau32) * 3.0517578125e-05) > d_kk + d_max);
+        if (tau32 > -INFINITY) open = open || !(s_kk - pk_settle_tau_cert(tau32) > d_kk + d_max);
         open = open || unbounded || (n_items - n_seen < topk) || !live;
         const unsigned long long ob = __ballot(open);
         const unsigned long long seg_mask = (SEG * LPC == 64) ? ~0ull : (((1ull << (SEG * LPC)) - 1ull) << (ul * SEG * LPC));

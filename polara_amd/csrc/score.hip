@@ -34,6 +34,7 @@
 // 5-7 bits of the score: a tau refreshed later can be smaller by up to 2^-16 relative than an earlier one,
 // and a dropped item can exceed it by as much — the re-scoring kernel's certification allows for 2^-15.
 #include "pk_common.h"
+#include "pk_settle.h"   // the settle rule shared with the re-scoring kernel (rescore.hip)
 #include <math.h>
 #include <stdlib.h>
 
@@ -42,7 +43,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #define RING 16          // lane-private candidate ring entries (8 for KC == 16, see PAIRED below)
 
-#define PK_IDX_NONE 0x7fffffff
 #define PK_IDX_FLOOR (-2)       // last slot of a list: "not full although the sweep started from a threshold" (see the kernel's end)
 #define PK_TILE_NONE 0xffffffff00000000ull   // end of a seen-tile stream
 
@@ -192,12 +192,44 @@ struct UserRows {
                         // for the settle tier of the re-scoring kernel (rescore.hip), which must not read the row to get one
 };
 
+// SETTLE instances (single sweep, lists in LDS, KC <= 32): what a wave does with its 32 final lists when it leaves the sweep.
+// The settle rule of the first re-scoring (pk_settle.h, rescore_topk_kernel's tier) needs the sweep's scores, the users' bounds
+// and the items' norm bounds — all at hand here: a user whose order the sweep's scores decide gets its ids written to out_idx
+// (row out_perm[u] when given) and flags[u] = PK_FLAG_SETTLED, and its candidate list is NOT written; every other live user
+// is appended to open_list (one atomicAdd per wave; the order of the list is arbitrary) and its list is written as always.
+struct SettleExit {
+    int topk;
+    double vmax;
+    const float *item_norm;     // float [n_items] or NULL (every item at vmax)
+    int64_t *out_idx;
+    const int64_t *out_perm;    // or NULL
+    int32_t *flags;
+    int32_t *open_list;         // int32 [n_users]
+    int32_t *open_count;        // zeroed by the caller
+};
+
+// What the exit block reads of the kernel's arguments.  Scalar registers are what the tile loop is shortest of (97 of 102 in
+// the plain instance): arguments that stay live through it for the sake of the exit block were spilled to VGPR lanes and
+// read back INSIDE the loop.  So the wave parks them in 128 bytes of LDS behind its lists before the loop and fetches them
+// back, through an offset the compiler cannot see through, when it leaves: the loop keeps the plain instance's allocation.
+struct ExitCtx {
+    SettleExit sx;
+    const int64_t *seen_ptr;
+    const double *extra;
+    int64_t extra_ld;
+    int64_t n_users;
+    int K;
+};
+#define PK_EXIT_CTX_BYTES 128
+static_assert(sizeof(ExitCtx) <= PK_EXIT_CTX_BYTES, "ExitCtx: one 128-byte LDS slot per wave");
+__host__ __device__ constexpr size_t pk_score_settle_lds_bytes(int nstep, int kc) { return pk_score_lds_bytes(nstep, kc) + 4 * PK_EXIT_CTX_BYTES; }
+
 // DENSE: the instance that reads them (the other one is the kernel as it was: in the throughput-bound regimes — full
 // sweeps, rank 200 — the extra registers and per-tile tests of a run-time switch cost 10 %).
 // (The LDS-staged forms of this sweep — 16- and 4-wave workgroups stepping through the tiles together — the two-groups-per-wave
 // kernel and the two-buffer / depth-2 / two-chain tile loops were built, verified and measured slower or mixed in rounds 3-4:
 // they live in csrc/experiments/score_variants.hip with their records in profiles/ and DESIGN.md K3, not in the product library.)
-template <int NSTEP, int KC, bool STRIDED, bool DENSE>
+template <int NSTEP, int KC, bool STRIDED, bool DENSE, bool SETTLE = false>
 __global__ __launch_bounds__(256) void score_candidates_kernel(
     const float4 *__restrict__ Vp, const float4 *__restrict__ Ep, int64_t n_users, int n_items,
     int n_tiles, int split_tiles, int chunk_begin, int chunk_tiles,
@@ -206,7 +238,7 @@ __global__ __launch_bounds__(256) void score_candidates_kernel(
     float *__restrict__ cand_score, int32_t *__restrict__ cand_idx,
     LaneState *__restrict__ st_lane, uint2 *__restrict__ st_ring,
     const float *__restrict__ user_bound, const float *__restrict__ tile_bound, SeenDense dense,
-    int tile_base, int slot_base, const LaneState *__restrict__ floor_state, int boot_tiles, UserRows rows) {
+    int tile_base, int slot_base, const LaneState *__restrict__ floor_state, int boot_tiles, UserRows rows, SettleExit sx) {
     constexpr int KQ = 2 * NSTEP;   // 16-byte groups per lane and tile: (hi, lo) x 8 bf16 for every 16-wide k-step
     // KC == 16: rings of 8, so that a user's list + both rings are 32 entries and TWO users are merged
     // per flush, one in each half of the wave (15 sort stages per two users instead of 21 per user).
@@ -229,6 +261,18 @@ __global__ __launch_bounds__(256) void score_candidates_kernel(
     const int64_t group = group_raw;
     uint2(*ring)[64] = reinterpret_cast<uint2(*)[64]>(pk_score_lds + wave * (RG * 64));
     uint2 *top = pk_score_lds + NW * RG * 64 + (TOP_LDS ? wave * (32 * KC) : 0);
+    constexpr int CTX_AT = NW * RG * 64 + NW * 32 * KC;      // (SETTLE: uint2 index of the waves' ExitCtx slots, behind the lists)
+    if constexpr (SETTLE) {
+        if (lane == 0) {
+            ExitCtx *cx = reinterpret_cast<ExitCtx *>(pk_score_lds + CTX_AT + wave * (PK_EXIT_CTX_BYTES / 8));
+            cx->sx = sx;
+            cx->seen_ptr = seen_ptr;
+            cx->extra = rows.extra;
+            cx->extra_ld = rows.extra_ld;
+            cx->n_users = n_users;
+            cx->K = rows.K;
+        }
+    }
 
     // Item split: blockIdx.y = h of S = gridDim.y owns every S-th tile of the catalogue, h, h+S, h+2S, ...
     // (`split_tiles` = ceil(n_tiles / S) of them at most), with its own threshold, rings, top lists and parked
@@ -927,9 +971,104 @@ __global__ __launch_bounds__(256) void score_candidates_kernel(
     // non-candidate scores at most the KC-th entry" would silently not hold — the last slot says so (PK_IDX_FLOOR) and
     // the re-scoring kernel sends the user to the exact path.
     const unsigned long long floored = (floor_state == nullptr) ? __ballot(tau_floor > -INFINITY) : 0ull;   // bit x: user x
+    unsigned settled_users = 0u;      // bit x: user x of the group leaves settled (SETTLE instances)
+    if constexpr (SETTLE) {
+        static_assert(TOP_LDS && !STRIDED && (KC == 16 || KC == 32), "settle at exit: single sweep, lists in LDS, KC <= 32");
+        // A segment of KC lanes per user, 64 / KC users per pass: the arithmetic of rescore_topk_kernel's tier, user by user.
+        constexpr int UPP = 64 / KC;
+        // (nothing of this block may stay in a register through the tile loop — the loop's allocation is the plain instance's:
+        // lane, group and user are derived afresh, the arguments come back from the wave's LDS slot (ExitCtx), and the user's
+        // bound is `en`, which the pruning test keeps anyway: with the pruning on, as the entry requires, en == en_rows for
+        // every live user)
+        const int sl = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        int cx_at = CTX_AT + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * (PK_EXIT_CTX_BYTES / 8);
+        asm volatile("" : "+s"(cx_at));
+        __builtin_amdgcn_wave_barrier();
+        const ExitCtx cx = *reinterpret_cast<const ExitCtx *>(pk_score_lds + cx_at);
+        const SettleExit &sx = cx.sx;        // (shadows the kernel argument from here on)
+        const int64_t n_users = cx.n_users;
+        const int64_t sgroup = (int64_t)blockIdx.x * NW + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        const int su = sl & 31;
+        const int64_t suser = sgroup * 32 + su;
+        const int t = sl % KC, seg = sl / KC;
+        // what the rule needs of a user, fetched once by the user's own lane: coefficient, unseen count, output row
+        double c_own = 0.0;
+        int can_own = 0;              // (a padding lane stays open)
+        int64_t irow_own = 0;
+        if (suser < n_users) {
+            c_own = pk_settle_coeff(cx.K, en, cx.extra[suser * cx.extra_ld]);
+            const int64_t n_seen = cx.seen_ptr ? cx.seen_ptr[suser + 1] - cx.seen_ptr[suser] : 0;
+            can_own = (n_items - n_seen >= sx.topk) ? 1 : 0;
+            irow_own = sx.out_perm ? sx.out_perm[suser] : suser;
+        }
+        // the norm bounds of all 32 * KC list entries in one batch of gathers, parked in the ring area (the final flush has
+        // emptied the rings: their 8 * RG * 64 bytes hold the 4 * 32 * KC)
+        static_assert((size_t)RG * 64 * sizeof(uint2) >= (size_t)32 * KC * sizeof(float), "norms fit the ring area");
+        float *nrm = reinterpret_cast<float *>(&ring[0][0]);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int i = 0; i < KC / 2; ++i) {
+            const int iv = (int)top[sl + 64 * i].y;
+            nrm[sl + 64 * i] = (sx.item_norm && iv >= 0) ? sx.item_norm[iv] : 0.0f;
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+        for (int p = 0; p < 32 / UPP; ++p) {
+            const int x = p * UPP + seg;                       // the user of my segment
+            const uint2 r = top[x * KC + t];
+            const uint2 rl = top[x * KC + KC - 1];             // last slot in the sweep's own order: its score bounds what the sweep left out
+            float n_me = nrm[x * KC + t];
+            double ts = -INFINITY;
+            int ti = PK_IDX_NONE;
+            if ((int)r.y >= 0) {
+                ts = (double)__uint_as_float(r.x);
+                ti = (int)r.y;
+            }
+            const double tau32 = ((int)rl.y >= 0) ? (double)__uint_as_float(rl.x) : -INFINITY;
+            const bool unbounded = (int)rl.y < 0 && ((floored >> x) & 1ull);     // what the copy below marks PK_IDX_FLOOR
+            // (the lists are ordered by key-only flush sorts: out of order by 2^-16 relative)
+            pk_bitonic_seg<KC, 1>(ts, ti, t, n_me);
+            // (every lane takes part in the exchanges)
+            const double c = __shfl(c_own, x, 64);
+            const int can = __shfl(can_own, x, 64);
+            const long long irow = __shfl((long long)irow_own, x, 64);
+            const double d_max = c * sx.vmax;
+            double d_me = d_max;
+            if (sx.item_norm && ti != PK_IDX_NONE) d_me = pk_settle_item_err(c, sx.vmax, n_me);
+            const int k_lane = seg * KC + sx.topk - 1;
+            const double s_nb = __shfl(ts, (sl + 1) & 63, 64), d_nb = __shfl(d_me, (sl + 1) & 63, 64);
+            const double s_next = (t + 1 < KC) ? s_nb : -INFINITY;
+            const double d_next = (t + 1 < KC) ? d_nb : d_max;
+            const double s_kk = __shfl(ts, k_lane, 64), d_kk = __shfl(d_me, k_lane, 64);
+            // (an empty slot holds -inf: below everything at any bound; a list shorter than topk compares -inf with -inf: NaN, open)
+            bool open = (t < sx.topk) ? !(ts - s_next > d_me + d_next) : !(s_kk - ts > d_kk + d_me);
+            if (tau32 > -INFINITY) open = open || !(s_kk - pk_settle_tau_cert(tau32) > d_kk + d_max);
+            open = open || unbounded || !can;
+            const unsigned long long ob = __ballot(open);
+            constexpr unsigned long long SEG_ONES = (1ull << KC) - 1ull;
+            if (((ob >> (seg * KC)) & SEG_ONES) == 0ull) {
+                if (t < sx.topk) sx.out_idx[irow * sx.topk + t] = (ti == PK_IDX_NONE) ? -1 : (int64_t)ti;
+                if (t == 0) sx.flags[sgroup * 32 + x] = PK_FLAG_SETTLED;
+            }
+#pragma unroll
+            for (int g = 0; g < UPP; ++g)
+                if (((ob >> (g * KC)) & SEG_ONES) == 0ull) settled_users |= 1u << (p * UPP + g);
+        }
+        // the users that stay open: one atomicAdd per wave, the ids behind its base (lanes 0..31 own users 0..31 of the group)
+        const unsigned open_users = (unsigned)__ballot(suser < n_users) & ~settled_users;
+        if (open_users) {
+            int base = 0;
+            if (sl == 0) base = atomicAdd(sx.open_count, __builtin_popcount(open_users));
+            base = __builtin_amdgcn_readfirstlane(base);
+            const int64_t at = (int64_t)base + __builtin_popcount(open_users & ((1u << su) - 1u));
+            // (at < n_users whenever the caller zeroed the counter; the test keeps a forgotten reset inside the list)
+            if (sl < 32 && ((open_users >> su) & 1u) && at >= 0 && at < n_users) sx.open_list[at] = (int32_t)suser;
+        }
+    }
     if (TOP_LDS) {
         __builtin_amdgcn_wave_barrier();
         for (int s = lane; s < 32 * KC; s += 64) {
+            if (SETTLE && ((settled_users >> (s / KC)) & 1u)) continue;     // a settled user's list is not written
             const uint2 r = top[s];
             int iv = (int)r.y;
             if ((s % KC) == KC - 1 && iv < 0 && ((floored >> (s / KC)) & 1ull)) iv = PK_IDX_FLOOR;
@@ -1345,7 +1484,8 @@ static int launch_candidates_n(hipStream_t st, int KC, dim3 grid, const float4 *
                                const int64_t *seen_ptr, const unsigned long long *seen_tiles,
                                const int32_t *seen_ntiles, float *cs, int32_t *ci,
                                LaneState *st_lane, uint2 *st_ring, const float *user_bound, const float *tile_bound,
-                               SeenDense dense, SweepPhase ph, UserRows rows) {
+                               SeenDense dense, SweepPhase ph, UserRows rows, const SettleExit *settle) {
+    const SettleExit sx = settle ? *settle : SettleExit{0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // Item chunks: tiles_per_chunk each while every group sweeps (the chunk's packed image stays in L2);
     // with pruning, groups leave the sweep early, so the chunks DOUBLE from launch to launch — the catalogue
     // is covered in O(log) launches and the few groups still sweeping late (low bandwidth demand) are not
@@ -1377,18 +1517,39 @@ static int launch_candidates_n(hipStream_t st, int KC, dim3 grid, const float4 *
             attr_set.done();                                                                                       \
         }                                                                                                       \
     }                                                                                                           \
-    if (grid.y > 1 || ph.floor_state != nullptr)                                                                \
+    if (settle) {                                                                                               \
+        /* settle at exit: the single sweep with KC <= 32 (checked by the entry); ONE instance per (NSTEP, KC) — without dense   \
+           masks (dn.tiles == 0) the DENSE form lets the stream serve every tile */                                  \
+        if constexpr (KCV <= 32) {                                                                                  \
+            if (pk_score_settle_lds_bytes(NSTEP, KCV) > 64 * 1024) {                                                \
+                static PkDeviceOnce settle_attr_set;                                                                \
+                if (settle_attr_set.pending()) {                                                                    \
+                    const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void *>(&score_candidates_kernel<NSTEP, KCV, false, DENSE_OK, true>), \
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize,           \
+                                                              (int)pk_score_settle_lds_bytes(NSTEP, KCV));          \
+                    if (e1 != hipSuccess) {                                                                         \
+                        pk_set_error("pk_score_candidates_rows_settle_f32: cannot raise the LDS limit: %s", hipGetErrorString(e1)); \
+                        return PK_E_LAUNCH;                                                                         \
+                    }                                                                                               \
+                    settle_attr_set.done();                                                                         \
+                }                                                                                                   \
+            }                                                                                                       \
+            hipLaunchKernelGGL((score_candidates_kernel<NSTEP, KCV, false, DENSE_OK, true>), grid, dim3(256), pk_score_settle_lds_bytes(NSTEP, KCV), st, Vp, Ep, n_users, \
+                               n_items, n_tiles, split_tiles, chunk_begin, chunk_tiles, seen_ptr, seen_tiles, seen_ntiles, cs, ci, st_lane, st_ring,  \
+                               user_bound, tile_bound, dn, 0, ph.slot_base, nullptr, ph.boot_tiles, rows, sx);  \
+        }                                                                                                           \
+    } else if (grid.y > 1 || ph.floor_state != nullptr)                                                         \
         hipLaunchKernelGGL((score_candidates_kernel<NSTEP, KCV, true, DENSE_OK>), grid, dim3(256), pk_score_lds_bytes(NSTEP, KCV), st, Vp, Ep, n_users, \
                            n_items, n_tiles, split_tiles, chunk_begin, chunk_tiles, seen_ptr, seen_tiles, seen_ntiles, cs, ci, st_lane, st_ring,  \
-                           user_bound, tile_bound, dn, ph.tile_base, ph.slot_base, ph.floor_state, ph.boot_tiles, rows); \
+                           user_bound, tile_bound, dn, ph.tile_base, ph.slot_base, ph.floor_state, ph.boot_tiles, rows, sx); \
     else if (use_dense)                                                                                         \
         hipLaunchKernelGGL((score_candidates_kernel<NSTEP, KCV, false, DENSE_OK>), grid, dim3(256), pk_score_lds_bytes(NSTEP, KCV), st, Vp, Ep, n_users, \
                            n_items, n_tiles, split_tiles, chunk_begin, chunk_tiles, seen_ptr, seen_tiles, seen_ntiles, cs, ci, st_lane, st_ring,  \
-                           user_bound, tile_bound, dn, 0, ph.slot_base, nullptr, ph.boot_tiles, rows);  \
+                           user_bound, tile_bound, dn, 0, ph.slot_base, nullptr, ph.boot_tiles, rows, sx);  \
     else                                                                                                        \
         hipLaunchKernelGGL((score_candidates_kernel<NSTEP, KCV, false, false>), grid, dim3(256), pk_score_lds_bytes(NSTEP, KCV), st, Vp, Ep, n_users, \
                            n_items, n_tiles, split_tiles, chunk_begin, chunk_tiles, seen_ptr, seen_tiles, seen_ntiles, cs, ci, st_lane, st_ring,  \
-                           user_bound, tile_bound, no_dense, 0, ph.slot_base, nullptr, ph.boot_tiles, rows)
+                           user_bound, tile_bound, no_dense, 0, ph.slot_base, nullptr, ph.boot_tiles, rows, sx)
         switch (KC) {
             case 16:
                 PK_LAUNCH(16);
@@ -1462,7 +1623,7 @@ static int pk_sweep_launches(hipStream_t st, int64_t n_users, int64_t n_items, i
                              const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits, int32_t total_slots,
                              float *cand_score_dev, int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
                              const float *user_bound_dev, const float *tile_bound_dev, SeenDense dense, SweepPhase ph,
-                             UserRows rows = UserRows{nullptr, 0, 0, nullptr, 0, 0.0, nullptr}) {
+                             UserRows rows = UserRows{nullptr, 0, 0, nullptr, 0, 0.0, nullptr}, const SettleExit *settle = nullptr) {
     const int kq = pk_pack_kq(K);
     const int nstep = pk_nstep(K);
     const int64_t groups = pk_ceil_div(n_users, 32);
@@ -1483,7 +1644,7 @@ static int pk_sweep_launches(hipStream_t st, int64_t n_users, int64_t n_items, i
                                     split_tiles, tiles_per_chunk, seen_ptr_dev,                                   \
                                     reinterpret_cast<const unsigned long long *>(seen_tiles_dev), seen_ntiles_dev, \
                                     cand_score_dev, cand_idx_dev,                                              \
-                                    st_lane, st_ring, user_bound_dev, tile_bound_dev, dense, ph, rows);        \
+                                    st_lane, st_ring, user_bound_dev, tile_bound_dev, dense, ph, rows, settle); \
         break;
     switch (nstep) {
         PK_N_CASE(1)
@@ -1534,7 +1695,7 @@ static int pk_score_candidates_impl(const char *who, void *stream, int64_t n_use
                                     const uint64_t *seen_tiles_dev, const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits,
                                     float *cand_score_dev, int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
                                     const float *user_bound_dev, const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                    const int32_t *seen_skip_dev, int32_t dense_tiles) {
+                                    const int32_t *seen_skip_dev, int32_t dense_tiles, const SettleExit *settle = nullptr) {
     const int rc = pk_score_check_args(who, n_users, n_items, K, Vp_dev, Ep_dev, seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev,
                                        state_dev, user_bound_dev, tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles, rows);
     if (rc != PK_OK) return rc;
@@ -1543,7 +1704,7 @@ static int pk_score_candidates_impl(const char *who, void *stream, int64_t n_use
     return pk_sweep_launches(pk_stream(stream), n_users, n_items, (int)pk_ceil_div(n_items, 32), K, Vp_dev, Ep_dev,
                              seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, splits, splits, cand_score_dev, cand_idx_dev,
                              state_dev, tiles_per_chunk, user_bound_dev, tile_bound_dev, dense, SweepPhase{0, 0, nullptr, 0},
-                             rows ? *rows : UserRows{nullptr, 0, 0, nullptr, 0, 0.0, nullptr});
+                             rows ? *rows : UserRows{nullptr, 0, 0, nullptr, 0, 0.0, nullptr}, settle);
 }
 
 extern "C" int pk_score_candidates_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K,
@@ -1590,6 +1751,39 @@ extern "C" int pk_score_candidates_rows_f32(void *stream, int64_t n_users, int64
                                               seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, splits, cand_score_dev, cand_idx_dev,
                                               state_dev, tiles_per_chunk, tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles,
                                               nullptr);
+}
+
+// 1: a single pruned sweep with this many candidates can settle its clear-cut users when they leave the sweep
+// (pk_score_candidates_rows_settle_f32) — lists in LDS (KC <= 32) and both options on: pk_set_option("sweep_settle", 0)
+// sends a pass back to the tier of the first re-scoring, "rescore_settle" = 0 switches the rule off wherever it runs
+extern "C" int pk_sweep_settles(int32_t KC) {
+    return (KC == 16 || KC == 32) && pk_option("sweep_settle", 1) && pk_option("rescore_settle", 1);
+}
+
+// The single pruned sweep from the rows of E (pk_score_candidates_rows_bound_f32 with splits = 1) that applies the settle rule
+// of the first re-scoring to a group's final lists when the group leaves the sweep: see PkSweepSettle (polara_hip.h) and
+// SettleExit above.  The first re-scoring then runs on open_list / open_count (pk_rescore_topk_rows_*: a row list, tier off).
+extern "C" int pk_score_candidates_rows_settle_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                                                   const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
+                                                   double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
+                                                   const int32_t *seen_ntiles_dev, int32_t KC, float *cand_score_dev,
+                                                   int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
+                                                   const float *tile_bound_dev, const uint32_t *seen_dense_dev,
+                                                   const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev,
+                                                   const PkSweepSettle *settle) {
+    const char *who = "pk_score_candidates_rows_settle_f32";
+    PK_REQUIRE(settle != nullptr && (KC == 16 || KC == 32), "%s: needs the settle block and KC = 16 or 32", who);
+    PK_REQUIRE(n_users >= 1 && n_users <= 0x7fffffffLL, "%s: user ids must fit the int32 open list", who);
+    PK_REQUIRE(tile_bound_dev != nullptr && extra_dev != nullptr && extra_ld >= 1,
+               "%s: needs the pruning bound and the fold-in's error weights", who);
+    PK_REQUIRE(settle->topk >= 1 && settle->topk <= KC && settle->vmax >= 0.0, "%s: need 1 <= topk <= KC", who);
+    PK_REQUIRE(settle->out_idx && settle->flags && settle->open_list && settle->open_count, "%s: null outputs", who);
+    const UserRows rows{E_dev, lde, K, extra_dev, extra_ld, extra_scale, user_bound_out_dev};
+    const SettleExit sx{settle->topk, settle->vmax, settle->item_norm, settle->out_idx, settle->out_perm, settle->flags,
+                        settle->open_list, settle->open_count};
+    return pk_score_candidates_impl(who, stream, n_users, n_items, K, Vp_dev, nullptr, &rows, seen_ptr_dev, seen_tiles_dev,
+                                    seen_ntiles_dev, KC, 1, cand_score_dev, cand_idx_dev, state_dev, tiles_per_chunk, nullptr,
+                                    tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles, &sx);
 }
 
 // ---- two-phase sweep -------------------------------------------------------------------------------------------------

@@ -1271,6 +1271,11 @@ class HipOps:
                                                 _ptr(dense), _ptr(skip)), 'pk_seen_dense_build')
         return dense, skip
 
+    def sweep_settles(self, KC):
+        """does a single pruned sweep with KC candidates settle its clear-cut users itself (`score_candidates(settle=)`)?  The
+        library's answer: KC <= 32 and the options "sweep_settle" / "rescore_settle" on."""
+        return bool(self.lib.pk_sweep_settles(int(KC)))
+
     def sweep_takes_rows(self, E):
         """can the candidate sweep read the users' side from these fp64 rows of E (16-byte aligned, even row stride)?  Then
         `score_candidates` / `score_two_phase` take `E_rows=(E, extra, extra_scale)` instead of packed fragments + bounds."""
@@ -1286,11 +1291,16 @@ class HipOps:
         return _ptr(E), E.stride(0), _ptr(extra), int(e_ld), float(scale if extra is not None else 0.0)
 
     def score_candidates(self, Vp, Ep, n_users, n_items, K, seen_ptr, seen_idx, KC, splits=1, tiles_per_chunk=0,
-                         user_bound=None, tile_bound=None, seen_tiles=None, seen_dense=None, E_rows=None, bound_out=None):
+                         user_bound=None, tile_bound=None, seen_tiles=None, seen_dense=None, E_rows=None, bound_out=None,
+                         settle=None):
         """E_rows = (E fp64 [n_users x >= K], extra column or None, extra_scale): the users' fragments and pruning bounds are
         built inside the sweep (pk_score_candidates_rows_f32; Ep and user_bound are not used, tile_bound alone switches the
         pruning on).  bound_out (float32 [n_users], E_rows only): the sweep stores the users' bounds there
-        (pk_score_candidates_rows_bound_f32) — what `rescore_topk` takes as `user_norm`."""
+        (pk_score_candidates_rows_bound_f32) — what `rescore_topk` takes as `user_norm`.
+        settle (E_rows with its extra column, tile_bound, splits == 1, `sweep_settles(KC)`): dict(topk, vmax, item_norm, out_idx,
+        out_perm, flags, open_list, open_count) — the settle rule of the first re-scoring runs where a group leaves the sweep
+        (pk_score_candidates_rows_settle_f32): settled users get their ids and flag 8 there and no candidate row, everybody
+        else is appended to open_list behind the zeroed device counter open_count — the row list of the first re-scoring."""
         n_pad = -(-n_users // 32) * 32
         need = self.lib.pk_score_state_bytes(n_users, splits)
         if self._score_states is None:
@@ -1313,7 +1323,22 @@ class HipOps:
                     KC, splits, _ptr(cs), _ptr(ci), _ptr(self._score_state), tiles_per_chunk or self.score_tiles_per_chunk,
                     _ptr(tile_bound), _ptr(dense), _ptr(skip), int(dtiles))
             with self._timed('score_candidates', (n_users, n_items, K)):
-                if bound_out is None:
+                if settle is not None:
+                    assert splits == 1 and tile_bound is not None and E_rows[1] is not None
+                    q = settle
+                    oi, fl, ol, oc = q['out_idx'], q['flags'], q['open_list'], q['open_count']
+                    assert oi.dtype == torch.int64 and oi.is_contiguous() and tuple(oi.shape) == (n_users, int(q['topk']))
+                    assert fl.dtype == torch.int32 and fl.is_contiguous() and fl.numel() == n_users
+                    assert ol.dtype == torch.int32 and ol.is_contiguous() and ol.numel() >= n_users
+                    assert oc.dtype == torch.int32 and oc.numel() == 1
+                    nrm, perm = q.get('item_norm'), q.get('out_perm')
+                    assert nrm is None or (nrm.dtype == torch.float32 and nrm.is_contiguous() and nrm.numel() == n_items)
+                    assert perm is None or (perm.dtype == torch.int64 and perm.is_contiguous() and perm.numel() == n_users)
+                    assert bound_out is None or (bound_out.dtype == torch.float32 and bound_out.is_contiguous() and bound_out.numel() == n_users)
+                    blk = _lib.PkSweepSettle(int(q['topk']), float(q['vmax']), _ptr(nrm), _ptr(oi), _ptr(perm), _ptr(fl), _ptr(ol), _ptr(oc))
+                    _lib.check(self.lib.pk_score_candidates_rows_settle_f32(*args[:14], *args[15:], _ptr(bound_out), C.byref(blk)),
+                               'pk_score_candidates_rows_settle_f32')
+                elif bound_out is None:
                     _lib.check(self.lib.pk_score_candidates_rows_f32(*args), 'pk_score_candidates_rows_f32')
                 else:
                     assert bound_out.dtype == torch.float32 and bound_out.is_contiguous() and bound_out.numel() == n_users
@@ -1392,7 +1417,7 @@ class HipOps:
 
     def rescore_topk(self, V, E, n_items, seen_ptr, KC, cs, ci, topk, vmax, want_scores=True, splits=1, out=None,
                      rows=None, n_rows_dev=None, e_err=None, e_exact=False, v32=None, flagged=None, item_norm=None,
-                     out_perm=None, user_norm=None):
+                     out_perm=None, user_norm=None, first_pass=None):
         """Exact fp64 re-scoring + certification.  rows (int32 tensor): only these users are re-done (outputs
         are still indexed by user: pass the full-size `out`); e_err: per-user error weight of an approximate E
         (flags bit 4 = not certified at that accuracy); v32: fp32 image of V [n_items x >= K], gathered instead
@@ -1403,7 +1428,9 @@ class HipOps:
         u goes to row out_perm[u] of out_idx (scores and flags stay at row u).  user_norm (float32 [n_users]): upper bounds
         of the norms of the rows of E — the users' side of the sweep's pruning bound; on a first pass over an approximate E
         (v32 and e_err given, no rows, not e_exact) the users whose order the sweep's own scores decide are then settled
-        without re-scoring (pk_rescore_topk_rows_settle_f64: flags = 8, no score row; `settled_users` counts them)."""
+        without re-scoring (pk_rescore_topk_rows_settle_f64: flags = 8, no score row; `settled_users` counts them).
+        first_pass (timers only): a call with a row list is booked as the pass's first re-scoring (the open list of a sweep
+        that settled at its exit) instead of the re-scoring of the re-folded users."""
         assert V.stride(1) == 1 and E.stride(1) == 1
         assert v32 is None or (v32.dtype == torch.float32 and v32.stride(1) == 1 and v32.shape[1] >= E.shape[1])
         n_users, K = E.shape
@@ -1416,7 +1443,9 @@ class HipOps:
             flags = torch.empty(n_users, dtype=torch.int32, device=self.device)
         n_rows = n_users if rows is None else int(rows.numel())
         e_ld = 0 if e_err is None else (e_err.stride(0) if e_err.numel() > 1 else 1)
-        with self._timed('rescore_topk' if rows is None else 'rescore_topk_refolded', (n_rows, KC, K)):
+        if first_pass is None:
+            first_pass = rows is None
+        with self._timed('rescore_topk' if first_pass else 'rescore_topk_refolded', (n_rows, KC, K)):
             fl, fc, fo = flagged if flagged is not None else (None, None, 0)
             assert item_norm is None or (item_norm.dtype == torch.float32 and item_norm.is_contiguous() and item_norm.numel() == n_items)
             args = (self.stream(), n_rows, _ptr(rows), _ptr(n_rows_dev), n_users, n_items, K, _ptr(V),

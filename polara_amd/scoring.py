@@ -303,11 +303,18 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
                 un = ub
         if not prune:
             ub = None
+        # One batch, ONE list per user from a single sweep, lists in LDS: the settle rule runs where a group LEAVES the sweep,
+        # on the sorted lists its wave still holds (ops.score_candidates `settle`) — the settled users' lists are never written
+        # or read back, and the first re-scoring runs densely packed on the users that stay open (its row list; same
+        # arithmetic user by user, so flags, re-fold list and final lists are those of the tier inside the re-scoring).
+        at_exit = bool(un is not None and rows_kw and one_batch and splits == 1 and not two_phase[0] and w is not None
+                       and hasattr(ops, 'sweep_settles') and ops.sweep_settles(KC))
         sp = seen_ptr[u0:u1 + 1] if filter_seen else None
         st = (seen_tiles[0], seen_tiles[1][u0:u1]) if seen_tiles is not None else None
         assert u0 % 32 == 0, 'user batches start on a 32-user group boundary (dense seen masks are indexed by group)'
         sd = (seen_dense[0][u0 // 32:], seen_dense[1][u0:u1], seen_dense[2]) if seen_dense is not None else None
         extra = {} if sd is None else {'seen_dense': sd}
+        outs = (out_idx[u0:u1], out_s[u0:u1], flags[u0:u1])
         if two_phase[0] and prune:
             # pruned sweep in two phases: head of the catalogue for every group, then item splits that start from the
             # head's thresholds, lists merged (K3; the chain of a group is head + tail / S tiles instead of head + tail)
@@ -315,10 +322,14 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
                                          factors.tile_bound, seen_tiles=st, seen_dense=sd, **rows_kw)
             splits = 1                                                                        # ONE merged list per user
         else:
+            if at_exit:
+                rows_kw.pop('bound_out')          # (the rule reads the bounds where the sweep holds them)
+                open_lst, open_cnt = torch.empty(nb, dtype=torch.int32, device=E.device), counters[-1:]
+                rows_kw['settle'] = dict(topk=topk, vmax=factors.vmax, item_norm=factors.vnorm, out_idx=outs[0], flags=outs[2],
+                                         out_perm=perm_kw.get('out_perm'), open_list=open_lst, open_count=open_cnt)
             cs, ci = ops.score_candidates(factors.Vp, Ep, nb, n_items, K, sp, seen_idx, KC, splits,
                                           user_bound=ub, tile_bound=factors.tile_bound if prune else None,
                                           seen_tiles=st, **extra, **rows_kw)                  # K3
-        outs = (out_idx[u0:u1], out_s[u0:u1], flags[u0:u1])
         to_final = (final_list, final_cnt, u0) if fused_lists else None
         if approx_fold_in and fused_lists:
             b = batch_no[0]
@@ -330,7 +341,8 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
         ops.rescore_topk(factors.V, Eb, n_items, sp, KC, cs, ci, topk, factors.vmax, want_scores=True,
                          splits=splits, out=outs, e_err=w, v32=factors.V32x if approx_fold_in else None, **perm_kw, **(
                              {'flagged': first, 'item_norm': factors.vnorm if approx_fold_in else None} if fused_lists else {}),
-                         **({'user_norm': un} if un is not None else {}))
+                         **({'rows': open_lst, 'n_rows_dev': open_cnt, 'first_pass': True} if at_exit else
+                            {'user_norm': un} if un is not None else {}))
         if un is not None and stats is not None:
             settled.append(outs[2])
         if approx_fold_in:
@@ -373,9 +385,10 @@ def recommend(ops, factors, T, topk, filter_seen=True, return_scores=False, stat
                        and topk <= PACKED_MAX_TOPK and hasattr(ops, 'fold_q20_zero'))
     if fused_lists:
         if fold_zeroes:
-            counters = ops.fold_q20_zero(T, factors.Q20, K, Ex, 2 + max(B, 2), rows=(0, n_users))
+            counters = ops.fold_q20_zero(T, factors.Q20, K, Ex, 3 + max(B, 2), rows=(0, n_users))
         else:
-            counters = ops.zero_counters(2 + max(B, 2))      # on the calling stream, before any batch stream forks from it
+            counters = ops.zero_counters(3 + max(B, 2))      # on the calling stream, before any batch stream forks from it
+        # (the last counter: the open list of a sweep that settles at its exit, `at_exit` in run_batch)
         final_cnt = counters[0:1]
         final_list = torch.empty(n_users, dtype=torch.int32, device=E.device)
     if one_batch:
