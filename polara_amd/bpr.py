@@ -44,23 +44,7 @@ def item_order(seed, epoch, n_items):
 def block_schedule(users, items, n_users, n_items, blocks, order=None):
     """pmf.block_schedule with the items cut into parts along `order` (None: the identity): (perm, block_ptr, item_part int64
     [n_items], item_ptr int64 [B + 1]); part c of the items is order[item_ptr[c] : item_ptr[c + 1]]."""
-    users, items = np.asarray(users, dtype=np.int64), np.asarray(items, dtype=np.int64)
-    B, nnz = int(blocks), len(users)
-    if B < 1 or B > min(int(n_users), int(n_items)):
-        raise ValueError('BPR: %d blocks for %d users and %d items (1 .. min of the two)' % (B, n_users, n_items))
-    order = np.arange(int(n_items), dtype=np.int64) if order is None else np.asarray(order, dtype=np.int64)
-    upart = pmf._parts(np.bincount(users, minlength=int(n_users)), B, nnz)
-    ordered_parts = pmf._parts(np.bincount(items, minlength=int(n_items))[order], B, nnz)
-    ipart = np.empty(int(n_items), dtype=np.int64)
-    ipart[order] = ordered_parts
-    item_ptr = np.zeros(B + 1, dtype=np.int64)
-    np.cumsum(np.bincount(ordered_parts, minlength=B), out=item_ptr[1:])
-    i, j = upart[users], ipart[items]
-    key = ((j - i) % B) * B + i
-    perm = np.argsort(key, kind='stable').astype(np.int64)
-    block_ptr = np.zeros(B * B + 1, dtype=np.int64)
-    np.cumsum(np.bincount(key, minlength=B * B), out=block_ptr[1:])
-    return perm, block_ptr, ipart, item_ptr
+    return pmf._block_schedule(users, items, n_users, n_items, blocks, order, what='BPR')
 
 
 def initial_factors(n_users, n_items, rank, seed=None):

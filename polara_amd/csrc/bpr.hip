@@ -10,8 +10,10 @@
 // every product and sum below is rounded on its own, as NumPy rounds them (the library is built with contraction on)
 #pragma clang fp contract(off)
 
+#include "blocked_sweep.h"            // after the pragma: the shared helpers are compiled without contraction too
+
 #define BPR_MAX_RANK 63             // k + 1 columns (the bias) in one wave
-#define BPR_THREADS 64              // one wave per workgroup, as in pmf.hip: a block's sweep is a chain of dependent loads
+#define BPR_THREADS 64              // one wave per workgroup, as PMF_THREADS: a block's sweep is a chain of dependent loads
 
 // ---- the sigmoid: IEEE operations only, the same sequence as tests/bpr_reference.py ---------------------------------------
 // sigm(x) = 1 / (1 + exp(x)).  With a = -|x| (cut at BPR_EXP_MIN, below which exp(a) is under half the smallest subnormal):
@@ -59,13 +61,6 @@ extern "C" int pk_bpr_sigmoid_f64(void *stream, int64_t n, const double *x_dev, 
 }
 
 // ---- the negatives of an epoch --------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint64_t bpr_mix(uint64_t z) {         // the splitmix64 output function (sample_mix of sampled.hip)
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 __global__ __launch_bounds__(256) void bpr_draw_kernel(int64_t nnz, const int32_t *__restrict__ users, const int32_t *__restrict__ items,
                                                        const int64_t *__restrict__ perm, const int32_t *__restrict__ item_order,
                                                        const int32_t *__restrict__ item_part, const int64_t *__restrict__ item_ptr,
@@ -80,7 +75,7 @@ __global__ __launch_bounds__(256) void bpr_draw_kernel(int64_t nnz, const int32_
     const uint64_t base = key + 4ull * (uint64_t)perm[p];
     int32_t found = -1;
     for (int t = 0; t < PK_BPR_DRAWS && found < 0; ++t) {
-        const uint64_t w = bpr_mix(base + (uint64_t)t) >> 32;
+        const uint64_t w = pk_mix64(base + (uint64_t)t) >> 32;
         const int32_t j = item_order[lo_c + (int64_t)((w * n_c) >> 32)];
         int64_t lo = r0, hi = r1;                                 // lower bound of j in the user's sorted row
         while (lo < hi) {
@@ -106,7 +101,7 @@ extern "C" int pk_bpr_draw_negatives(void *stream, int64_t nnz, int64_t n_users,
     PK_REQUIRE(item_order_dev && item_part_dev && item_ptr_dev && indptr_dev, "pk_bpr_draw_negatives: bad pointers");
     PK_REQUIRE(nnz == 0 || (users_dev && items_dev && perm_dev && indices_dev && neg_dev), "pk_bpr_draw_negatives: no interactions given");
     if (nnz == 0) return PK_OK;
-    const uint64_t key = bpr_mix(((uint64_t)seed << 32) + (uint64_t)epoch);
+    const uint64_t key = pk_mix64(((uint64_t)seed << 32) + (uint64_t)epoch);
     hipLaunchKernelGGL(bpr_draw_kernel, dim3((unsigned)pk_ceil_div(nnz, 256)), dim3(256), 0, pk_stream(stream), nnz, users_dev, items_dev,
                        perm_dev, item_order_dev, item_part_dev, item_ptr_dev, indptr_dev, indices_dev, key, neg_dev);
     PK_CHECK_LAUNCH("bpr_draw_kernel");
@@ -124,18 +119,6 @@ struct BprArgs {
     int64_t *counts;                    // [3][B * B]: trained, skipped, correct of every block
 };
 
-// the halving tree of polara_hip.h on a xor butterfly (pmf_group_sum of pmf.hip): every lane of the group ends with the same bits
-template <int W>
-__device__ __forceinline__ double bpr_group_sum(double v) {
-    if constexpr (W >= 64) v = v + pk_lane_xor<32>(v);
-    if constexpr (W >= 32) v = v + pk_lane_xor<16>(v);
-    v = v + pk_lane_xor<8>(v);
-    v = v + pk_lane_xor<4>(v);
-    v = v + pk_lane_xor<2>(v);
-    v = v + pk_lane_xor<1>(v);
-    return v;
-}
-
 // W lanes per block, 64 / W blocks per wave; lane c holds column c of the k + 1 (column k: the constant 1 of P, the bias of Q).
 // The loop runs to the longest block of the wave with every lane active (the butterfly reads its neighbours); a group past the
 // end of its block, or at a skipped sample (negative -1), holds no rows: it computes on zeros, loads nothing and stores nothing.
@@ -143,24 +126,11 @@ __device__ __forceinline__ double bpr_group_sum(double v) {
 // forwarded in registers: the user row, and each of the two item rows from either item row of sample t.
 template <int W>
 __global__ __launch_bounds__(BPR_THREADS) void bpr_stratum_kernel(BprArgs a, int stratum) {
-    constexpr int G = 64 / W;
-    const int lane = pk_lane();
-    const int g = lane / W, c = lane % W;
-    const int64_t b = (int64_t)blockIdx.x * G + g;
+    int c;
+    const int64_t b = pk_sweep_lanes<W>(c);
     const bool qcol = c <= a.rank, pcol = c < a.rank;
-    int64_t t0 = 0, len = 0;
-    if (b < a.B) {
-        t0 = a.block_ptr[(int64_t)stratum * a.B + b];
-        len = a.block_ptr[(int64_t)stratum * a.B + b + 1] - t0;
-    }
-    int64_t maxlen = len;
-#pragma unroll
-    for (int off = 32; off >= W; off >>= 1) {
-        const int64_t o = __shfl_xor(maxlen, off, 64);
-        maxlen = o > maxlen ? o : maxlen;
-    }
-    maxlen = ((int64_t)__builtin_amdgcn_readfirstlane((int)(maxlen >> 32)) << 32) |
-             (uint32_t)__builtin_amdgcn_readfirstlane((int)(maxlen & 0xffffffffll));
+    int64_t t0, len;
+    const int64_t maxlen = pk_sweep_range<W>(a.B, a.block_ptr, stratum, b, t0, len);
 
     auto sample = [&](int64_t t, int &u, int &i, int &j) {
         u = i = j = -1;
@@ -188,7 +158,7 @@ __global__ __launch_bounds__(BPR_THREADS) void bpr_stratum_kernel(BprArgs a, int
         const double qj_next = (j_from_i || j_from_j) ? 0.0 : row(a.Q, a.ldq, j1);
 
         const double d = qi - qj;
-        const double x = bpr_group_sum<W>(p * d);
+        const double x = group_sum<W>(p * d);
         const double z = bpr_sigmoid(x);
         const double p_new = pcol ? p + a.lr * (z * d - a.reg * p) : p;
         const double qi_new = qi + a.lr * (z * p - a.reg * qi);
@@ -246,32 +216,29 @@ extern "C" int pk_bpr_epoch_f64(void *stream, int32_t blocks, int32_t rank, int6
                                 const int32_t *users_dev, const int32_t *items_dev, const int32_t *neg_dev, double *P_dev, int64_t ldp,
                                 double *Q_dev, int64_t ldq, double learning_rate, double regularization, void *work_dev,
                                 int64_t *counts_dev) {
-    PK_REQUIRE(rank >= 1 && rank <= BPR_MAX_RANK, "pk_bpr_epoch_f64: rank %d outside 1..%d", (int)rank, BPR_MAX_RANK);
-    PK_REQUIRE(blocks >= 1 && blocks <= PK_PMF_MAX_BLOCKS, "pk_bpr_epoch_f64: %d blocks outside 1..%d", (int)blocks, PK_PMF_MAX_BLOCKS);
-    PK_REQUIRE(nnz >= 0 && block_ptr_dev && P_dev && Q_dev && work_dev && counts_dev && P_dev != Q_dev, "pk_bpr_epoch_f64: bad pointers");
-    PK_REQUIRE(nnz == 0 || (users_dev && items_dev && neg_dev), "pk_bpr_epoch_f64: no samples given");
-    PK_REQUIRE(ldp >= rank + 1 && ldq >= rank + 1, "pk_bpr_epoch_f64: bad leading dimension (rank + 1 columns)");
+    const int rc = pk_sweep_check("pk_bpr_epoch_f64", blocks, rank, BPR_MAX_RANK, rank + 1, true,
+                                  nnz >= 0 && block_ptr_dev && P_dev && Q_dev && work_dev && counts_dev && P_dev != Q_dev,
+                                  nnz == 0 || (users_dev && items_dev && neg_dev), "samples", ldp, ldq);
+    if (rc != PK_OK) return rc;
     BprArgs a;
     a.B = blocks, a.rank = rank;
     a.block_ptr = block_ptr_dev, a.users = users_dev, a.items = items_dev, a.neg = neg_dev;
     a.P = P_dev, a.Q = Q_dev, a.ldp = ldp, a.ldq = ldq;
     a.lr = learning_rate, a.reg = regularization;
     a.counts = (int64_t *)work_dev;
-    const int w = rank + 1 <= 16 ? 16 : rank + 1 <= 32 ? 32 : 64;
-    const unsigned grid = (unsigned)pk_ceil_div(blocks, 64 / w);
     hipStream_t st = pk_stream(stream);
-    for (int s = 0; s < blocks; ++s) {
-        if (w == 16)
-            hipLaunchKernelGGL(bpr_stratum_kernel<16>, dim3(grid), dim3(BPR_THREADS), 0, st, a, s);
-        else if (w == 32)
-            hipLaunchKernelGGL(bpr_stratum_kernel<32>, dim3(grid), dim3(BPR_THREADS), 0, st, a, s);
-        else
-            hipLaunchKernelGGL(bpr_stratum_kernel<64>, dim3(grid), dim3(BPR_THREADS), 0, st, a, s);
-        PK_CHECK_LAUNCH("bpr_stratum_kernel");
-    }
-    hipLaunchKernelGGL(bpr_counts_kernel, dim3(1), dim3(256), 0, st, (int)blocks, (const int64_t *)work_dev, counts_dev);
-    PK_CHECK_LAUNCH("bpr_counts_kernel");
-    return PK_OK;
+    return pk_sweep_epoch(
+        blocks, rank + 1,
+        [&](auto w, unsigned grid, int s) -> int {
+            hipLaunchKernelGGL(bpr_stratum_kernel<w()>, dim3(grid), dim3(BPR_THREADS), 0, st, a, s);
+            PK_CHECK_LAUNCH("bpr_stratum_kernel");
+            return PK_OK;
+        },
+        [&]() -> int {
+            hipLaunchKernelGGL(bpr_counts_kernel, dim3(1), dim3(256), 0, st, (int)blocks, (const int64_t *)work_dev, counts_dev);
+            PK_CHECK_LAUNCH("bpr_counts_kernel");
+            return PK_OK;
+        });
 }
 
 // eager load of this translation unit's code object (pk_warm_up, api.cpp)

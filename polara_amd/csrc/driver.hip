@@ -235,19 +235,13 @@ __global__ void v32_image_kernel(int64_t n, int K, int ld32, const double *__res
     out[i] = c < K ? (float)V[r * K + c] : (c == K ? bound[r] : 0.0f);
 }
 
-// standard normal start block: counter-based (splitmix64 of seed and element index -> two uniforms -> Box-Muller), so
+// standard normal start block: counter-based (pk_mix64 of seed and element index -> two uniforms -> Box-Muller), so
 // the block depends on (seed, n, l) only — no host generator, no 14 MB upload
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __global__ void randn_kernel(int64_t n_elems, uint64_t seed, double *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_elems) return;
-    const uint64_t a = splitmix64(seed * 0xD1342543DE82EF95ull + (uint64_t)(2 * i));
-    const uint64_t b = splitmix64(seed * 0xD1342543DE82EF95ull + (uint64_t)(2 * i + 1));
+    const uint64_t a = pk_mix64(seed * 0xD1342543DE82EF95ull + (uint64_t)(2 * i));
+    const uint64_t b = pk_mix64(seed * 0xD1342543DE82EF95ull + (uint64_t)(2 * i + 1));
     const double u1 = ((double)(a >> 11) + 1.0) * (1.0 / 9007199254740993.0);     // (0, 1)
     const double u2 = (double)(b >> 11) * (1.0 / 9007199254740992.0);             // [0, 1)
     out[i] = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);

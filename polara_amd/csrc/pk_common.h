@@ -35,6 +35,14 @@ static inline hipStream_t pk_stream(void *s) { return reinterpret_cast<hipStream
 
 static inline int64_t pk_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// the splitmix64 output function: the one finaliser behind every counter-based draw stream of polara_hip.h
+__host__ __device__ __forceinline__ uint64_t pk_mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // ---- "done once" flags for PER-DEVICE function attributes (hipFuncSetAttribute raises the dynamic-LDS limit of a kernel
 // on the CURRENT device only; the coarse ABI allows contexts on several devices in one process).  One bit per device
 // ordinal; two threads racing on the first call both set the attribute, which is idempotent.

@@ -19,7 +19,7 @@
 //
 // pk_sample_unseen: n distinct items per user, uniform over the items outside the user's row of a CSR and outside its row of a
 //   second CSR, in draw order.  The stream is defined so that NumPy can restate it draw by draw (tests/sampled_reference.py):
-//     draw t = 0, 1, 2, ...:  z = mix64(seed_u * 2^32 + t)  (the splitmix64 finaliser, sample_mix), w = z >> 32,
+//     draw t = 0, 1, 2, ...:  z = mix64(seed_u * 2^32 + t)  (the splitmix64 finaliser, pk_mix64), w = z >> 32,
 //                             m = w * n_items (64-bit), the draw is REJECTED when (m mod 2^32) < (2^32 mod n_items), else x = m >> 32;
 //     x is ACCEPTED when it is in neither row and was not accepted before; the output is the first n accepted x in order of t.
 //   * one wave per user evaluates 64 consecutive t per round: exclusion by binary search in the sorted row and a scan of the
@@ -151,13 +151,6 @@ extern "C" int pk_candidates_topk_f64(void *stream, int64_t n_users, int64_t n_i
 }
 
 // ---- sampling without replacement --------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint64_t sample_mix(uint64_t z) {          // the splitmix64 output function
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // Rounds of 64 draws after which every user must be done, given that each has at least min_eligible >= n items outside its
 // rows.  A user is NOT done after t accepted-or-repeated draws iff m = e - n + 1 of its e eligible items are still unseen:
 //   P <= C(e, n - 1) (1 - m / N)^t <= exp((n - 1) ln(e E / (n - 1)) - t m / N)       (union over the sets of m items)
@@ -199,7 +192,7 @@ __global__ __launch_bounds__(64) void sample_unseen_kernel(int64_t n_items, cons
     int count = 0;
     for (int64_t round = 0; round < max_rounds && count < n; ++round) {
         const uint64_t t = (uint64_t)round * 64 + lane;           // < 2^32 (checked on the host)
-        const uint64_t m = (sample_mix(hi_seed | t) >> 32) * (uint64_t)n_items;
+        const uint64_t m = (pk_mix64(hi_seed | t) >> 32) * (uint64_t)n_items;
         const int32_t x = (int32_t)(m >> 32);
         bool ok = (uint32_t)m >= thresh;
         if (ok) ok = !sample_in_sorted(t_indices, t0, t1, x);

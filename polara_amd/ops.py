@@ -2088,38 +2088,58 @@ class HipOps:
 
     _PMF_ADJUST = {None: 0, 'adagrad': 1, 'rmsprop': 2}
 
+    @staticmethod
+    def _check_row_blocks(what, blocks, rows, cols):
+        """every block is fp64 [n x cols] with unit column stride, n running through `rows` again and again"""
+        for X, n in zip(blocks, tuple(rows) * len(blocks)):
+            if X.dtype != torch.float64 or X.dim() != 2 or tuple(X.shape) != (n, cols) or X.stride(1) != 1 or X.stride(0) < cols:
+                raise ValueError('%s: a block of shape %s, strides %s for [%d x %d] fp64 rows' % (what, tuple(X.shape), X.stride(), n, cols))
+
+    @staticmethod
+    def _check_plan(plan, what, users=(), items=(), entries=(), **others):
+        """B of a plan of `what`_plan: block_ptr holds B * B + 1 elements, the named tensors one per user, per item and per
+        entry, and the `others` as many as given"""
+        B = int(plan['blocks'])
+        n_users, n_items = plan['shape']
+        want = dict(others, block_ptr=B * B + 1)
+        for names, n in ((users, n_users), (items, n_items), (entries, plan['nnz'])):
+            want.update((name, n) for name in names)
+        if any(name not in plan or plan[name].numel() != n for name, n in want.items()):
+            raise ValueError('%s: not a plan of %s_plan' % (what, what.lower()))
+        return B
+
+    def _pmf_sweep(self, what, B, plan, P, Q, eta, lambd, adjust, state, gamma, smoothing, sizes=(), kernelized=(), snapshots=()):
+        """pmf_epoch and kpmf_epoch behind their plan checks: rank, adjuster, state and blocks checked under the model's name
+        `what`, then pk_pmf_epoch_f64, or pk_kpmf_epoch_f64 with its `sizes` and `kernelized` arguments in their places"""
+        n_users, n_items = plan['shape']
+        k = int(P.shape[1])
+        if k < 1 or k > self.pmf_max_rank():
+            raise ValueError('%s: rank %d outside 1..%d' % (what, k, self.pmf_max_rank()))
+        if adjust not in self._PMF_ADJUST:
+            raise ValueError('%s: unknown gradient adjustment %r' % (what, adjust))
+        if adjust and (state is None or len(state) != 2):
+            raise ValueError('%s: the gradient adjustment %r needs state = (SP, SQ)' % (what, adjust))
+        self._check_row_blocks(what, (P, Q) + tuple(snapshots) + (tuple(state) if adjust else ()), (n_users, n_items), k)
+        SP, SQ = state if adjust else (None, None)
+        work = self.empty(int(self.lib.pk_pmf_work_doubles(B)))       # the block sums of the squared error
+        out = self.empty(1)
+        name = what.lower() + '_epoch'
+        entry = 'pk_%s_f64' % name
+        with self._timed(name, (plan['nnz'], k, B)):
+            _lib.check(getattr(self.lib, entry)(
+                self.stream(), B, k, int(plan['nnz']), *sizes, _ptr(plan['block_ptr']), _ptr(plan['users']), _ptr(plan['items']),
+                _ptr(plan['vals']), _ptr(P), P.stride(0), _ptr(Q), Q.stride(0), _ptr(plan['row_nnz']), _ptr(plan['col_nnz']),
+                *kernelized, float(eta), float(lambd), self._PMF_ADJUST[adjust], _ptr(SP), SP.stride(0) if adjust else 0, _ptr(SQ),
+                SQ.stride(0) if adjust else 0, float(gamma), float(smoothing), _ptr(work), _ptr(out)), entry)
+        return out
+
     def pmf_epoch(self, plan, P, Q, eta, lambd, adjust=None, state=None, gamma=0.9, smoothing=1e-6):
         """One SGD sweep over the plan's interactions (pk_pmf_epoch_f64: one launch per stratum and one for the squared
         error), P [n_users x k] and Q [n_items x k] updated in place.  adjust: None, 'adagrad' or 'rmsprop' with
         state = (SP, SQ) of the shapes of P and Q, zeroed by the caller before every epoch.  Returns a device tensor of one
         double: the epoch's squared error."""
-        n_users, n_items = plan['shape']
-        k = int(P.shape[1])
-        if k < 1 or k > self.pmf_max_rank():
-            raise ValueError('PMF: rank %d outside 1..%d' % (k, self.pmf_max_rank()))
-        if adjust not in self._PMF_ADJUST:
-            raise ValueError('PMF: unknown gradient adjustment %r' % (adjust,))
-        if adjust and (state is None or len(state) != 2):
-            raise ValueError('PMF: the gradient adjustment %r needs state = (SP, SQ)' % adjust)
-        blocks = (P, Q) + (tuple(state) if adjust else ())
-        for X, n in zip(blocks, (n_users, n_items) * 2):
-            if X.dtype != torch.float64 or X.dim() != 2 or tuple(X.shape) != (n, k) or X.stride(1) != 1 or X.stride(0) < k:
-                raise ValueError('PMF: a block of shape %s, strides %s for [%d x %d] fp64 rows' % (tuple(X.shape), X.stride(), n, k))
-        B = int(plan['blocks'])
-        if plan['block_ptr'].numel() != B * B + 1 or plan['users'].numel() != plan['nnz'] or plan['row_nnz'].numel() != n_users \
-                or plan['col_nnz'].numel() != n_items:
-            raise ValueError('PMF: not a plan of pmf_plan')
-        SP, SQ = state if adjust else (None, None)
-        work = self.empty(int(self.lib.pk_pmf_work_doubles(B)))       # the block sums of the squared error
-        out = self.empty(1)
-        with self._timed('pmf_epoch', (plan['nnz'], k, B)):
-            _lib.check(self.lib.pk_pmf_epoch_f64(self.stream(), B, k, int(plan['nnz']), _ptr(plan['block_ptr']), _ptr(plan['users']),
-                                                 _ptr(plan['items']), _ptr(plan['vals']), _ptr(P), P.stride(0), _ptr(Q), Q.stride(0),
-                                                 _ptr(plan['row_nnz']), _ptr(plan['col_nnz']), float(eta), float(lambd),
-                                                 self._PMF_ADJUST[adjust], _ptr(SP), SP.stride(0) if adjust else 0, _ptr(SQ),
-                                                 SQ.stride(0) if adjust else 0, float(gamma), float(smoothing), _ptr(work), _ptr(out)),
-                       'pk_pmf_epoch_f64')
-        return out
+        B = self._check_plan(plan, 'PMF', users=('row_nnz',), items=('col_nnz',), entries=('users',))
+        return self._pmf_sweep('PMF', B, plan, P, Q, eta, lambd, adjust, state, gamma, smoothing)
 
     # ---- Kernelized probabilistic matrix factorisation (csrc/kpmf.hip) ------------------------------------------------------
     def kpmf_plan(self, A, blocks, Ku, Ki):
@@ -2147,42 +2167,17 @@ class HipOps:
         when None): whatever they hold is overwritten, and they equal P and Q when the epoch ends.  Returns a device tensor
         of one double: the epoch's squared error."""
         n_users, n_items = plan['shape']
-        k = int(P.shape[1])
-        if k < 1 or k > self.pmf_max_rank():
-            raise ValueError('KPMF: rank %d outside 1..%d' % (k, self.pmf_max_rank()))
-        if adjust not in self._PMF_ADJUST:
-            raise ValueError('KPMF: unknown gradient adjustment %r' % (adjust,))
-        if adjust and (state is None or len(state) != 2):
-            raise ValueError('KPMF: the gradient adjustment %r needs state = (SP, SQ)' % adjust)
         if snapshots is None:
-            snapshots = (self.empty(n_users, k), self.empty(n_items, k))
+            snapshots = (self.empty(n_users, int(P.shape[1])), self.empty(n_items, int(P.shape[1])))
         if len(snapshots) != 2:
             raise ValueError('KPMF: snapshots = (P_snap, Q_snap)')
-        blocks = (P, Q) + tuple(snapshots) + (tuple(state) if adjust else ())
-        for X, n in zip(blocks, (n_users, n_items) * 3):
-            if X.dtype != torch.float64 or X.dim() != 2 or tuple(X.shape) != (n, k) or X.stride(1) != 1 or X.stride(0) < k:
-                raise ValueError('KPMF: a block of shape %s, strides %s for [%d x %d] fp64 rows' % (tuple(X.shape), X.stride(), n, k))
-        B = int(plan['blocks'])
-        if 'ku_ptr' not in plan or plan['block_ptr'].numel() != B * B + 1 or plan['users'].numel() != plan['nnz'] \
-                or plan['row_nnz'].numel() != n_users or plan['col_nnz'].numel() != n_items \
-                or plan['user_part'].numel() != n_users or plan['item_part'].numel() != n_items \
-                or plan['ku_ptr'].numel() != n_users + 1 or plan['ki_ptr'].numel() != n_items + 1 \
-                or plan['ku_diag'].numel() != n_users or plan['ki_diag'].numel() != n_items:
-            raise ValueError('KPMF: not a plan of kpmf_plan')
-        SP, SQ = state if adjust else (None, None)
+        B = self._check_plan(plan, 'KPMF', users=('row_nnz', 'user_part', 'ku_diag'), items=('col_nnz', 'item_part', 'ki_diag'),
+                             entries=('users',), ku_ptr=n_users + 1, ki_ptr=n_items + 1)
         PS, QS = snapshots
-        work = self.empty(int(self.lib.pk_pmf_work_doubles(B)))       # the block sums of the squared error
-        out = self.empty(1)
-        with self._timed('kpmf_epoch', (plan['nnz'], k, B)):
-            _lib.check(self.lib.pk_kpmf_epoch_f64(
-                self.stream(), B, k, int(plan['nnz']), n_users, n_items, _ptr(plan['block_ptr']), _ptr(plan['users']),
-                _ptr(plan['items']), _ptr(plan['vals']), _ptr(P), P.stride(0), _ptr(Q), Q.stride(0), _ptr(plan['row_nnz']),
-                _ptr(plan['col_nnz']), _ptr(plan['user_part']), _ptr(plan['item_part']), _ptr(plan['ku_ptr']), _ptr(plan['ku_idx']),
-                _ptr(plan['ku_val']), _ptr(plan['ku_diag']), _ptr(plan['ki_ptr']), _ptr(plan['ki_idx']), _ptr(plan['ki_val']),
-                _ptr(plan['ki_diag']), _ptr(PS), PS.stride(0), _ptr(QS), QS.stride(0), float(eta), float(lambd),
-                self._PMF_ADJUST[adjust], _ptr(SP), SP.stride(0) if adjust else 0, _ptr(SQ), SQ.stride(0) if adjust else 0,
-                float(gamma), float(smoothing), _ptr(work), _ptr(out)), 'pk_kpmf_epoch_f64')
-        return out
+        kernelized = [_ptr(plan[name]) for name in ('user_part', 'item_part', 'ku_ptr', 'ku_idx', 'ku_val', 'ku_diag', 'ki_ptr',
+                                                    'ki_idx', 'ki_val', 'ki_diag')] + [_ptr(PS), PS.stride(0), _ptr(QS), QS.stride(0)]
+        return self._pmf_sweep('KPMF', B, plan, P, Q, eta, lambd, adjust, state, gamma, smoothing, sizes=(n_users, n_items),
+                               kernelized=kernelized, snapshots=snapshots)
 
     # ---- Bayesian personalised ranking (csrc/bpr.hip) -------------------------------------------------------------------
     def bpr_max_rank(self):
@@ -2214,15 +2209,9 @@ class HipOps:
                         users=users[perm].to(torch.int32).contiguous(), items=items[perm].to(torch.int32).contiguous(),
                         item_order=order.to(torch.int32).contiguous(), item_part=item_part, matrix=A)
 
-    @staticmethod
-    def _bpr_check_plan(plan):
-        B = int(plan['blocks'])
-        n_items = plan['shape'][1]
-        if plan['block_ptr'].numel() != B * B + 1 or plan['item_ptr'].numel() != B + 1 or plan['users'].numel() != plan['nnz'] \
-                or plan['items'].numel() != plan['nnz'] or plan['perm'].numel() != plan['nnz'] \
-                or plan['item_order'].numel() != n_items or plan['item_part'].numel() != n_items:
-            raise ValueError('BPR: not a plan of bpr_plan')
-        return B
+    def _bpr_check_plan(self, plan):
+        return self._check_plan(plan, 'BPR', items=('item_order', 'item_part'), entries=('users', 'items', 'perm'),
+                                item_ptr=int(plan['blocks']) + 1)
 
     def bpr_draw_negatives(self, plan, seed, epoch):
         """int32 [nnz] (device): the negative of every position of the plan's schedule, -1 where all PK_BPR_DRAWS draws were
@@ -2249,9 +2238,7 @@ class HipOps:
         k = int(P.shape[1]) - 1
         if k < 1 or k > self.bpr_max_rank():
             raise ValueError('BPR: rank %d outside 1..%d' % (k, self.bpr_max_rank()))
-        for X, n in zip((P, Q), (n_users, n_items)):
-            if X.dtype != torch.float64 or X.dim() != 2 or tuple(X.shape) != (n, k + 1) or X.stride(1) != 1 or X.stride(0) < k + 1:
-                raise ValueError('BPR: a block of shape %s, strides %s for [%d x %d] fp64 rows' % (tuple(X.shape), X.stride(), n, k + 1))
+        self._check_row_blocks('BPR', (P, Q), (n_users, n_items), k + 1)
         B = self._bpr_check_plan(plan)
         if neg.dtype != torch.int32 or neg.dim() != 1 or neg.numel() != plan['nnz'] or (neg.numel() and neg.stride(0) != 1):
             raise ValueError('BPR: the negatives must be int32 [%d] (bpr_draw_negatives)' % plan['nnz'])

@@ -58,23 +58,35 @@ def _parts(counts, blocks, nnz):
     return np.minimum(before * blocks // max(int(nnz), 1), blocks - 1)
 
 
-def block_schedule(users, items, n_users, n_items, blocks):
-    """(perm int64 [nnz], block_ptr int64 [B * B + 1]) of interactions in canonical order: position p of the schedule holds
-    canonical entry perm[p]; block i of stratum s is positions block_ptr[s * B + i] .. block_ptr[s * B + i + 1].  `perm` is the
-    stable sort by s * B + i, so a block keeps the canonical order (runs of one user stay together).  Empty parts and empty
-    blocks are legal; B = 1 is the identity."""
+def _block_schedule(users, items, n_users, n_items, blocks, order=None, what='PMF'):
+    """The one host copy of the schedule, of interactions in canonical order: (perm int64 [nnz], block_ptr int64 [B * B + 1],
+    item_part int64 [n_items], item_ptr int64 [B + 1]).  Position p of the schedule holds canonical entry perm[p]; block i of
+    stratum s is positions block_ptr[s * B + i] .. block_ptr[s * B + i + 1].  `perm` is the stable sort by s * B + i, so a block
+    keeps the canonical order (runs of one user stay together).  The items are cut into parts along `order` (None: the
+    identity): part c is order[item_ptr[c] : item_ptr[c + 1]].  Empty parts and empty blocks are legal; B = 1 is the identity.
+    `what` names the model in the message."""
     users, items = np.asarray(users, dtype=np.int64), np.asarray(items, dtype=np.int64)
     B, nnz = int(blocks), len(users)
     if B < 1 or B > min(int(n_users), int(n_items)):
-        raise ValueError('PMF: %d blocks for %d users and %d items (1 .. min of the two)' % (B, n_users, n_items))
+        raise ValueError('%s: %d blocks for %d users and %d items (1 .. min of the two)' % (what, B, n_users, n_items))
+    order = np.arange(int(n_items), dtype=np.int64) if order is None else np.asarray(order, dtype=np.int64)
     upart = _parts(np.bincount(users, minlength=int(n_users)), B, nnz)
-    ipart = _parts(np.bincount(items, minlength=int(n_items)), B, nnz)
+    ordered_parts = _parts(np.bincount(items, minlength=int(n_items))[order], B, nnz)
+    ipart = np.empty(int(n_items), dtype=np.int64)
+    ipart[order] = ordered_parts
+    item_ptr = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(np.bincount(ordered_parts, minlength=B), out=item_ptr[1:])
     i, j = upart[users], ipart[items]
     key = ((j - i) % B) * B + i
     perm = np.argsort(key, kind='stable').astype(np.int64)
     block_ptr = np.zeros(B * B + 1, dtype=np.int64)
     np.cumsum(np.bincount(key, minlength=B * B), out=block_ptr[1:])
-    return perm, block_ptr
+    return perm, block_ptr, ipart, item_ptr
+
+
+def block_schedule(users, items, n_users, n_items, blocks):
+    """(perm, block_ptr) of `_block_schedule` with the items in their own order"""
+    return _block_schedule(users, items, n_users, n_items, blocks)[:2]
 
 
 def schedule_stats(block_ptr, blocks):

@@ -11,7 +11,7 @@ import torch
 import kpmf_reference as ref
 from conftest import load_golden
 from test_gpu_pmf import device_csr, padding_is_zero, strided, tiny_triplets
-from test_kpmf_host import FIXTURES, check_kpmf_model_against_fixture, restated_solution
+from test_kpmf_host import FIXTURES, check_kpmf_model_against_fixture, half_identity_kernels, restated_solution
 
 pytestmark = pytest.mark.gpu
 
@@ -148,6 +148,35 @@ def test_one_epoch_is_bit_equal_to_the_restatement(hip_ops, blocks, rank, adjust
 @pytest.mark.parametrize('adjust', [None, 'adagrad', 'rmsprop'])
 def test_the_tiny_case_is_bit_equal_to_the_restatement(hip_ops, adjust):
     run_epochs(hip_ops, 'tiny', 4, 3, adjust)
+
+
+@pytest.mark.parametrize('case, rank, adjust', [('tiny', 3, None), ('tiny', 3, 'adagrad'), ('tiny', 3, 'rmsprop'),
+                                                ('fixture', 17, 'rmsprop')])
+def test_half_identity_kernels_give_the_plain_sweep(hip_ops, case, rank, adjust):
+    """both kernel matrices I / 2 (the diagonal stored, no off-diagonal entry): the kernelized term is (+0.0 + 0.5 * (p + p)) = p
+    exactly, so kpmf_epoch leaves P, Q, the state and the squared error bit-equal to pmf_epoch on the same plan (B = 4), and
+    the snapshots equal to P and Q"""
+    ops = hip_ops
+    u, i, v, n_users, n_items = case_of(case)[:5]
+    plan = ops.kpmf_plan(device_csr(ops, u, i, v, n_users, n_items), 4, *half_identity_kernels(n_users, n_items))
+    assert plan['ku_idx'].numel() == 0 and plan['ki_idx'].numel() == 0
+    rng = np.random.RandomState(rank)
+    P0, Q0 = rng.normal(scale=0.1, size=(n_users, rank)), rng.normal(scale=0.1, size=(n_items, rank))
+    out = {}
+    for kind in ('pmf', 'kpmf'):
+        P, Q = ops.to_device(P0), ops.to_device(Q0)
+        state = (ops.zeros(n_users, rank), ops.zeros(n_items, rank))
+        if kind == 'kpmf':
+            snaps = (ops.zeros(n_users, rank), ops.zeros(n_items, rank))
+            sse = ops.kpmf_epoch(plan, P, Q, ETA, LAMBD, adjust=adjust, state=state if adjust else None, snapshots=snaps)
+        else:
+            sse = ops.pmf_epoch(plan, P, Q, ETA, LAMBD, adjust=adjust, state=state if adjust else None)
+        out[kind] = [ops.to_host(x) for x in (P, Q) + state + (sse,)]
+    for a, b in zip(out['pmf'], out['kpmf']):
+        assert np.array_equal(a, b)
+    assert np.array_equal(ops.to_host(snaps[0]), out['kpmf'][0]) and np.array_equal(ops.to_host(snaps[1]), out['kpmf'][1])
+    assert not np.array_equal(out['kpmf'][0], P0) and not np.array_equal(out['kpmf'][1], Q0)
+    assert bool(adjust) == bool(out['kpmf'][2].any())
 
 
 def test_a_second_epoch_continues_from_the_first(hip_ops):

@@ -118,6 +118,37 @@ def test_the_cached_user_sum_gives_the_same_bits(adjust):
     assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1]) and out[0][2] == out[1][2]
 
 
+def half_identity_kernels(n_users, n_items):
+    """Ku = Ki = I / 2: the diagonal is stored and nothing else, so the kernelized term (+0.0 + 0.5 * (p + p)) is p exactly"""
+    return 0.5 * sps.identity(n_users, format='csr'), 0.5 * sps.identity(n_items, format='csr')
+
+
+@pytest.mark.parametrize('adjust', [None, 'adagrad', 'rmsprop'])
+def test_half_identity_kernels_give_the_plain_sweep(adjust):
+    """the two restatements against each other on a 40 x 25 random matrix: with both kernel matrices I / 2 the kernelized
+    epoch leaves P, Q, the state and the squared error bit-equal to the PMF epoch on the same plan, and snapshots equal to P, Q"""
+    import pmf_reference
+    rng = np.random.RandomState(5)
+    dense = rng.rand(40, 25) < 0.3
+    u, i = np.nonzero(dense)
+    v = rng.randint(1, 6, size=len(u)).astype(np.float64)
+    for blocks in (1, 4):
+        plan = ref.make_plan(u, i, v, 40, 25, blocks, *half_identity_kernels(40, 25))
+        assert plan['ku_idx'].size == 0 and plan['ki_idx'].size == 0 and (plan['ku_diag'] == 0.5).all() and (plan['ki_diag'] == 0.5).all()
+        for rank in (3, 17):
+            P0, Q0 = rng.normal(scale=0.1, size=(40, rank)), rng.normal(scale=0.1, size=(25, rank))
+            out = []
+            for epoch in (pmf_reference.epoch, ref.epoch):
+                P, Q = P0.copy(), Q0.copy()
+                S = (np.zeros_like(P), np.zeros_like(Q))
+                snaps = []
+                kw = dict(snapshots=snaps) if epoch is ref.epoch else {}
+                out.append((P, Q, S[0], S[1], np.float64(epoch(plan, P, Q, 0.05, 0.5, adjust, S if adjust else None, **kw))))
+            assert all(np.array_equal(a, b) for a, b in zip(*out)), (blocks, rank)
+            assert np.array_equal(snaps[0], out[1][0]) and np.array_equal(snaps[1], out[1][1])
+            assert not np.array_equal(out[1][0], P0)
+
+
 def test_one_epoch_is_the_serial_sweep_with_snapshots():
     """the restated epoch (sample t of all blocks of a stratum at once) against a plain loop over the schedule, block after
     block, that spells the per-sample arithmetic of include/polara_hip.h out entry by entry: bit for bit"""
