@@ -1363,10 +1363,11 @@ class HipOps:
         return int(h.value), int(s.value)
 
     def score_two_phase(self, Vp, Ep, n_users, n_items, K, seen_ptr, KC, head_tiles, splits, user_bound, tile_bound,
-                        seen_tiles=None, seen_dense=None, tiles_per_chunk=0, E_rows=None, bound_out=None):
+                        seen_tiles=None, seen_dense=None, tiles_per_chunk=0, E_rows=None, bound_out=None, work=None):
         """The pruned candidate sweep in two phases (pk_score_two_phase_f32): head sweep, `splits` sweeps of the tail from
         the head's thresholds, merge.  Returns the merged (scores, ids) [n_pad x KC] — a single list per user.
-        bound_out: as in `score_candidates`."""
+        bound_out: as in `score_candidates`.  work = (float32, int32) [(splits + 1) * n_pad * KC]: the caller's arrays for the
+        raw lists (slot 0: head, then the splits) instead of scratch of the call's own — whoever wants to read them."""
         n_pad = -(-n_users // 32) * 32
         total = splits + 1
         need = self.lib.pk_score_state_bytes(n_users, total)
@@ -1376,8 +1377,13 @@ class HipOps:
         if skey not in self._score_states or self._score_states[skey].numel() < need:
             self._score_states[skey] = torch.empty(need, dtype=torch.uint8, device=self.device)
         self._score_state = self._score_states[skey]
-        ws = torch.empty(total * n_pad * KC, dtype=torch.float32, device=self.device)
-        wi = torch.empty(total * n_pad * KC, dtype=torch.int32, device=self.device)
+        if work is not None:
+            ws, wi = work
+            assert ws.dtype == torch.float32 and wi.dtype == torch.int32 and ws.is_contiguous() and wi.is_contiguous()
+            assert ws.numel() >= total * n_pad * KC and wi.numel() >= total * n_pad * KC
+        else:
+            ws = torch.empty(total * n_pad * KC, dtype=torch.float32, device=self.device)
+            wi = torch.empty(total * n_pad * KC, dtype=torch.int32, device=self.device)
         cs = torch.empty(n_pad * KC, dtype=torch.float32, device=self.device)
         ci = torch.empty(n_pad * KC, dtype=torch.int32, device=self.device)
         tiles = ntiles = dense = skip = None

@@ -4,10 +4,11 @@ and no candidate row, everybody else is appended to a device-side open list that
 The route (option "sweep_settle", default on) must give what the tier inside the re-scoring gives (option off): the same
 lists, flags, re-fold list and final list, and the same settled set — the one the numpy restatement computes.
 
-Shapes: 75 users (three groups, the last with 11 live lanes), 300 items (10 tiles, the last with 12 real items), ranks 12 and
-50 (packed fold-in pieces of 2 and 8 lanes), top-10 / KC 16 and top-20 / KC 32.  Seeds and clone counts were chosen on the
+Shapes: 75 users (three groups, the last with 11 live lanes), 300 items (10 tiles, the last with 12 real items), one rank per
+rank class of the sweep — 12, 24, 40, 50, 72, 88, 104, 120, 150, 200, 250 (ranks 12 and 50: packed fold-in pieces of 2 and 8
+lanes) — top-10 / KC 16 and top-20 / KC 32.  Seeds and clone counts were chosen on the
 CPU so that the restatement ALONE (exact scores standing in for the sweep's, R.exact_stand_in; error weights 10, 40 and 160
-fp32 roundings; with and without the seen filter) settles 33 to 54 of the 75 users and leaves 18 or more of the ordinary ones
+fp32 roundings; with and without the seen filter) settles 20 to 53 of the 75 users and leaves 18 or more of the ordinary ones
 open; every case asserts both populations again before it touches the device.
 
 Three users are constructed to stay open: one whose two best items are identical rows of V (exact tie), one with an empty
@@ -26,7 +27,13 @@ import rescore_settle_reference as R
 pytestmark = pytest.mark.gpu
 
 N_USERS, N_ITEMS = 75, 300
-CASES = {(12, 10): (11, 5), (50, 10): (11, 5), (12, 20): (11, 0), (50, 20): (11, 0)}     # (rank, topk) -> (seed, near-clone pairs)
+# (rank, topk) -> (seed, near-clone pairs): one rank per rank class of the sweep (NSTEP 1, 2, 3, 4, 5, 6, 7, 8, 10, 13, 16), each with
+# top-10 / KC 16 and top-20 / KC 32 — the 22 instances the SETTLE twin of score_candidates_kernel exists for.  On the CPU the
+# restatement alone settles 20 to 53 of the 75 users in every one of them (thinnest: rank 104 / top-20 without the seen
+# filter at the 160-rounding weight, 20 against the floor of 18.75).
+RANKS = (12, 24, 40, 50, 72, 88, 104, 120, 150, 200, 250)
+CASES = {(K, topk): (11, 5 if topk == 10 else 0) for K in RANKS for topk in (10, 20)}
+FULL_PRODUCT = ((12, 10), (12, 20), (50, 10), (50, 20))      # these take every (output order, filter) combination below
 NEAR_TWINS = (60, 120)                               # items whose right-hand neighbour becomes their near-twin
 TIE_USER, EMPTY_USER, FEW_USER = 3, 40, 70          # one per group; 70 sits among the 11 live lanes of the last one
 CONSTRUCTED = (TIE_USER, EMPTY_USER, FEW_USER)
@@ -188,9 +195,12 @@ def check_open_list(on, settled, filter_seen, constructed=CONSTRUCTED):
         assert int((lst == u).sum()) == 1, u
 
 
-@pytest.mark.parametrize('filter_seen', [True, False], ids=['filter_seen', 'no_filter'])
-@pytest.mark.parametrize('with_perm', [False, True], ids=['plain', 'out_perm'])
-@pytest.mark.parametrize('K,topk', sorted(CASES))
+ROUTE_CASES = [(K, topk, with_perm, filter_seen) for K, topk in sorted(CASES) for with_perm in (False, True) for filter_seen in (True, False)
+               if (K, topk) in FULL_PRODUCT or (with_perm, filter_seen) in ((False, True), (True, False))]
+
+
+@pytest.mark.parametrize('K,topk,with_perm,filter_seen', ROUTE_CASES,
+                         ids=['%d-%d-%s-%s' % (K, topk, 'out_perm' if p else 'plain', 'filter_seen' if f else 'no_filter') for K, topk, p, f in ROUTE_CASES])
 def test_route_equals_the_tier_of_the_first_rescoring(hip_ops, pk_options, monkeypatch, K, topk, with_perm, filter_seen):
     ops = hip_ops
     K, topk, KC, V, ip, ix, va, same = case(K, topk)
