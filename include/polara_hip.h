@@ -80,7 +80,7 @@ int pk_spmm_csr_f64(void *stream,
 /* Same product with the dense block X given in fp32 (x_kind = PK_VAL_F32; needs nc % 4 == 0, ldx % 4 == 0,
  * 16-byte aligned X) or fp64 (PK_VAL_F64 = pk_spmm_csr_f64).  Accumulation and output are fp64.  Used for the
  * approximate fold-in of the scoring pass: E' = A_test fl32(V) moves half the gather bytes of models.py:860's
- * left factor; the re-scoring kernel certifies the result against the rounding of V (pk_rescore_topk_f64). */
+ * left factor; the re-scoring kernel certifies the result against the rounding of V (pk_rescore_f64). */
 int pk_spmm_csr_x(void *stream,
                   int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
                   const int64_t *task_end_dev, const int32_t *task_slot_dev,
@@ -271,7 +271,7 @@ int32_t pk_candidate_capacity(int32_t topk);
  * idx -1.  `splits` = S > 1 deals the 32-item tiles of the catalogue round-robin to S sweeps per user group
  * (split h takes tiles h, h+S, ...), each with its own wave and threshold (more, smaller work items when
  * there are few users; interleaved so that every sweep meets the high-norm head first and the exact pruning
- * keeps working); the per-split lists are merged by pk_rescore_topk_f64.
+ * keeps working); the per-split lists are merged by pk_rescore_f64.
  * seen lists must be sorted ascending per user (CSR canonical form).
  * The item range is swept in chunks of `tiles_per_chunk` 32-item tiles, one launch per chunk, so the
  * packed item factors of a chunk stay resident in the 4 MiB per-XCD L2 while every workgroup streams
@@ -282,7 +282,7 @@ int32_t pk_candidate_capacity(int32_t topk);
  * KC / 2 largest group maxima in a sorted register list — and starts from the smallest of a user's KC values, a lower
  * bound of its final KC-th best score: a quarter of the pushes and flush sorts of a cold start (pk_set_option
  * "score_boot_tiles" overrides; 0 = off).  Should such a sweep end without a full list, the last slot of the list holds idx -2 and
- * pk_rescore_topk_* sends the user to the exact path. */
+ * pk_rescore_f64 sends the user to the exact path. */
 int64_t pk_score_state_bytes(int64_t n_users, int32_t splits);
 /* recommended number of item splits for this many users (1 when the users alone fill the chip) */
 int32_t pk_score_splits(int64_t n_users, int32_t KC);
@@ -324,7 +324,7 @@ int pk_score_candidates_rows_f32(void *stream, int64_t n_users, int64_t n_items,
                                  const float *tile_bound_dev /* or NULL */, const uint32_t *seen_dense_dev,
                                  const int32_t *seen_skip_dev, int32_t dense_tiles);
 /* ... and the users' side of the pruning bound left in user_bound_out_dev (float [n_users], or NULL): bound_u above, an
- * upper bound of ||E_u|| — four bytes per user, stored by the sweep's prologue, for pk_rescore_topk_rows_settle_f64. */
+ * upper bound of ||E_u|| — four bytes per user, stored by the sweep's prologue, for pk_rescore_f64. */
 int pk_score_candidates_rows_bound_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
                                        const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
                                        double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
@@ -332,7 +332,7 @@ int pk_score_candidates_rows_bound_f32(void *stream, int64_t n_users, int64_t n_
                                        int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk /* 0 = auto */,
                                        const float *tile_bound_dev /* or NULL */, const uint32_t *seen_dense_dev,
                                        const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev);
-/* ... and the settle rule of the first re-scoring (pk_rescore_topk_rows_settle_f64) applied where a group of 32 users LEAVES the
+/* ... and the settle rule of the first re-scoring (pk_rescore_f64) applied where a group of 32 users LEAVES the
  * sweep, to the final sorted lists the wave still holds: single sweep (one list per user), KC = 16 or 32, pruning bound and
  * error weights (extra_dev) required.  A user whose order the sweep's own scores decide is SETTLED: its topk ids go to row u
  * of out_idx (row out_perm[u] when given), flags[u] = 8, and its row of cand_score / cand_idx is NOT written (stale).  Every
@@ -367,7 +367,7 @@ int pk_score_candidates_rows_settle_f32(void *stream, int64_t n_users, int64_t n
  * round-robin to `splits` sweeps per group that all START from the head's threshold (a score below it cannot be among
  * the KC best, whatever a split's own list holds), and the splits + 1 lists of a user are merged into ONE list of KC
  * candidates with exact comparisons: the dependent chain of a group is head + tail / splits tiles at the same number
- * of tile-waves.  The merged list is what pk_rescore_topk_* takes with splits = 1.
+ * of tile-waves.  The merged list is what pk_rescore_f64 takes with splits = 1.
  *   work_*   [(splits + 1)][n_users_pad][KC] raw lists;  cand_*  [n_users_pad][KC] merged;
  *   state    pk_score_state_bytes(n_users, splits + 1): records of slot 0 = the head, slots 1.. = the splits (first int64
  *            of a record: the tile at which the group left that sweep; a head exit below head_tiles means the group was
@@ -415,7 +415,7 @@ int32_t pk_score_chunk_launches(int64_t n_items, int32_t K, int32_t splits, int3
  * The reference scores every item for every user (models.py:860); the sweep may instead stop, per
  * group of 32 users, at the first tile from which  ||E_u|| * max_{i >= tile} ||V_i||  can no longer
  * beat the user's current KC-th best score.  Both bounds are rounded UP, so the candidate lists — and
- * the certification done by pk_rescore_topk_f64 — are exactly those of the full sweep.
+ * the certification done by pk_rescore_f64 — are exactly those of the full sweep.
  *   pk_row_norm_bound_f32:  out[r] >= ||src[r,:]||_2                       (user_bound from E)
  *   pk_tile_norm_bound_f32: out[t] >= max_{i >= 32 t} ||V[i,:]||_2         (tile_bound; work: float[n_items])
  * The bound falls fastest when the internal item order is by descending popularity or norm. */
@@ -435,90 +435,39 @@ int pk_pack_frag_bound_f32(void *stream, int64_t n, int32_t K, const double *src
                            float *bound_dev, const double *extra_dev, int64_t extra_ld, double extra_scale);
 int pk_tile_norm_bound_f32(void *stream, int64_t n_items, int32_t K, const double *V_dev, int64_t ld,
                            float *work_dev, float *out_dev);
-/* Exact fp64 re-scoring + final ordering (score desc, item asc).  Writes topk item ids (int64) and
+/* Exact fp64 re-scoring + final ordering (score desc, item asc) of the candidate lists: ONE entry.  Every choice is an
+ * argument (NULL = not used) and nothing is kept between two calls.  Writes topk item ids (int64) and
  * optionally their fp64 scores.  flags[u] != 0 marks users whose result is NOT guaranteed exact by
  * the fp32 candidate pass (bit0: candidate margin below the fp32 error bound; bit1: fewer than
- * topk unseen items) — the host re-runs those through pk_score_exact_rows_f64.
- * v_row_norm_max = max_i ||V[i,:]||_2 (<= 1 for orthonormal factors) enters the fp32 error bound. */
-int pk_rescore_topk_f64(void *stream, int64_t n_users, int64_t n_items, int32_t K,
-                        const double *V_dev, int64_t ldv, const double *E_dev, int64_t lde,
-                        const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                        const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                        double v_row_norm_max,
-                        int64_t *out_idx_dev, double *out_score_dev /* or NULL */, int32_t *flags_dev);
-/* General form: the r-th row processed is user rows_dev[r] (NULL: user r, n_rows = n_users) — used to re-do a
- * list of users; e_err_dev (or NULL): per-user bound w_u such that the given E rows satisfy
+ * topk unseen items) — those are re-run through pk_score_exact_rows_f64 / pk_score_exact_list_f64.
+ * v_row_norm_max = max_i ||V[i,:]||_2 (<= 1 for orthonormal factors) enters the fp32 error bound.
+ * The plain call over everybody with exact E rows: n_rows = n_users, e_exact = 0, flagged_offset = 0, ldv32 = e_err_ld = 0 and
+ * every optional pointer (rows, n_rows, V32, e_err, out_score, flagged_list / _count, item_norm, out_perm, user_norm) NULL.
+ *
+ * rows_dev: the r-th row processed is user rows_dev[r] (NULL: user r, n_rows = n_users) — used to re-do a
+ * list of users; n_rows_dev (or NULL): the list length is then min(*n_rows_dev, n_rows), read on the device.
+ * e_err_dev (or NULL): per-user bound w_u (that of user u at e_err_dev[u * e_err_ld]) such that the given E rows satisfy
  * ||E'_u - E_u|| <= 2^-24 w_u (the approximate fold-in against fl32(V): w_u = sum_j |a_uj| ||V_j||).  Scores are
  * then within delta_u = 2^-24 w_u max||V_i|| of the exact ones, and flags bit2 (value 4) marks the users whose
  * order is NOT certified at that accuracy (two consecutive scores of the top-k, or the k-th and the best
- * excluded item, closer than 2 delta_u): the host recomputes their E rows exactly and calls again with
- * e_exact = 1 (the same e_err_dev: the non-candidates are still only known through the approximate sweep).
+ * excluded item, closer than 2 delta_u): the caller recomputes their E rows exactly and calls again with
+ * e_exact = 1 (these E rows are exact, the candidates came from a sweep over approximate ones; the same e_err_dev: the
+ * non-candidates are still only known through the approximate sweep).
  * V32_dev (or NULL): fl32 image of the item factors [n_items x ldv32]; used INSTEAD of V_dev in a first call over
  * approximate E rows (e_err_dev given, e_exact = 0) — half the cache lines per gathered row; its rounding,
- * 2^-24 ||E'_u|| max||V_i||, is added to delta_u.  Ignored when the E rows are exact. */
-int pk_rescore_topk_rows_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
-                             const int32_t *n_rows_dev /* or NULL; else the list length is min(*n_rows_dev, n_rows) */,
-                             int64_t n_users, int64_t n_items,
-                             int32_t K, const double *V_dev, int64_t ldv,
-                             const float *V32_dev /* or NULL */, int64_t ldv32,
-                             const double *E_dev, int64_t lde,
-                             const double *e_err_dev, int64_t e_err_ld /* e_err of user u at e_err_dev[u * e_err_ld] */,
-                             int32_t e_exact /* 1: these E rows are exact, the candidates came
-                             from a sweep over approximate ones (second call) */,
-                             const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                             double v_row_norm_max,
-                             int64_t *out_idx_dev, double *out_score_dev /* or NULL */, int32_t *flags_dev);
-/* The same, and the users it flags are appended to a device-side list while it runs: flagged_list_dev[old *count ...] =
- * flagged_offset + user for every user whose flag is not 0 (order arbitrary), *flagged_count_dev advanced by an atomic —
- * what pk_flag_compact(mask = all) makes of the flags afterwards, without its two launches.  The counter is NOT zeroed
- * here (several calls may append to one list: user batches): pk_zero_i32 (n <= 2^20 counters, a kernel) first.
- * list / count both NULL: plain pk_rescore_topk_rows_f64. */
-int pk_rescore_topk_rows_list_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
-                             const int32_t *n_rows_dev /* or NULL; else the list length is min(*n_rows_dev, n_rows) */,
-                             int64_t n_users, int64_t n_items,
-                             int32_t K, const double *V_dev, int64_t ldv,
-                             const float *V32_dev /* or NULL */, int64_t ldv32,
-                             const double *E_dev, int64_t lde,
-                             const double *e_err_dev, int64_t e_err_ld /* e_err of user u at e_err_dev[u * e_err_ld] */,
-                             int32_t e_exact /* 1: these E rows are exact, the candidates came
-                             from a sweep over approximate ones (second call) */,
-                             const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                             double v_row_norm_max,
-                             int64_t *out_idx_dev, double *out_score_dev /* or NULL */, int32_t *flags_dev,
-                             int32_t *flagged_list_dev, int32_t *flagged_count_dev, int32_t flagged_offset);
-/* The same with the items' own norm bounds: item_norm_dev[i] >= ||V_i|| (fp32, e.g. pk_row_norm_bound_f32) — the order of
- * two neighbouring entries is then certified against cu (||V_i|| + ||V_i'||) instead of 2 cu max ||V||
- * (cu = 2^-24 (e_err[u] + ||E'_u||)): fewer users to re-fold for the same proof.  NULL: pk_rescore_topk_rows_list_f64. */
-int pk_rescore_topk_rows_norms_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
-                             const int32_t *n_rows_dev, int64_t n_users, int64_t n_items,
-                             int32_t K, const double *V_dev, int64_t ldv,
-                             const float *V32_dev, int64_t ldv32,
-                             const double *E_dev, int64_t lde,
-                             const double *e_err_dev, int64_t e_err_ld, int32_t e_exact,
-                             const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                             double v_row_norm_max,
-                             int64_t *out_idx_dev, double *out_score_dev, int32_t *flags_dev,
-                             int32_t *flagged_list_dev, int32_t *flagged_count_dev, int32_t flagged_offset,
-                             const float *item_norm_dev);
-/* ... and with out_perm_dev (int64 [n_users], or NULL): the out_idx row of user u is written to row out_perm_dev[u]; the rows
+ * 2^-24 ||E'_u|| max||V_i||, is added to delta_u.  Ignored when the E rows are exact.
+ * flagged_list_dev / flagged_count_dev (both or neither): the users the call flags are appended to a device-side list while
+ * it runs: flagged_list_dev[old *count ...] = flagged_offset + user for every user whose flag is not 0 (order arbitrary),
+ * *flagged_count_dev advanced by an atomic — what pk_flag_compact(mask = all) makes of the flags afterwards, without its
+ * two launches.  The counter is NOT zeroed here (several calls may append to one list: user batches): pk_zero_i32
+ * (n <= 2^20 counters, a kernel) first.
+ * item_norm_dev (or NULL): the items' own norm bounds, item_norm_dev[i] >= ||V_i|| (fp32, e.g. pk_row_norm_bound_f32) — the
+ * order of two neighbouring entries is then certified against cu (||V_i|| + ||V_i'||) instead of 2 cu max ||V||
+ * (cu = 2^-24 (e_err[u] + ||E'_u||)): fewer users to re-fold for the same proof.
+ * out_perm_dev (int64 [n_users], or NULL): the out_idx row of user u is written to row out_perm_dev[u]; the rows
  * of out_score and flags stay where they are.  A pass that sweeps its users in another order than the caller's then needs
- * no pk_scatter_rows_i64 behind it. */
-int pk_rescore_topk_rows_perm_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
-                             const int32_t *n_rows_dev, int64_t n_users, int64_t n_items,
-                             int32_t K, const double *V_dev, int64_t ldv,
-                             const float *V32_dev, int64_t ldv32,
-                             const double *E_dev, int64_t lde,
-                             const double *e_err_dev, int64_t e_err_ld, int32_t e_exact,
-                             const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                             double v_row_norm_max,
-                             int64_t *out_idx_dev, double *out_score_dev, int32_t *flags_dev,
-                             int32_t *flagged_list_dev, int32_t *flagged_count_dev, int32_t flagged_offset,
-                             const float *item_norm_dev, const int64_t *out_perm_dev);
-/* ... and with the SETTLE TIER: user_norm_dev (float [n_users], or NULL = the call above) holds N_u >= ||E'_u||, the users'
+ * no pk_scatter_rows_i64 behind it.
+ * user_norm_dev (float [n_users], or NULL): the SETTLE TIER.  It holds N_u >= ||E'_u||, the users'
  * side of the sweep's pruning bound (pk_pack_frag_bound_f32's bound_dev, or what pk_score_*_rows_bound_f32 stored).  Active
  * only on the first call over an approximate E — V32_dev and e_err_dev given, e_exact = 0, rows_dev = NULL.  The sweep's
  * fp32 score of an item is within d_i = (B N_u + 2^-24 e_err[u]) n_i of its exact score, B = 3 * 2^-16 + (4 K + 10) * 2^-23,
@@ -527,32 +476,24 @@ int pk_rescore_topk_rows_perm_f64(void *stream, int64_t n_rows, const int32_t *r
  * bound on the items the sweep left out (tau_cert: d_topk + d at n = v_row_norm_max) is SETTLED: its ids are written in that
  * order — the exact one — without gathering an item row or reading its row of E; flags[u] = 8 (above the mask 7 of the
  * lists: such a user is on no list), its out_score row is not written.  Ties, unbounded lists and users with fewer than
- * topk unseen items never settle and take the path of the call above, bit for bit.
+ * topk unseen items never settle and take the path of a call without user_norm_dev, bit for bit.
  * pk_set_option("rescore_settle", 0) switches the tier off in every call. */
-int pk_rescore_topk_rows_settle_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
-                             const int32_t *n_rows_dev, int64_t n_users, int64_t n_items,
-                             int32_t K, const double *V_dev, int64_t ldv,
-                             const float *V32_dev, int64_t ldv32,
-                             const double *E_dev, int64_t lde,
-                             const double *e_err_dev, int64_t e_err_ld, int32_t e_exact,
-                             const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                             double v_row_norm_max,
-                             int64_t *out_idx_dev, double *out_score_dev, int32_t *flags_dev,
-                             int32_t *flagged_list_dev, int32_t *flagged_count_dev, int32_t flagged_offset,
-                             const float *item_norm_dev, const int64_t *out_perm_dev, const float *user_norm_dev);
-/* The same pointer for a caller that keeps to the older entries above (a recorded call sequence that is fixed): the bound
- * is left with the stream FOR ONE CALL.  The next call of pk_rescore_topk_rows_perm_f64 (or of an entry that forwards to it)
- * on that stream takes it as its user_norm_dev if it is the call named — same n_users, same flags_dev — and drops it
- * otherwise; the binding is gone afterwards either way, also when that call fails.  NULL clears a pending one.  Host-side
- * bookkeeping (thread-safe), nothing is enqueued.  This is state between two calls: bind immediately in front of the call
- * it is meant for, keep the array alive until that call is issued, and prefer pk_rescore_topk_rows_settle_f64, which takes
- * the pointer as an argument, wherever the entry is free to choose. */
-int pk_rescore_bind_user_norm(void *stream, const float *user_norm_dev, int64_t n_users, const int32_t *flags_dev);
+int pk_rescore_f64(void *stream, int64_t n_rows, const int32_t *rows_dev, const int32_t *n_rows_dev,
+                   int64_t n_users, int64_t n_items,
+                   int32_t K, const double *V_dev, int64_t ldv,
+                   const float *V32_dev, int64_t ldv32,
+                   const double *E_dev, int64_t lde,
+                   const double *e_err_dev, int64_t e_err_ld, int32_t e_exact,
+                   const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
+                   const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
+                   double v_row_norm_max,
+                   int64_t *out_idx_dev, double *out_score_dev, int32_t *flags_dev,
+                   int32_t *flagged_list_dev, int32_t *flagged_count_dev, int32_t flagged_offset,
+                   const float *item_norm_dev, const int64_t *out_perm_dev, const float *user_norm_dev);
 int pk_zero_i32(void *stream, int32_t *p_dev, int32_t n);
 /* The re-do of flagged users without a host round trip: pk_flag_compact lists the users with (flags & mask) != 0
  * (list capacity n, *count_dev = list length), pk_fold_rows_f64 recomputes the listed rows of E = A_test V in fp64
- * straight from the CSR (row = row_offset + list[r]), pk_rescore_topk_rows_f64 re-scores them (rows_dev = the list,
+ * straight from the CSR (row = row_offset + list[r]), pk_rescore_f64 re-scores them (rows_dev = the list,
  * n_rows_dev = count_dev).  All three take the list length from device memory. */
 int pk_flag_compact(void *stream, int64_t n, const int32_t *flags_dev, int32_t mask, int32_t *list_dev,
                     int32_t *count_dev);
@@ -562,7 +503,7 @@ int pk_fold_rows_f64(void *stream, int64_t cap, const int32_t *list_dev, const i
 
 /* The product restricted to FLAGGED rows: only the tasks of rows r with (row_flags_dev[r] & flag_mask) != 0 run, every
  * other row of `out` is left alone.  The exact re-fold of the users an ids-only pass could not certify at the accuracy
- * of its approximate fold-in (pk_rescore_topk_rows_list_f64 leaves the flags on the device): same plan, mapping and
+ * of its approximate fold-in (pk_rescore_f64 leaves the flags on the device): same plan, mapping and
  * summation order as pk_spmm_csr_ex with an fp64 dense block, so a re-folded row has the bits of the exact product.
  * Even nc and ldx, X 16-byte aligned (odd ranks: pk_fold_rows_f64). */
 int pk_spmm_csr_flagged_f64(void *stream, int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
@@ -590,7 +531,7 @@ int pk_spmm_csr_rows_list_f64(void *stream, int64_t cap, const int32_t *list_dev
  * (csrc/foldq.hip): E'[u, 0:K] = sum_j a_uj decode(image row j), E'[u, K] = w_u = sum_j a_uj D_j with
  * ||E'_u - E_u|| <= 2^-24 w_u PROVEN (D_j is computed by the encoder from the bits it wrote), columns K+1 .. Kx-1 = 0.
  * Replaces `test_matrix.dot(v)` (models.py:857-860) wherever the pass certifies its lists against that bound
- * (pk_rescore_topk_rows_list_f64 with e_err = column K; users it cannot certify are re-folded in fp64 by
+ * (pk_rescore_f64 with e_err = column K; users it cannot certify are re-folded in fp64 by
  * pk_fold_rows_f64).  A rank-K row takes pk_q20_lanes(K) * 16 bytes (128 for K <= 50: ONE cache line per gathered
  * entry where the fp32 image takes two); ranks above 202 have no packed image (pk_q20_lanes returns 0).
  * pk_q20_encode_f64: V [n x K] fp64 row-major -> image (pk_q20_image_bytes, 128-byte aligned), the bracket scale table
@@ -642,16 +583,13 @@ int pk_score_exact_rows_f64(void *stream, int32_t n_rows, const int32_t *rows_de
  * of those users in the [n_users x topk] outputs.  One launch; n_wg row slots (work >= pk_exact_work_bytes(n_wg, n_items),
  * prepared ONCE with pk_exact_work_init(stream, work, n_wg, n_items): the buffer ends in one int32 ticket per row slot that
  * must be zero at the first use and that every call leaves zero); the list never visits the host, so a scoring pass needs
- * no synchronisation.  A buffer serves one stream at a time.  _perm: out_perm_dev as in pk_rescore_topk_rows_perm_f64. */
+ * no synchronisation.  A buffer serves one stream at a time.  out_perm_dev (or NULL: rows stay where they are) as in
+ * pk_rescore_f64. */
 int pk_exact_work_init(void *stream, void *work_dev, int32_t n_rows, int64_t n_items);
-int pk_score_exact_list_perm_f64(void *stream, int32_t n_wg, const int32_t *list_dev, const int32_t *count_dev, int64_t n_items,
-                                 int32_t K, const double *V_dev, int64_t ldv, const double *E_dev, int64_t lde,
-                                 const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev, int32_t topk, int64_t *out_idx_dev,
-                                 double *out_score_dev, void *work_dev, const int64_t *out_perm_dev);
 int pk_score_exact_list_f64(void *stream, int32_t n_wg, const int32_t *list_dev, const int32_t *count_dev, int64_t n_items,
                             int32_t K, const double *V_dev, int64_t ldv, const double *E_dev, int64_t lde,
                             const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev, int32_t topk, int64_t *out_idx_dev,
-                            double *out_score_dev, void *work_dev);
+                            double *out_score_dev, void *work_dev, const int64_t *out_perm_dev);
 /* Evaluation support (models.py:408-485, evaluation.py:24-44 `build_rank_matrix` restricted to the holdout):
  * rank_out[e] = 1-based position of hold_item[e] in row hold_row[e] of the device-resident [n_users x topk]
  * recommendation array, 0 if absent.  Every hit/rank metric is a reduction of this holdout-sized vector. */

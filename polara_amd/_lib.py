@@ -100,8 +100,6 @@ PROTOTYPES = {
     'pk_pack_frag_bound_f32': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _f64]),
     'pk_row_norm_bound_f32': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp]),
     'pk_tile_norm_bound_f32': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
-    'pk_rescore_topk_f64': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp,
-                                      _i32, _f64, _vp, _vp, _vp]),
     'pk_flag_compact': (C.c_int, [_vp, _i64, _vp, _i32, _vp, _vp]),
     'pk_fold_rows_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, C.c_int, _vp, _i64, _i32, _vp, _i64]),
     'pk_spmm_csr_flagged_f64': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _i64, _i32,
@@ -117,17 +115,8 @@ PROTOTYPES = {
                               _vp, _i64, _vp]),
     'pk_fold_q20_zero': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _i64, _i32, _i32,
                                    _vp, _i64, _vp, _vp, _i32]),
-    'pk_rescore_topk_rows_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
-                                           _vp, _vp, _i32, _f64, _vp, _vp, _vp]),
-    'pk_rescore_topk_rows_list_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
-                                           _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),
-    'pk_rescore_topk_rows_norms_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
-                                           _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
-    'pk_rescore_topk_rows_perm_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
-                                           _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
-    'pk_rescore_topk_rows_settle_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
-                                           _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
-    'pk_rescore_bind_user_norm': (C.c_int, [_vp, _vp, _i64, _vp]),
+    'pk_rescore_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
+                                 _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     'pk_zero_i32': (C.c_int, [_vp, _vp, _i32]),
     'pk_scatter_rows_i64': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     'pk_map_ids_i64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
@@ -135,9 +124,7 @@ PROTOTYPES = {
     'pk_score_exact_rows_f64': (C.c_int, [_vp, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32,
                                           _vp, _vp, _vp]),
     'pk_score_exact_list_f64': (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32,
-                                          _vp, _vp, _vp]),
-    'pk_score_exact_list_perm_f64': (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32,
-                                               _vp, _vp, _vp, _vp]),
+                                          _vp, _vp, _vp, _vp]),
     'pk_exact_work_init': (C.c_int, [_vp, _vp, _i32, _i64]),
     'pk_eval_ranks': (C.c_int, [_vp, _i64, _vp, _i32, _vp, _vp, _vp]),
     'pk_eval_cols': (_i32, []),

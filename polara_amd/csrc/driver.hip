@@ -2074,7 +2074,7 @@ int serving_score(pk_ctx *ctx, pk_serving *sv, int32_t topk, int32_t filter_seen
         CK(spmm(ctx, Ts, V.p(), PK_VAL_F64, K, K, E.p(), K, all));
         hipLaunchKernelGGL(iota_i32_kernel, dim3((unsigned)((n_users + 255) / 256)), dim3(256), 0, st, n_users, lst.as<int32_t>(), cnt.as<int32_t>());
         CK(pk_score_exact_list_f64(st, n_wg, lst.as<int32_t>(), cnt.as<int32_t>(), n_items, K, V.p(), K, E.p(), K, seen_ptr, seen_idx, topk,
-                                   out_i.as<int64_t>(), out_s.as<double>(), exact_work.p));
+                                   out_i.as<int64_t>(), out_s.as<double>(), exact_work.p, nullptr));
         HIPCK(hipStreamSynchronize(st));
     } else {
         const bool approx = !out_scores && sv->have_v32;
@@ -2161,11 +2161,12 @@ int serving_score(pk_ctx *ctx, pk_serving *sv, int32_t topk, int32_t filter_seen
         // the re-fold list (lst), cnt2[1] the final list for the exact-row kernel (lst2)
         if (!counters_zeroed) CK(pk_zero_i32(st, cnt2.as<int32_t>(), 2));
         int32_t *c_refold = cnt2.as<int32_t>(), *c_final = cnt2.as<int32_t>() + 1;
-        CK(pk_rescore_topk_rows_norms_f64(st, n_users, nullptr, nullptr, n_users, n_items, K, V.p(), K, approx ? sv->V32.as<float>() : nullptr, approx ? ld32 : 0,
-                                          Ex.p(), Kx, w, approx ? Kx : 0, 0, seen_ptr, KC, splits, cs.as<float>(), ci.as<int32_t>(), topk, vmax,
-                                          out_i.as<int64_t>(), out_s.as<double>(), flags.as<int32_t>(),
-                                          approx ? lst.as<int32_t>() : lst2.as<int32_t>(), approx ? c_refold : c_final, 0,
-                                          approx ? sv->vnorm.as<float>() : nullptr));
+        // (no out_perm: the lists are in serving order already; no user_norm: this pass runs without the settle tier)
+        CK(pk_rescore_f64(st, n_users, nullptr, nullptr, n_users, n_items, K, V.p(), K, approx ? sv->V32.as<float>() : nullptr, approx ? ld32 : 0,
+                          Ex.p(), Kx, w, approx ? Kx : 0, 0, seen_ptr, KC, splits, cs.as<float>(), ci.as<int32_t>(), topk, vmax,
+                          out_i.as<int64_t>(), out_s.as<double>(), flags.as<int32_t>(),
+                          approx ? lst.as<int32_t>() : lst2.as<int32_t>(), approx ? c_refold : c_final, 0,
+                          approx ? sv->vnorm.as<float>() : nullptr, nullptr, nullptr));
         if (approx) {
             // the exact re-fold of the listed users on the product's own row tasks (scoring.py: ops.spmm_rows_list)
             // (even ranks; odd ones keep the one-workgroup-per-row kernel)
@@ -2181,12 +2182,12 @@ int serving_score(pk_ctx *ctx, pk_serving *sv, int32_t topk, int32_t filter_seen
             } else
             CK(pk_fold_rows_f64(st, n_users, lst.as<int32_t>(), c_refold, 0, Ts.indptr.as<int64_t>(), Ts.indices.as<int32_t>(), Ts.values.p,
                                 Ts.val_kind, V.p(), K, K, Ex.p(), Kx));
-            CK(pk_rescore_topk_rows_list_f64(st, n_users, lst.as<int32_t>(), c_refold, n_users, n_items, K, V.p(), K, nullptr, 0, Ex.p(), Kx, w, Kx,
-                                             1, seen_ptr, KC, splits, cs.as<float>(), ci.as<int32_t>(), topk, vmax, out_i.as<int64_t>(), out_s.as<double>(),
-                                             flags.as<int32_t>(), lst2.as<int32_t>(), c_final, 0));
+            CK(pk_rescore_f64(st, n_users, lst.as<int32_t>(), c_refold, n_users, n_items, K, V.p(), K, nullptr, 0, Ex.p(), Kx, w, Kx,
+                              1, seen_ptr, KC, splits, cs.as<float>(), ci.as<int32_t>(), topk, vmax, out_i.as<int64_t>(), out_s.as<double>(),
+                              flags.as<int32_t>(), lst2.as<int32_t>(), c_final, 0, nullptr, nullptr, nullptr));
         }
         CK(pk_score_exact_list_f64(st, n_wg, lst2.as<int32_t>(), c_final, n_items, K, V.p(), K, Ex.p(), Kx, seen_ptr, seen_idx, topk,
-                                   out_i.as<int64_t>(), out_s.as<double>(), exact_work.p));
+                                   out_i.as<int64_t>(), out_s.as<double>(), exact_work.p, nullptr));
         HIPCK(hipStreamSynchronize(st));   // every temporary above is still alive here
     }
     // serving order -> the caller's item ids on the device, then one transfer into the caller's array

@@ -2336,7 +2336,7 @@ extern "C" int pk_score_two_phase_plan(int64_t n_users, int64_t n_items, int32_t
 // dealt round-robin to `splits` sweeps per group that start from the head's thresholds, then the merge.  Needs the
 // pruning bounds (without them nobody leaves early and a single sweep is the shortest chain there is).
 //   work_score / work_idx  [(splits + 1) * n_pad * KC]   the raw lists (slot 0: head), n_pad = n_users rounded up to 32
-//   cand_score / cand_idx  [n_pad * KC]                   the merged list: what pk_rescore_topk_* takes with splits = 1
+//   cand_score / cand_idx  [n_pad * KC]                   the merged list: what pk_rescore_f64 takes with splits = 1
 //   state                  pk_score_state_bytes(n_users, splits + 1)
 extern "C" int pk_score_two_phase_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K,
                                       const float *Vp_dev, const float *Ep_dev, const int64_t *seen_ptr_dev,

@@ -13,8 +13,6 @@
 #include "pk_settle.h"   // pk_bitonic_seg, pk_sweep_err_coeff, PK_FLAG_SETTLED: shared with the sweep's exit (score.hip)
 #include <math.h>
 #include <stdlib.h>
-#include <mutex>
-#include <unordered_map>
 
 // ---- the ONE summation order of every exact fp64 score in this file ---------------------------------
 // The K products are dealt to four chains by element PAIR: pair p = (2p, 2p+1) goes to chain p & 3, each
@@ -94,7 +92,7 @@ __device__ __forceinline__ double pk_dot_chains(const double *__restrict__ vr, c
     return s;
 }
 
-// Approximate score against the fp32 image of an item row (pk_rescore_topk_rows_f64 with V32_dev): lane q of
+// Approximate score against the fp32 image of an item row (pk_rescore_f64 with V32_dev): lane q of
 // LPC takes the 16-byte pieces (four elements) q, q + LPC, ... of the row, fp64 fma chains, any order — these
 // scores are only trusted to within the delta the caller adds for them, never returned as exact ones.
 template <int LPC>
@@ -351,159 +349,38 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
 // written, flags[u] = 8, no out_score row, on no list (see the kernel).  pk_set_option("rescore_settle", 0) switches it off.
 // out_perm_dev (int64 [n_users], may be NULL): the out_idx row of user u is written to row out_perm[u] (out_score and flags
 // rows stay where they are) — the pass then needs no scatter of its lists at the end
-//
-// The same pointer for a caller that keeps to the older entries of the family (a host layer whose recorded call sequence is
-// fixed): pk_rescore_bind_user_norm(stream, p, n_users, flags_dev) leaves p with the stream FOR ONE CALL — the next call of
-// an older entry on that stream takes it as its user_norm_dev if it is the call named (same n_users, same flags_dev) and
-// drops it otherwise; either way the binding is gone afterwards, also when that call fails its argument checks.  Host-side
-// bookkeeping only (a mutex and a map by stream handle): nothing is enqueued, captures and replays see two ordinary calls.
-// What is left of the hazard of state between calls: a binding whose call never comes stays until the next older-entry
-// call on the stream, which drops it unless it writes the same flags buffer for the same number of users — bind
-// immediately in front of the call, and pass the pointer to pk_rescore_topk_rows_settle_f64 wherever the entry is free.
-namespace {
-struct NormBinding { const float *ptr; int64_t n_users; const int32_t *flags; };
-std::mutex g_norm_mu;
-std::unordered_map<void *, NormBinding> g_norm_bound;
-}
-extern "C" int pk_rescore_bind_user_norm(void *stream, const float *user_norm_dev, int64_t n_users, const int32_t *flags_dev) {
-    std::lock_guard<std::mutex> lock(g_norm_mu);
-    if (user_norm_dev) g_norm_bound[stream] = NormBinding{user_norm_dev, n_users, flags_dev};
-    else g_norm_bound.erase(stream);
-    return PK_OK;
-}
-static const float *pk_take_user_norm(void *stream, int64_t n_users, const int32_t *flags_dev) {
-    std::lock_guard<std::mutex> lock(g_norm_mu);
-    const auto it = g_norm_bound.find(stream);
-    if (it == g_norm_bound.end()) return nullptr;
-    const NormBinding nb = it->second;
-    g_norm_bound.erase(it);
-    return (nb.n_users == n_users && nb.flags == flags_dev) ? nb.ptr : nullptr;
-}
-
-extern "C" int pk_rescore_topk_rows_settle_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
-                                            const int32_t *n_rows_dev, int64_t n_users,
-                                            int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
-                                            const float *V32_dev, int64_t ldv32,
-                                            const double *E_dev, int64_t lde, const double *e_err_dev,
-                                            int64_t e_err_ld, int32_t e_exact,
-                                            const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                                            const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                                            double v_row_norm_max, int64_t *out_idx_dev, double *out_score_dev,
-                                            int32_t *flags_dev, int32_t *flagged_list_dev, int32_t *flagged_count_dev,
-                                            int32_t flagged_offset, const float *item_norm_dev, const int64_t *out_perm_dev,
-                                            const float *user_norm_dev) {
+// Every choice is an argument of this one entry: nothing is kept between two calls.
+extern "C" int pk_rescore_f64(void *stream, int64_t n_rows, const int32_t *rows_dev, const int32_t *n_rows_dev, int64_t n_users,
+                              int64_t n_items, int32_t K, const double *V_dev, int64_t ldv, const float *V32_dev, int64_t ldv32,
+                              const double *E_dev, int64_t lde, const double *e_err_dev, int64_t e_err_ld, int32_t e_exact,
+                              const int64_t *seen_ptr_dev, int32_t KC, int32_t splits, const float *cand_score_dev,
+                              const int32_t *cand_idx_dev, int32_t topk, double v_row_norm_max, int64_t *out_idx_dev,
+                              double *out_score_dev, int32_t *flags_dev, int32_t *flagged_list_dev, int32_t *flagged_count_dev,
+                              int32_t flagged_offset, const float *item_norm_dev, const int64_t *out_perm_dev,
+                              const float *user_norm_dev) {
     if (user_norm_dev && !pk_option("rescore_settle", 1)) user_norm_dev = nullptr;
-    PK_REQUIRE((flagged_list_dev == nullptr) == (flagged_count_dev == nullptr), "pk_rescore_topk_f64: flagged list without its counter");
-    PK_REQUIRE(n_users >= 1 && K >= 1 && K <= 256 && ldv >= K && lde >= K, "pk_rescore_topk_f64: bad sizes");
-    PK_REQUIRE(n_rows >= 0 && n_rows <= n_users, "pk_rescore_topk_f64: bad row count");
-    PK_REQUIRE(V32_dev == nullptr || ldv32 >= K, "pk_rescore_topk_f64: ldv32 < K");
+    PK_REQUIRE((flagged_list_dev == nullptr) == (flagged_count_dev == nullptr), "pk_rescore_f64: flagged list without its counter");
+    PK_REQUIRE(n_users >= 1 && K >= 1 && K <= 256 && ldv >= K && lde >= K, "pk_rescore_f64: bad sizes");
+    PK_REQUIRE(n_rows >= 0 && n_rows <= n_users, "pk_rescore_f64: bad row count");
+    PK_REQUIRE(V32_dev == nullptr || ldv32 >= K, "pk_rescore_f64: ldv32 < K");
     PK_REQUIRE(KC >= 1 && splits >= 1 && KC * splits <= 64 && topk >= 1 && topk <= KC,
-               "pk_rescore_topk_f64: need topk <= KC and KC*splits <= 64");
+               "pk_rescore_f64: need topk <= KC and KC*splits <= 64");
     if (n_rows == 0) return PK_OK;
-    const int seg = (KC * splits <= 16) ? 16 : (KC * splits <= 32) ? 32 : 64;
-    const int lpc_req = 0;        // lanes per candidate: by the segment width (below)
-    const bool score4 = true;     // two-step scoring (four lanes per candidate first)
-#define PK_RESCORE(SEGV, LPCV) PK_RESCORE_X(SEGV, LPCV, false)
-#define PK_RESCORE_X(SEGV, LPCV, S4)                                                                                    \
+    // lanes per candidate by the segment width; segments that fill a wave score with four lanes per candidate first (SCORE4)
+#define PK_RESCORE(SEGV, LPCV, S4)                                                                                      \
     hipLaunchKernelGGL((rescore_topk_kernel<SEGV, LPCV, S4>), dim3((unsigned)pk_ceil_div(n_rows, 4 * (64 / (SEGV * LPCV)))), \
                        dim3(256), 0, pk_stream(stream), n_rows, rows_dev, n_rows_dev, n_users, n_items, K, V_dev, ldv, V32_dev, ldv32, E_dev, lde, \
                        e_err_dev, e_err_ld, e_exact, seen_ptr_dev, KC, splits, cand_score_dev, cand_idx_dev, topk, v_row_norm_max,   \
                        out_idx_dev, out_score_dev, flags_dev, flagged_list_dev, flagged_count_dev, flagged_offset, item_norm_dev, \
                        out_perm_dev, user_norm_dev)
-    if (seg == 16) {
-        if (lpc_req == 1) PK_RESCORE(16, 1);
-        else if (lpc_req == 4) PK_RESCORE(16, 4);
-        else PK_RESCORE(16, 2);    // two users per wave: scoring them one after the other with four lanes per candidate
-                                   // was measured 3-8 % SLOWER (0.076 -> 0.083 ms ML-20M-shaped, 0.65 -> 0.67 ms S-1M)
-    } else if (seg == 32) {
-        if (lpc_req == 1) PK_RESCORE(32, 1);
-        else if (score4) PK_RESCORE_X(32, 2, true);
-        else PK_RESCORE(32, 2);
-    } else {
-        if (score4) PK_RESCORE_X(64, 1, true);
-        else PK_RESCORE(64, 1);
-    }
+    if (KC * splits <= 16)
+        PK_RESCORE(16, 2, false);   // two users per wave: scoring them one after the other with four lanes per candidate
+                                    // was measured 3-8 % SLOWER (0.076 -> 0.083 ms ML-20M-shaped, 0.65 -> 0.67 ms S-1M)
+    else if (KC * splits <= 32) PK_RESCORE(32, 2, true);
+    else PK_RESCORE(64, 1, true);
 #undef PK_RESCORE
-#undef PK_RESCORE_X
     PK_CHECK_LAUNCH("rescore_topk_kernel");
     return PK_OK;
-}
-
-extern "C" int pk_rescore_topk_rows_perm_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
-                                            const int32_t *n_rows_dev, int64_t n_users,
-                                            int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
-                                            const float *V32_dev, int64_t ldv32,
-                                            const double *E_dev, int64_t lde, const double *e_err_dev,
-                                            int64_t e_err_ld, int32_t e_exact,
-                                            const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                                            const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                                            double v_row_norm_max, int64_t *out_idx_dev, double *out_score_dev,
-                                            int32_t *flags_dev, int32_t *flagged_list_dev, int32_t *flagged_count_dev,
-                                            int32_t flagged_offset, const float *item_norm_dev, const int64_t *out_perm_dev) {
-    return pk_rescore_topk_rows_settle_f64(stream, n_rows, rows_dev, n_rows_dev, n_users, n_items, K, V_dev, ldv, V32_dev, ldv32, E_dev,
-                                           lde, e_err_dev, e_err_ld, e_exact, seen_ptr_dev, KC, splits, cand_score_dev, cand_idx_dev, topk,
-                                           v_row_norm_max, out_idx_dev, out_score_dev, flags_dev, flagged_list_dev, flagged_count_dev,
-                                           flagged_offset, item_norm_dev, out_perm_dev, pk_take_user_norm(stream, n_users, flags_dev));
-}
-
-extern "C" int pk_rescore_topk_rows_norms_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
-                                             const int32_t *n_rows_dev, int64_t n_users,
-                                             int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
-                                             const float *V32_dev, int64_t ldv32,
-                                             const double *E_dev, int64_t lde, const double *e_err_dev,
-                                             int64_t e_err_ld, int32_t e_exact,
-                                             const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                                             double v_row_norm_max, int64_t *out_idx_dev, double *out_score_dev,
-                                             int32_t *flags_dev, int32_t *flagged_list_dev, int32_t *flagged_count_dev,
-                                             int32_t flagged_offset, const float *item_norm_dev) {
-    return pk_rescore_topk_rows_perm_f64(stream, n_rows, rows_dev, n_rows_dev, n_users, n_items, K, V_dev, ldv, V32_dev, ldv32, E_dev,
-                                         lde, e_err_dev, e_err_ld, e_exact, seen_ptr_dev, KC, splits, cand_score_dev, cand_idx_dev, topk,
-                                         v_row_norm_max, out_idx_dev, out_score_dev, flags_dev, flagged_list_dev, flagged_count_dev,
-                                         flagged_offset, item_norm_dev, nullptr);
-}
-
-extern "C" int pk_rescore_topk_rows_list_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
-                                             const int32_t *n_rows_dev, int64_t n_users,
-                                             int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
-                                             const float *V32_dev, int64_t ldv32,
-                                             const double *E_dev, int64_t lde, const double *e_err_dev,
-                                             int64_t e_err_ld, int32_t e_exact,
-                                             const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                                             const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                                             double v_row_norm_max, int64_t *out_idx_dev, double *out_score_dev,
-                                             int32_t *flags_dev, int32_t *flagged_list_dev, int32_t *flagged_count_dev,
-                                             int32_t flagged_offset) {
-    return pk_rescore_topk_rows_norms_f64(stream, n_rows, rows_dev, n_rows_dev, n_users, n_items, K, V_dev, ldv, V32_dev, ldv32, E_dev,
-                                          lde, e_err_dev, e_err_ld, e_exact, seen_ptr_dev, KC, splits, cand_score_dev, cand_idx_dev, topk,
-                                          v_row_norm_max, out_idx_dev, out_score_dev, flags_dev, flagged_list_dev, flagged_count_dev,
-                                          flagged_offset, nullptr);
-}
-
-extern "C" int pk_rescore_topk_rows_f64(void *stream, int64_t n_rows, const int32_t *rows_dev,
-                                        const int32_t *n_rows_dev, int64_t n_users,
-                                        int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
-                                        const float *V32_dev, int64_t ldv32,
-                                        const double *E_dev, int64_t lde, const double *e_err_dev,
-                                        int64_t e_err_ld, int32_t e_exact,
-                                        const int64_t *seen_ptr_dev, int32_t KC, int32_t splits,
-                                        const float *cand_score_dev, const int32_t *cand_idx_dev, int32_t topk,
-                                        double v_row_norm_max, int64_t *out_idx_dev, double *out_score_dev,
-                                        int32_t *flags_dev) {
-    return pk_rescore_topk_rows_list_f64(stream, n_rows, rows_dev, n_rows_dev, n_users, n_items, K, V_dev, ldv, V32_dev, ldv32, E_dev,
-                                         lde, e_err_dev, e_err_ld, e_exact, seen_ptr_dev, KC, splits, cand_score_dev, cand_idx_dev, topk,
-                                         v_row_norm_max, out_idx_dev, out_score_dev, flags_dev, nullptr, nullptr, 0);
-}
-
-extern "C" int pk_rescore_topk_f64(void *stream, int64_t n_users, int64_t n_items, int32_t K, const double *V_dev,
-                                   int64_t ldv, const double *E_dev, int64_t lde, const int64_t *seen_ptr_dev,
-                                   int32_t KC, int32_t splits, const float *cand_score_dev,
-                                   const int32_t *cand_idx_dev,
-                                   int32_t topk, double v_row_norm_max, int64_t *out_idx_dev,
-                                   double *out_score_dev, int32_t *flags_dev) {
-    return pk_rescore_topk_rows_f64(stream, n_users, nullptr, nullptr, n_users, n_items, K, V_dev, ldv, nullptr, 0, E_dev, lde,
-                                    nullptr, 0, 0, seen_ptr_dev, KC, splits, cand_score_dev, cand_idx_dev, topk, v_row_norm_max,
-                                    out_idx_dev, out_score_dev, flags_dev);
 }
 
 // ---- re-doing flagged users without the host -------------------------------------------------------
@@ -1120,26 +997,18 @@ extern "C" int pk_score_exact_rows_f64(void *stream, int32_t n_rows, const int32
  * n_items), its tickets zeroed once by pk_exact_work_init(n_wg, n_items)): the first n_wg listed users go through the chunk
  * workgroups, any further ones share n_wg one-workgroup slices — one launch (exact_list_kernel).  Nothing about the list
  * visits the host, so a scoring pass needs no synchronisation.
- * _perm form: out_perm_dev (int64 [n_users], may be NULL) sends the out_idx row of user u to row out_perm[u]; out_score rows
- * stay where they are. */
-extern "C" int pk_score_exact_list_perm_f64(void *stream, int32_t n_wg, const int32_t *list_dev, const int32_t *count_dev,
-                                            int64_t n_items, int32_t K, const double *V_dev, int64_t ldv, const double *E_dev,
-                                            int64_t lde, const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev, int32_t topk,
-                                            int64_t *out_idx_dev, double *out_score_dev, void *work_dev,
-                                            const int64_t *out_perm_dev) {
+ * out_perm_dev (int64 [n_users], may be NULL: rows stay where they are) sends the out_idx row of user u to row out_perm[u];
+ * out_score rows stay where they are. */
+extern "C" int pk_score_exact_list_f64(void *stream, int32_t n_wg, const int32_t *list_dev, const int32_t *count_dev,
+                                       int64_t n_items, int32_t K, const double *V_dev, int64_t ldv, const double *E_dev,
+                                       int64_t lde, const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev, int32_t topk,
+                                       int64_t *out_idx_dev, double *out_score_dev, void *work_dev,
+                                       const int64_t *out_perm_dev) {
     PK_REQUIRE(n_wg >= 1 && n_items >= 1 && K >= 1 && K <= 8192 && topk >= 1 && list_dev && count_dev,
                "pk_score_exact_list_f64: bad sizes");
     PK_REQUIRE(ldv >= K && lde >= K && work_dev && out_idx_dev, "pk_score_exact_list_f64: bad arguments");
     return exact_launch(pk_stream(stream), 0, count_dev, n_wg, list_dev, 1, n_items, K, V_dev, ldv, E_dev, lde, seen_ptr_dev,
                         seen_idx_dev, topk, out_idx_dev, out_score_dev, static_cast<unsigned char *>(work_dev), n_wg, out_perm_dev);
-}
-
-extern "C" int pk_score_exact_list_f64(void *stream, int32_t n_wg, const int32_t *list_dev, const int32_t *count_dev,
-                                       int64_t n_items, int32_t K, const double *V_dev, int64_t ldv, const double *E_dev,
-                                       int64_t lde, const int64_t *seen_ptr_dev, const int32_t *seen_idx_dev, int32_t topk,
-                                       int64_t *out_idx_dev, double *out_score_dev, void *work_dev) {
-    return pk_score_exact_list_perm_f64(stream, n_wg, list_dev, count_dev, n_items, K, V_dev, ldv, E_dev, lde, seen_ptr_dev,
-                                        seen_idx_dev, topk, out_idx_dev, out_score_dev, work_dev, nullptr);
 }
 
 // zeroes the tickets of a work buffer of pk_exact_work_bytes(n_rows, n_items) bytes: once, where the buffer is allocated —

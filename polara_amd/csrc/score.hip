@@ -1726,7 +1726,7 @@ extern "C" int pk_score_candidates_f32(void *stream, int64_t n_users, int64_t n_
 extern "C" int pk_sweep_takes_rows(void) { return 1; }
 
 // user_bound_out_dev (float [n_users], may be NULL): the users' side of the pruning bound as the sweep computed it, for
-// pk_rescore_topk_rows_settle_f64
+// pk_rescore_f64
 extern "C" int pk_score_candidates_rows_bound_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
                                                   const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
                                                   double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
@@ -1762,7 +1762,7 @@ extern "C" int pk_sweep_settles(int32_t KC) {
 
 // The single pruned sweep from the rows of E (pk_score_candidates_rows_bound_f32 with splits = 1) that applies the settle rule
 // of the first re-scoring to a group's final lists when the group leaves the sweep: see PkSweepSettle (polara_hip.h) and
-// SettleExit above.  The first re-scoring then runs on open_list / open_count (pk_rescore_topk_rows_*: a row list, tier off).
+// SettleExit above.  The first re-scoring then runs on open_list / open_count (pk_rescore_f64 with a row list: tier off).
 extern "C" int pk_score_candidates_rows_settle_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
                                                    const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
                                                    double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
@@ -1913,7 +1913,7 @@ extern "C" int pk_score_two_phase_plan(int64_t n_users, int64_t n_items, int32_t
 // dealt round-robin to `splits` sweeps per group that start from the head's thresholds, then the merge.  Needs the
 // pruning bounds (without them nobody leaves early and a single sweep is the shortest chain there is).
 //   work_score / work_idx  [(splits + 1) * n_pad * KC]   the raw lists (slot 0: head), n_pad = n_users rounded up to 32
-//   cand_score / cand_idx  [n_pad * KC]                   the merged list: what pk_rescore_topk_* takes with splits = 1
+//   cand_score / cand_idx  [n_pad * KC]                   the merged list: what pk_rescore_f64 takes with splits = 1
 //   state                  pk_score_state_bytes(n_users, splits + 1)
 static int pk_score_two_phase_impl(const char *who, void *stream, int64_t n_users, int64_t n_items, int32_t K,
                                    const float *Vp_dev, const float *Ep_dev, const UserRows *rows_in, const int64_t *seen_ptr_dev,

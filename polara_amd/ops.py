@@ -1434,7 +1434,7 @@ class HipOps:
         u goes to row out_perm[u] of out_idx (scores and flags stay at row u).  user_norm (float32 [n_users]): upper bounds
         of the norms of the rows of E — the users' side of the sweep's pruning bound; on a first pass over an approximate E
         (v32 and e_err given, no rows, not e_exact) the users whose order the sweep's own scores decide are then settled
-        without re-scoring (pk_rescore_topk_rows_settle_f64: flags = 8, no score row; `settled_users` counts them).
+        without re-scoring (pk_rescore_f64: flags = 8, no score row; `settled_users` counts them).
         first_pass (timers only): a call with a row list is booked as the pass's first re-scoring (the open list of a sweep
         that settled at its exit) instead of the re-scoring of the re-folded users."""
         assert V.stride(1) == 1 and E.stride(1) == 1
@@ -1454,25 +1454,15 @@ class HipOps:
         with self._timed('rescore_topk' if first_pass else 'rescore_topk_refolded', (n_rows, KC, K)):
             fl, fc, fo = flagged if flagged is not None else (None, None, 0)
             assert item_norm is None or (item_norm.dtype == torch.float32 and item_norm.is_contiguous() and item_norm.numel() == n_items)
-            args = (self.stream(), n_rows, _ptr(rows), _ptr(n_rows_dev), n_users, n_items, K, _ptr(V),
-                    V.stride(0), _ptr(v32), 0 if v32 is None else v32.stride(0), _ptr(E), E.stride(0), _ptr(e_err), e_ld,
-                    1 if e_exact else 0, _ptr(seen_ptr), KC, splits, _ptr(cs), _ptr(ci), topk, float(vmax),
-                    _ptr(out_idx), _ptr(out_s), _ptr(flags), _ptr(fl), _ptr(fc), int(fo), _ptr(item_norm))
             assert out_perm is None or (out_perm.dtype == torch.int64 and out_perm.is_contiguous() and out_perm.numel() == n_users)
             if user_norm is not None:
                 assert user_norm.dtype == torch.float32 and user_norm.is_contiguous() and user_norm.numel() == n_users
-            if user_norm is not None and out_perm is None:
-                _lib.check(self.lib.pk_rescore_topk_rows_settle_f64(*args, None, _ptr(user_norm)),
-                           'pk_rescore_topk_rows_settle_f64')
-            elif out_perm is None:
-                _lib.check(self.lib.pk_rescore_topk_rows_norms_f64(*args), 'pk_rescore_topk_rows_norms_f64')
-            else:
-                # the producer-order pass keeps its recorded sequence of entries (two `_perm` re-scorings): the norm bounds
-                # travel with the stream to the call behind them (pk_rescore_bind_user_norm)
-                if user_norm is not None:
-                    _lib.check(self.lib.pk_rescore_bind_user_norm(self.stream(), _ptr(user_norm), n_users, _ptr(flags)),
-                               'pk_rescore_bind_user_norm')
-                _lib.check(self.lib.pk_rescore_topk_rows_perm_f64(*args, _ptr(out_perm)), 'pk_rescore_topk_rows_perm_f64')
+            _lib.check(self.lib.pk_rescore_f64(
+                self.stream(), n_rows, _ptr(rows), _ptr(n_rows_dev), n_users, n_items, K, _ptr(V),
+                V.stride(0), _ptr(v32), 0 if v32 is None else v32.stride(0), _ptr(E), E.stride(0), _ptr(e_err), e_ld,
+                1 if e_exact else 0, _ptr(seen_ptr), KC, splits, _ptr(cs), _ptr(ci), topk, float(vmax),
+                _ptr(out_idx), _ptr(out_s), _ptr(flags), _ptr(fl), _ptr(fc), int(fo), _ptr(item_norm), _ptr(out_perm),
+                _ptr(user_norm)), 'pk_rescore_f64')
         return out_idx, out_s, flags
 
     @staticmethod
@@ -1533,13 +1523,11 @@ class HipOps:
             _lib.check(self.lib.pk_exact_work_init(self.stream(), _ptr(work), int(n_wg), n_items), 'pk_exact_work_init')
             self._exact_work[key] = work
         with self._timed('score_exact_list', (n_items, K, topk)):
-            args = (self.stream(), int(n_wg), _ptr(lst), _ptr(cnt), n_items, K, _ptr(V), V.stride(0), _ptr(E), E.stride(0),
-                    _ptr(seen_ptr), _ptr(seen_idx), topk, _ptr(out_idx), _ptr(out_s), _ptr(work))
-            if out_perm is None:
-                _lib.check(self.lib.pk_score_exact_list_f64(*args), 'pk_score_exact_list_f64')
-            else:
-                assert out_perm.dtype == torch.int64 and out_perm.is_contiguous()
-                _lib.check(self.lib.pk_score_exact_list_perm_f64(*args, _ptr(out_perm)), 'pk_score_exact_list_perm_f64')
+            assert out_perm is None or (out_perm.dtype == torch.int64 and out_perm.is_contiguous())
+            _lib.check(self.lib.pk_score_exact_list_f64(
+                self.stream(), int(n_wg), _ptr(lst), _ptr(cnt), n_items, K, _ptr(V), V.stride(0), _ptr(E), E.stride(0),
+                _ptr(seen_ptr), _ptr(seen_idx), topk, _ptr(out_idx), _ptr(out_s), _ptr(work), _ptr(out_perm)),
+                'pk_score_exact_list_f64')
         return work
 
     def scatter_rows(self, src, perm, out=None):

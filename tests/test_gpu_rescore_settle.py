@@ -1,4 +1,4 @@
-"""The settle tier of the first re-scoring (pk_rescore_topk_rows_settle_f64): users whose order the candidate sweep's own
+"""The settle tier of the first re-scoring (pk_rescore_f64 with user_norm_dev): users whose order the candidate sweep's own
 scores already decide get their lists without a gather — the lists stay the exact ones, every other user and every other
 route is what it was.  The rule is restated in numpy (rescore_settle_reference.py); shapes: 333 users (partial waves, a
 partial last segment), 700 items (22 tiles, the last one partial), the three segment instances (KC = 16, 32, 64)."""
@@ -33,12 +33,14 @@ def device_case(ops, V, indptr, indices, values):
     return T, scoring.FactorImage(ops, ops.to_device(V))
 
 
-def first_pass(ops, F, T, topk, settle=True, item_norm=True, negate=None, second=False, perm=False, splits=1):
+def first_pass(ops, F, T, topk, settle=True, item_norm=True, negate=None, second=False, perm=None, splits=1, then_without_norm=False):
     """fold-in, candidate sweep and FIRST re-scoring as `scoring.recommend` issues them for one batch: a single sweep with ONE
     list per user (what a pass over many users runs: the segment of the re-scoring kernel is then KC wide — 16 and 32: two
     users and one user per wave with two lanes per candidate, 64: one user per wave) or with `splits` lists per user (a
-    small batch: KC * splits candidates, here always the 64-wide segment).  Returns host arrays: ids, flags, and what the
-    restatement needs."""
+    small batch: KC * splits candidates, here always the 64-wide segment).  perm (int64 array): passed as `out_perm`, the list
+    of user u goes to row perm[u].  then_without_norm: the same call is issued again at once — same stream, same ids, scores
+    and flags buffers — without `user_norm`, and the results are those of that second call.  Returns host arrays: ids,
+    flags, and what the restatement needs."""
     from polara_amd import scoring
     n, n_items = T.shape
     K, KC = F.K, ops.candidate_capacity(topk)
@@ -62,9 +64,13 @@ def first_pass(ops, F, T, topk, settle=True, item_norm=True, negate=None, second
         kw.update(rows=torch.arange(n, dtype=torch.int32, device=Ex.device), e_exact=True)
     else:
         kw.update(v32=F.V32x)
-    if perm:        # the producer-order entry (here with the identity): the bounds reach it through the stream
-        kw.update(out_perm=torch.arange(n, dtype=torch.int64, device=Ex.device))
-    ids, _, flags = ops.rescore_topk(F.V, E, n_items, T.indptr, KC, cs, ci, topk, F.vmax, **kw)
+    if perm is not None:
+        kw.update(out_perm=torch.as_tensor(np.asarray(perm, dtype=np.int64), device=Ex.device))
+    ids, sc, flags = ops.rescore_topk(F.V, E, n_items, T.indptr, KC, cs, ci, topk, F.vmax, **kw)
+    if then_without_norm:
+        lst, cnt = torch.empty_like(lst), ops.zero_counters(1)
+        kw.update(user_norm=None, flagged=(lst, cnt, 0), out=(ids, sc, flags))
+        ops.rescore_topk(F.V, E, n_items, T.indptr, KC, cs, ci, topk, F.vmax, **kw)
     h = ops.to_host
     return dict(ids=h(ids), flags=h(flags), listed=np.sort(h(lst)[:int(cnt.item())]), cs=h(cs), ci=h(ci), un=h(un), w=h(w).copy(),
                 vnorm=h(F.vnorm), vmax=float(F.vmax), KC=KC, splits=splits, seg=seg, E=h(E).copy())
@@ -111,17 +117,23 @@ def test_decaying_norm_catalogue_settles_what_the_rule_says(hip_ops, pk_options,
     clear = np.abs(margin) > 1e-6
     assert np.array_equal(st[clear], want[clear]) and (~clear).sum() <= 3
     assert st.sum() >= N_USERS / 2 and (~st).sum() >= 10           # both branches are exercised
-    # the same through the older `_perm` entry with the bounds bound to the stream; a binding serves ONE call
-    bound = first_pass(ops, F, T, topk, perm=True, splits=splits)
-    assert np.array_equal(bound['ids'], on['ids']) and np.array_equal(bound['flags'], on['flags'])
-    assert not (first_pass(ops, F, T, topk, settle=False, perm=True, splits=splits)['flags'] & 8).any()
-    # ... and only the call it names: a binding made for another flags buffer is dropped by the next `_perm` call, not used
-    from polara_amd import _lib
-    other = torch.empty(N_USERS, dtype=torch.int32, device=ops.device)
-    stale = torch.ones(N_USERS, dtype=torch.float32, device=ops.device)
-    _lib.check(ops.lib.pk_rescore_bind_user_norm(ops.stream(), stale.data_ptr(), N_USERS, other.data_ptr()), 'pk_rescore_bind_user_norm')
-    assert not (first_pass(ops, F, T, topk, settle=False, perm=True, splits=splits)['flags'] & 8).any()
-    assert not (first_pass(ops, F, T, topk, settle=False, perm=True, splits=splits)['flags'] & 8).any()
+    # `out_perm` and `user_norm` are arguments of the one call: with the identity and with a shuffle of the 333 users the
+    # flags are those of the call without `out_perm`, the list of user u sits in row perm[u], every settled user is flagged 8
+    shuffle = np.random.RandomState(KC + splits).permutation(N_USERS)
+    assert (shuffle != np.arange(N_USERS)).any()
+    for perm in (np.arange(N_USERS), shuffle):
+        moved = first_pass(ops, F, T, topk, perm=perm, splits=splits)
+        assert np.array_equal(moved['flags'], on['flags']) and np.array_equal(moved['ids'][perm], on['ids'])
+        assert np.array_equal(moved['flags'][st], np.full(int(st.sum()), 8))
+    # ... and with `out_perm` but no `user_norm` nobody settles
+    plain = first_pass(ops, F, T, topk, settle=False, perm=shuffle, splits=splits)
+    assert not (plain['flags'] & 8).any()
+    # nothing stays behind a call: the same call again on the same stream, into the same flags buffer, without `user_norm`
+    # settles nobody — it is the call without the bounds, flag for flag and id for id
+    for perm in (None, shuffle):
+        again = first_pass(ops, F, T, topk, perm=perm, splits=splits, then_without_norm=True)
+        assert not (again['flags'] & 8).any()
+        assert np.array_equal(again['flags'], plain['flags']) and np.array_equal(again['ids'] if perm is None else again['ids'][perm], plain['ids'][shuffle])
     # the whole pass with the same number of lists: exact lists, byte-identical with the tier off, and the count it reports
     ops.score_splits_override = splits
     try:
