@@ -296,51 +296,35 @@ int pk_seen_tiles_build(void *stream, int64_t n_users, const int64_t *seen_ptr_d
                         int64_t max_row_len /* only read when rows_sorted == 0: <= pk_seen_tiles_max_unsorted_row() */,
                         uint64_t *tiles_dev, int32_t *ntiles_dev);
 int32_t pk_seen_tiles_max_unsorted_row(void);
-int pk_score_candidates_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K,
-                            const float *Vp_dev, const float *Ep_dev,
-                            const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                            const int32_t *seen_ntiles_dev /* all three NULL: nothing is masked */,
-                            int32_t KC, int32_t splits /* splits*KC <= 64 */,
-                            float *cand_score_dev, int32_t *cand_idx_dev /* [splits][n_users_pad][KC] */,
-                            void *state_dev /* pk_score_state_bytes(n_users, splits) */,
-                            int32_t tiles_per_chunk /* 0 = auto */,
-                            const float *user_bound_dev /* [n_users] or NULL */,
-                            const float *tile_bound_dev /* [ceil(n_items/32)] or NULL */,
-                            const uint32_t *seen_dense_dev, const int32_t *seen_skip_dev,
-                            int32_t dense_tiles /* pk_seen_dense_build output, or NULL, NULL, 0: the stream serves every tile */);
-/* The same sweep with the users' side read from the fp64 ROWS of E = test_matrix.dot(v) (models.py:860) as the fold-in
- * leaves them: every wave builds its 32 users' MFMA fragments and pruning bounds in its prologue — the arithmetic of
- * pk_pack_frag_bound_f32, bit for bit: bound_u = ||E[u, :K]|| (1 + 1e-6) + extra_scale * extra[u * extra_ld] — so a pass
- * needs neither the packing launch nor a packed copy of E.  E_dev 16-byte aligned, lde even and >= K; extra_dev: the
- * error weight column of an approximate fold-in, or NULL; tile_bound_dev == NULL: full sweep (no pruning). */
-/* 1 when the sweeps of this library take the users' side from the rows of E (the two *_rows_f32 entries below); a probe build of
- * csrc/experiments/ returns 0 and its callers pack fragments first */
-int pk_sweep_takes_rows(void);
-int pk_score_candidates_rows_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
-                                 const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
-                                 double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                                 const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits, float *cand_score_dev,
-                                 int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk /* 0 = auto */,
-                                 const float *tile_bound_dev /* or NULL */, const uint32_t *seen_dense_dev,
-                                 const int32_t *seen_skip_dev, int32_t dense_tiles);
-/* ... and the users' side of the pruning bound left in user_bound_out_dev (float [n_users], or NULL): bound_u above, an
- * upper bound of ||E_u|| — four bytes per user, stored by the sweep's prologue, for pk_rescore_f64. */
-int pk_score_candidates_rows_bound_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
-                                       const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
-                                       double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                                       const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits, float *cand_score_dev,
-                                       int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk /* 0 = auto */,
-                                       const float *tile_bound_dev /* or NULL */, const uint32_t *seen_dense_dev,
-                                       const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev);
-/* ... and the settle rule of the first re-scoring (pk_rescore_f64) applied where a group of 32 users LEAVES the
- * sweep, to the final sorted lists the wave still holds: single sweep (one list per user), KC = 16 or 32, pruning bound and
- * error weights (extra_dev) required.  A user whose order the sweep's own scores decide is SETTLED: its topk ids go to row u
- * of out_idx (row out_perm[u] when given), flags[u] = 8, and its row of cand_score / cand_idx is NOT written (stale).  Every
- * other user keeps its candidate row and is appended to open_list (int32 [n_users], arbitrary order) behind the device
- * counter open_count, which the caller zeroes in front of the sweep (pk_zero_i32, or pk_fold_q20_zero).  The first re-scoring
- * then takes open_list / open_count as its row list; the settled set, the flags and the lists are those of the tier in the
- * re-scoring kernel.  pk_sweep_settles(KC): 1 when a host layer should take this route — KC fits and the options
- * "sweep_settle" and "rescore_settle" (pk_set_option, default 1) are on; the entry itself settles whenever it is called. */
+/* The candidate sweep as ONE launch sequence: pk_score_candidates_f32 covers the single sweep with or without item splits,
+ * with or without the settle rule at a group's exit.  Every choice is an argument, NULL or 0 = not used, and every rule below
+ * is checked before anything is launched.
+ *
+ * The users' side is given in exactly one of two forms:
+ *   packed    Ep_dev: the MFMA fragments of E (pk_pack_frag_f32 / pk_pack_frag_bound_f32), with user_bound_dev [n_users] or
+ *             NULL — user_bound_dev and tile_bound_dev go together (both: pruned sweep; neither: full sweep).  E_dev, extra_dev,
+ *             user_bound_out_dev and settle must be NULL: nothing would read or write them.
+ *   rows      E_dev: the fp64 ROWS of E = test_matrix.dot(v) (models.py:860) as the fold-in leaves them: every wave builds
+ *             its 32 users' MFMA fragments and pruning bounds in its prologue — the arithmetic of pk_pack_frag_bound_f32, bit
+ *             for bit: bound_u = ||E[u, :K]|| (1 + 1e-6) + extra_scale * extra[u * extra_ld] — so a pass needs neither the
+ *             packing launch nor a packed copy of E.  E_dev 16-byte aligned, lde even and >= K; extra_dev: the error weight
+ *             column of an approximate fold-in (extra_ld >= 1), or NULL; tile_bound_dev == NULL: full sweep (no pruning).
+ *             Ep_dev and user_bound_dev must be NULL.
+ *             user_bound_out_dev (float [n_users], or NULL): the users' side of the pruning bound is left there: bound_u
+ *             above, an upper bound of ||E_u|| — four bytes per user, stored by the sweep's prologue, for pk_rescore_f64.
+ * pk_sweep_takes_rows(): 1 when the sweeps of this library take the rows form; a probe build of csrc/experiments/ returns 0,
+ * refuses E_dev, and its callers pack fragments first.
+ *
+ * settle (or NULL; rows form only): the settle rule of the first re-scoring (pk_rescore_f64) applied where a group of 32
+ * users LEAVES the sweep, to the final sorted lists the wave still holds: single sweep (splits = 1, one list per user), KC = 16
+ * or 32, 1 <= topk <= KC, vmax >= 0, n_users within int32, pruning bound (tile_bound_dev) and error weights (extra_dev)
+ * required.  A user whose order the sweep's own scores decide is SETTLED: its topk ids go to row u of out_idx (row out_perm[u]
+ * when given), flags[u] = 8, and its row of cand_score / cand_idx is NOT written (stale).  Every other user keeps its candidate
+ * row and is appended to open_list (int32 [n_users], arbitrary order) behind the device counter open_count, which the caller
+ * zeroes in front of the sweep (pk_zero_i32, or pk_fold_q20_zero).  The first re-scoring then takes open_list / open_count as
+ * its row list; the settled set, the flags and the lists are those of the tier in the re-scoring kernel.
+ * pk_sweep_settles(KC): 1 when a host layer should take this route — KC fits and the options "sweep_settle" and
+ * "rescore_settle" (pk_set_option, default 1) are on; the entry itself settles whenever it is given the block. */
 typedef struct PkSweepSettle {
     int32_t topk;
     double vmax;                 /* v_row_norm_max of the re-scoring entries */
@@ -351,15 +335,22 @@ typedef struct PkSweepSettle {
     int32_t *open_list;          /* [n_users] */
     int32_t *open_count;         /* [1], zero at the start of the sweep */
 } PkSweepSettle;
+int pk_sweep_takes_rows(void);
 int pk_sweep_settles(int32_t KC);
-int pk_score_candidates_rows_settle_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
-                                        const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
-                                        double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                                        const int32_t *seen_ntiles_dev, int32_t KC, float *cand_score_dev,
-                                        int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk /* 0 = auto */,
-                                        const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                        const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev /* or NULL */,
-                                        const PkSweepSettle *settle);
+int pk_score_candidates_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                            const float *Ep_dev, const float *user_bound_dev /* packed */,
+                            const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld, double extra_scale,
+                            float *user_bound_out_dev /* rows */,
+                            const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
+                            const int32_t *seen_ntiles_dev /* all three NULL: nothing is masked */,
+                            int32_t KC, int32_t splits /* splits*KC <= 64 */,
+                            float *cand_score_dev, int32_t *cand_idx_dev /* [splits][n_users_pad][KC] */,
+                            void *state_dev /* pk_score_state_bytes(n_users, splits) */,
+                            int32_t tiles_per_chunk /* 0 = auto */,
+                            const float *tile_bound_dev /* [ceil(n_items/32)] or NULL */,
+                            const uint32_t *seen_dense_dev, const int32_t *seen_skip_dev,
+                            int32_t dense_tiles /* pk_seen_dense_build output, or NULL, NULL, 0: the stream serves every tile */,
+                            const PkSweepSettle *settle /* or NULL */);
 /* The pruned sweep in TWO PHASES (replaces the same reference lines: the chunk loop body of models.py:359-371, with
  * downvote_seen_items :494-519 and topsort :488-491 fused in).  A launch of the single sweep lasts as long as its slowest
  * wave — the groups of the heaviest users stay ~270 tiles in the sweep, everybody else 70-130 — so the catalogue is
@@ -372,35 +363,23 @@ int pk_score_candidates_rows_settle_f32(void *stream, int64_t n_users, int64_t n
  *   state    pk_score_state_bytes(n_users, splits + 1): records of slot 0 = the head, slots 1.. = the splits (first int64
  *            of a record: the tile at which the group left that sweep; a head exit below head_tiles means the group was
  *            pruned inside the head and its splits did not run).
+ * The users' side: packed or rows, with the rules of pk_score_candidates_f32 (user_bound_out_dev as there); the pruning
+ * bounds are required — user_bound_dev and tile_bound_dev with Ep_dev, tile_bound_dev with E_dev — and 1 <= head_tiles <
+ * ceil(n_items / 32).  There is no settle block: the rule needs the one final list of a single sweep.
  * pk_score_two_phase_plan: the default (head_tiles, splits) for a user set and a catalogue; head_tiles = 0: use the single
  * sweep (user sets that fill the chip's wave slots on their own: there the sweep is bound by the work of the head tiles,
  * not by its longest chain, and the scheme was measured slower). */
 int pk_score_two_phase_plan(int64_t n_users, int64_t n_items, int32_t KC, int32_t *head_tiles, int32_t *splits);
-int pk_score_two_phase_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K,
-                           const float *Vp_dev, const float *Ep_dev,
+int pk_score_two_phase_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                           const float *Ep_dev, const float *user_bound_dev /* packed */,
+                           const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld, double extra_scale,
+                           float *user_bound_out_dev /* rows */,
                            const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev, const int32_t *seen_ntiles_dev,
                            int32_t KC, int32_t head_tiles, int32_t splits /* (splits + 1) * KC <= 256 */,
                            float *work_score_dev, int32_t *work_idx_dev, float *cand_score_dev, int32_t *cand_idx_dev,
                            void *state_dev, int32_t tiles_per_chunk /* 0 = auto */,
-                           const float *user_bound_dev, const float *tile_bound_dev /* both required */,
+                           const float *tile_bound_dev /* required */,
                            const uint32_t *seen_dense_dev, const int32_t *seen_skip_dev, int32_t dense_tiles);
-/* ... with the users' side from the rows of E (see pk_score_candidates_rows_f32; tile_bound_dev required) */
-int pk_score_two_phase_rows_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
-                                const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
-                                double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                                const int32_t *seen_ntiles_dev, int32_t KC, int32_t head_tiles, int32_t splits,
-                                float *work_score_dev, int32_t *work_idx_dev, float *cand_score_dev, int32_t *cand_idx_dev,
-                                void *state_dev, int32_t tiles_per_chunk, const float *tile_bound_dev,
-                                const uint32_t *seen_dense_dev, const int32_t *seen_skip_dev, int32_t dense_tiles);
-/* ... and user_bound_out_dev as in pk_score_candidates_rows_bound_f32 */
-int pk_score_two_phase_rows_bound_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
-                                      const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
-                                      double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                                      const int32_t *seen_ntiles_dev, int32_t KC, int32_t head_tiles, int32_t splits,
-                                      float *work_score_dev, int32_t *work_idx_dev, float *cand_score_dev, int32_t *cand_idx_dev,
-                                      void *state_dev, int32_t tiles_per_chunk, const float *tile_bound_dev,
-                                      const uint32_t *seen_dense_dev, const int32_t *seen_skip_dev, int32_t dense_tiles,
-                                      float *user_bound_out_dev);
 /* Dense seen masks for the first dense_tiles tiles of the catalogue — where the sweep spends its time, and where a user
  * has a record in nearly every tile: dense_dev[(u / 32 * dense_tiles + tile) * 32 + u % 32] = the user's 32-bit mask in
  * that tile (one coalesced 128-byte load per tile and wave instead of a cursor walk with a scattered 8-byte load per
@@ -468,7 +447,7 @@ int pk_tile_norm_bound_f32(void *stream, int64_t n_items, int32_t K, const doubl
  * of out_score and flags stay where they are.  A pass that sweeps its users in another order than the caller's then needs
  * no pk_scatter_rows_i64 behind it.
  * user_norm_dev (float [n_users], or NULL): the SETTLE TIER.  It holds N_u >= ||E'_u||, the users'
- * side of the sweep's pruning bound (pk_pack_frag_bound_f32's bound_dev, or what pk_score_*_rows_bound_f32 stored).  Active
+ * side of the sweep's pruning bound (pk_pack_frag_bound_f32's bound_dev, or what a sweep left in user_bound_out_dev).  Active
  * only on the first call over an approximate E — V32_dev and e_err_dev given, e_exact = 0, rows_dev = NULL.  The sweep's
  * fp32 score of an item is within d_i = (B N_u + 2^-24 e_err[u]) n_i of its exact score, B = 3 * 2^-16 + (4 K + 10) * 2^-23,
  * n_i = item_norm[i] or v_row_norm_max.  A user whose candidates, sorted by their sweep scores, keep more than d + d'

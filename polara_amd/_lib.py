@@ -17,7 +17,7 @@ _vp, _i32, _i64, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 
 
 class PkSweepSettle(C.Structure):
-    """the settle block of pk_score_candidates_rows_settle_f32 (include/polara_hip.h)"""
+    """the settle block of pk_score_candidates_f32 (include/polara_hip.h)"""
     _fields_ = [('topk', _i32), ('vmax', _f64), ('item_norm', _vp), ('out_idx', _vp), ('out_perm', _vp), ('flags', _vp),
                 ('open_list', _vp), ('open_count', _vp)]
 
@@ -78,22 +78,13 @@ PROTOTYPES = {
     'pk_score_splits': (_i32, [_i64, _i32]),
     'pk_seen_tiles_build': (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i64, _vp, _vp]),
     'pk_seen_tiles_max_unsorted_row': (_i32, []),
-    'pk_score_candidates_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp,
-                                          _i32, _vp, _vp, _vp, _vp, _i32]),
-    'pk_score_candidates_rows_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _i32, _i32,
-                                               _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32]),
-    'pk_score_two_phase_rows_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _i32, _i32, _i32,
-                                              _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32]),
-    'pk_score_candidates_rows_bound_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _i32, _i32,
-                                                     _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    # the users' side of both sweep entries: Ep, user_bound | E, lde, extra, extra_ld, extra_scale, user_bound_out
+    'pk_score_candidates_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _vp,
+                                          _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, C.POINTER(PkSweepSettle)]),
     'pk_sweep_settles': (C.c_int, [_i32]),
-    'pk_score_candidates_rows_settle_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _i32,
-                                                      _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, C.POINTER(PkSweepSettle)]),
-    'pk_score_two_phase_rows_bound_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _i32, _i32,
-                                                    _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
     'pk_score_two_phase_plan': (C.c_int, [_i64, _i64, _i32, _vp, _vp]),
-    'pk_score_two_phase_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
-                                         _i32, _vp, _vp, _vp, _vp, _i32]),
+    'pk_score_two_phase_f32': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _vp, _vp,
+                                         _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32]),
     'pk_seen_dense_bytes': (_i64, [_i64, _i32]),
     'pk_seen_dense_build': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp]),
     'pk_score_chunk_launches': (_i32, [_i64, _i32, _i32, _i32, _i32]),

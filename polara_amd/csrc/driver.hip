@@ -2135,27 +2135,22 @@ int serving_score(pk_ctx *ctx, pk_serving *sv, int32_t topk, int32_t filter_seen
         if (!state.p || !cs.p || !ci.p || (head_tiles && (!ms.p || !mi.p))) return fail(ctx, PK_E_LAUNCH, "out of device memory (candidates)");
         const uint32_t *dense_p = (filter_seen && sv->dense_tiles) ? sv->dense.as<uint32_t>() : nullptr;
         const int32_t *skip_p = (filter_seen && sv->dense_tiles) ? sv->skip.as<int32_t>() : nullptr;
+        // the users' side of the sweep entries: the rows of E with their error weights, or the packed fragments with their bounds
+        const double *rows_p = from_rows ? Ex.p() : nullptr, *rows_w = from_rows ? w : nullptr;
+        const int64_t rows_wld = (from_rows && approx) ? Kx : 0;
         if (head_tiles) {
-            if (from_rows)
-                CK(pk_score_two_phase_rows_f32(st, n_users, n_items, K, sv->Vp.as<float>(), Ex.p(), Kx, w, approx ? Kx : 0, 1.2e-7, seen_ptr,
-                                               tiles, ntiles, KC, head_tiles, splits2, cs.as<float>(), ci.as<int32_t>(), ms.as<float>(),
-                                               mi.as<int32_t>(), state.p, 0, sv->tile_bound.as<float>(), dense_p, skip_p,
-                                               filter_seen ? sv->dense_tiles : 0));
-            else
-                CK(pk_score_two_phase_f32(st, n_users, n_items, K, sv->Vp.as<float>(), Ep.as<float>(), seen_ptr, tiles, ntiles, KC, head_tiles,
-                                          splits2, cs.as<float>(), ci.as<int32_t>(), ms.as<float>(), mi.as<int32_t>(), state.p, 0, ub.as<float>(),
-                                          sv->tile_bound.as<float>(), dense_p, skip_p, filter_seen ? sv->dense_tiles : 0));
+            CK(pk_score_two_phase_f32(st, n_users, n_items, K, sv->Vp.as<float>(), Ep.as<float>(), ub.as<float>(), rows_p, Kx, rows_w,
+                                      rows_wld, 1.2e-7, nullptr, seen_ptr, tiles, ntiles, KC, head_tiles, splits2, cs.as<float>(),
+                                      ci.as<int32_t>(), ms.as<float>(), mi.as<int32_t>(), state.p, 0, sv->tile_bound.as<float>(),
+                                      dense_p, skip_p, filter_seen ? sv->dense_tiles : 0));
             std::swap(cs, ms);      // the merged list is what the re-scoring takes: one list per user
             std::swap(ci, mi);
             splits = 1;
-        } else if (from_rows) {
-            CK(pk_score_candidates_rows_f32(st, n_users, n_items, K, sv->Vp.as<float>(), Ex.p(), Kx, w, approx ? Kx : 0, 1.2e-7, seen_ptr,
-                                            tiles, ntiles, KC, splits, cs.as<float>(), ci.as<int32_t>(), state.p, 0,
-                                            sv->tile_bound.as<float>(), dense_p, skip_p, filter_seen ? sv->dense_tiles : 0));
         } else {
-            CK(pk_score_candidates_f32(st, n_users, n_items, K, sv->Vp.as<float>(), Ep.as<float>(), seen_ptr, tiles, ntiles,
-                                       KC, splits, cs.as<float>(), ci.as<int32_t>(), state.p, 0, ub.as<float>(), sv->tile_bound.as<float>(),
-                                       dense_p, skip_p, filter_seen ? sv->dense_tiles : 0));
+            CK(pk_score_candidates_f32(st, n_users, n_items, K, sv->Vp.as<float>(), Ep.as<float>(), ub.as<float>(), rows_p, Kx, rows_w,
+                                       rows_wld, 1.2e-7, nullptr, seen_ptr, tiles, ntiles, KC, splits, cs.as<float>(),
+                                       ci.as<int32_t>(), state.p, 0, sv->tile_bound.as<float>(), dense_p, skip_p,
+                                       filter_seen ? sv->dense_tiles : 0, nullptr));
         }
         // the lists of users to re-do are appended by the re-scoring kernel itself (scoring.py: fused lists): cnt2[0] counts
         // the re-fold list (lst), cnt2[1] the final list for the exact-row kernel (lst2)

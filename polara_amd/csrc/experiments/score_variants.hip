@@ -2190,14 +2190,23 @@ static int pk_score_check_args(const char *who, int64_t n_users, int64_t n_items
     return PK_OK;
 }
 
-extern "C" int pk_score_candidates_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K,
-                                       const float *Vp_dev, const float *Ep_dev, const int64_t *seen_ptr_dev,
-                                       const uint64_t *seen_tiles_dev, const int32_t *seen_ntiles_dev,
-                                       int32_t KC, int32_t splits,
-                                       float *cand_score_dev, int32_t *cand_idx_dev, void *state_dev,
-                                       int32_t tiles_per_chunk, const float *user_bound_dev,
+// The product's signatures (polara_hip.h); this frozen tree takes packed fragments only: the rows of E, the stored bounds and the
+// settle block are refused (the Python layer keeps the packed route under a probe library: ops.sweep_takes_rows).
+extern "C" int pk_sweep_takes_rows(void) { return 0; }
+extern "C" int pk_sweep_settles(int32_t) { return 0; }
+
+extern "C" int pk_score_candidates_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                                       const float *Ep_dev, const float *user_bound_dev, const double *E_dev, int64_t,
+                                       const double *, int64_t, double, float *user_bound_out_dev,
+                                       const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
+                                       const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits, float *cand_score_dev,
+                                       int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
                                        const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                       const int32_t *seen_skip_dev, int32_t dense_tiles) {
+                                       const int32_t *seen_skip_dev, int32_t dense_tiles, const PkSweepSettle *settle) {
+    if (E_dev || user_bound_out_dev || settle) {
+        pk_set_error("pk_score_candidates_f32: E_dev, user_bound_out_dev and settle are not part of the experiment tree (probe library)");
+        return PK_E_UNSUPPORTED;
+    }
     const int rc = pk_score_check_args("pk_score_candidates_f32", n_users, n_items, K, Vp_dev, Ep_dev, seen_ptr_dev,
                                        seen_tiles_dev, seen_ntiles_dev, state_dev, user_bound_dev, tile_bound_dev,
                                        seen_dense_dev, seen_skip_dev, dense_tiles);
@@ -2338,15 +2347,19 @@ extern "C" int pk_score_two_phase_plan(int64_t n_users, int64_t n_items, int32_t
 //   work_score / work_idx  [(splits + 1) * n_pad * KC]   the raw lists (slot 0: head), n_pad = n_users rounded up to 32
 //   cand_score / cand_idx  [n_pad * KC]                   the merged list: what pk_rescore_f64 takes with splits = 1
 //   state                  pk_score_state_bytes(n_users, splits + 1)
-extern "C" int pk_score_two_phase_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K,
-                                      const float *Vp_dev, const float *Ep_dev, const int64_t *seen_ptr_dev,
-                                      const uint64_t *seen_tiles_dev, const int32_t *seen_ntiles_dev,
-                                      int32_t KC, int32_t head_tiles, int32_t splits,
-                                      float *work_score_dev, int32_t *work_idx_dev,
-                                      float *cand_score_dev, int32_t *cand_idx_dev, void *state_dev,
-                                      int32_t tiles_per_chunk, const float *user_bound_dev,
+extern "C" int pk_score_two_phase_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                                      const float *Ep_dev, const float *user_bound_dev, const double *E_dev, int64_t,
+                                      const double *, int64_t, double, float *user_bound_out_dev,
+                                      const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
+                                      const int32_t *seen_ntiles_dev, int32_t KC, int32_t head_tiles, int32_t splits,
+                                      float *work_score_dev, int32_t *work_idx_dev, float *cand_score_dev,
+                                      int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
                                       const float *tile_bound_dev, const uint32_t *seen_dense_dev,
                                       const int32_t *seen_skip_dev, int32_t dense_tiles) {
+    if (E_dev || user_bound_out_dev) {
+        pk_set_error("pk_score_two_phase_f32: E_dev and user_bound_out_dev are not part of the experiment tree (probe library)");
+        return PK_E_UNSUPPORTED;
+    }
     int rc = pk_score_check_args("pk_score_two_phase_f32", n_users, n_items, K, Vp_dev, Ep_dev, seen_ptr_dev,
                                  seen_tiles_dev, seen_ntiles_dev, state_dev, user_bound_dev, tile_bound_dev,
                                  seen_dense_dev, seen_skip_dev, dense_tiles);
@@ -2383,26 +2396,6 @@ extern "C" int pk_score_two_phase_f32(void *stream, int64_t n_users, int64_t n_i
 #undef PK_MERGE
     PK_CHECK_LAUNCH("merge_candidates_kernel");
     return PK_OK;
-}
-
-// The rows entries of the product (round 5: the sweep builds the users' fragments from the rows of E) do not exist in this
-// frozen tree; the Python layer keeps the packed route under a probe library (ops.sweep_takes_rows), the symbols are here so
-// that the product's driver.hip links.
-extern "C" int pk_sweep_takes_rows(void) { return 0; }      // the experiment tree takes packed fragments only
-
-extern "C" int pk_score_candidates_rows_f32(void *, int64_t, int64_t, int32_t, const float *, const double *, int64_t, const double *,
-                                            int64_t, double, const int64_t *, const uint64_t *, const int32_t *, int32_t, int32_t,
-                                            float *, int32_t *, void *, int32_t, const float *, const uint32_t *, const int32_t *,
-                                            int32_t) {
-    pk_set_error("pk_score_candidates_rows_f32: not part of the experiment tree (probe library)");
-    return PK_E_UNSUPPORTED;
-}
-extern "C" int pk_score_two_phase_rows_f32(void *, int64_t, int64_t, int32_t, const float *, const double *, int64_t, const double *,
-                                           int64_t, double, const int64_t *, const uint64_t *, const int32_t *, int32_t, int32_t,
-                                           int32_t, float *, int32_t *, float *, int32_t *, void *, int32_t, const float *,
-                                           const uint32_t *, const int32_t *, int32_t) {
-    pk_set_error("pk_score_two_phase_rows_f32: not part of the experiment tree (probe library)");
-    return PK_E_UNSUPPORTED;
 }
 
 // eager load of this translation unit's code object (pk_warm_up, api.cpp): the runtime loads a code object at the first

@@ -344,7 +344,7 @@ __global__ __launch_bounds__(256) void rescore_topk_kernel(
 }
 
 // user_norm_dev (float [n_users], may be NULL = tier off): upper bounds of ||E_u|| — the users' side of the sweep's pruning
-// bound (pk_pack_frag_bound_f32's, or what pk_score_*_rows_bound_f32 stored).  On the first pass over an approximate E
+// bound (pk_pack_frag_bound_f32's, or what a sweep from the rows of E left in user_bound_out_dev).  On the first pass over an approximate E
 // (V32_dev, e_err_dev, !e_exact, no row list) the users whose order the sweep's scores already decide are SETTLED: ids
 // written, flags[u] = 8, no out_score row, on no list (see the kernel).  pk_set_option("rescore_settle", 0) switches it off.
 // out_perm_dev (int64 [n_users], may be NULL): the out_idx row of user u is written to row out_perm[u] (out_score and flags

@@ -1528,7 +1528,7 @@ static int launch_candidates_n(hipStream_t st, int KC, dim3 grid, const float4 *
                                                               hipFuncAttributeMaxDynamicSharedMemorySize,           \
                                                               (int)pk_score_settle_lds_bytes(NSTEP, KCV));          \
                     if (e1 != hipSuccess) {                                                                         \
-                        pk_set_error("pk_score_candidates_rows_settle_f32: cannot raise the LDS limit: %s", hipGetErrorString(e1)); \
+                        pk_set_error("pk_score_candidates_f32: cannot raise the LDS limit (settle): %s", hipGetErrorString(e1)); \
                         return PK_E_LAUNCH;                                                                         \
                     }                                                                                               \
                     settle_attr_set.done();                                                                         \
@@ -1665,17 +1665,28 @@ static int pk_sweep_launches(hipStream_t st, int64_t n_users, int64_t n_items, i
     return PK_OK;
 }
 
+// The arguments both sweep entries share (polara_hip.h), checked before anything is launched.  The users' side is given ONCE:
+// packed (Ep_dev with user_bound_dev) or as rows of E (E_dev .. user_bound_out_dev), and what the other form would read
+// or write must be NULL — nothing is ignored silently.
 static int pk_score_check_args(const char *who, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
-                               const float *Ep_dev, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                               const int32_t *seen_ntiles_dev, void *state_dev, const float *user_bound_dev,
-                               const float *tile_bound_dev, const uint32_t *seen_dense_dev, const int32_t *seen_skip_dev,
-                               int32_t dense_tiles, const UserRows *rows = nullptr) {
+                               const float *Ep_dev, const float *user_bound_dev, const double *E_dev, int64_t lde,
+                               const double *extra_dev, int64_t extra_ld, const float *user_bound_out_dev,
+                               const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev, const int32_t *seen_ntiles_dev,
+                               void *state_dev, const float *tile_bound_dev, const uint32_t *seen_dense_dev,
+                               const int32_t *seen_skip_dev, int32_t dense_tiles, bool settle) {
     PK_REQUIRE(n_users >= 1 && n_items >= 1 && n_items < 0x7fffff00LL, "%s: bad sizes", who);
-    if (rows) {
+    PK_REQUIRE((Ep_dev != nullptr) != (E_dev != nullptr), "%s: the users' side is Ep_dev or E_dev (exactly one of them)", who);
+    if (E_dev) {
         // the users' side comes from rows of E: 16-byte aligned, even leading dimension (a lane fetches two columns per load)
-        PK_REQUIRE(rows->E != nullptr && rows->ld >= K && rows->ld % 2 == 0 && ((uintptr_t)rows->E % 16) == 0 && rows->K == K,
+        PK_REQUIRE(user_bound_dev == nullptr, "%s: user_bound goes with Ep_dev (the rows of E give the bound themselves)", who);
+        PK_REQUIRE(lde >= K && lde % 2 == 0 && ((uintptr_t)E_dev % 16) == 0,
                    "%s: E rows must be 16-byte aligned with an even leading dimension >= K", who);
-        PK_REQUIRE(rows->extra == nullptr || rows->extra_ld >= 1, "%s: bad stride of the extra term", who);
+        PK_REQUIRE(extra_dev == nullptr || extra_ld >= 1, "%s: bad stride of the extra term", who);
+    } else {
+        PK_REQUIRE(extra_dev == nullptr && user_bound_out_dev == nullptr && !settle,
+                   "%s: extra, user_bound_out and settle go with E_dev (packed fragments carry neither)", who);
+        PK_REQUIRE((user_bound_dev == nullptr) == (tile_bound_dev == nullptr),
+                   "%s: user_bound and tile_bound go together (both or neither)", who);
     }
     PK_REQUIRE(dense_tiles >= 0 && (dense_tiles == 0 || (seen_dense_dev && seen_skip_dev && seen_ptr_dev)),
                "%s: dense seen masks need seen_dense, seen_skip and the seen-tile stream", who);
@@ -1685,105 +1696,63 @@ static int pk_score_check_args(const char *who, int64_t n_users, int64_t n_items
     PK_REQUIRE((seen_ptr_dev == nullptr) == (seen_tiles_dev == nullptr) &&
                    (seen_ptr_dev == nullptr) == (seen_ntiles_dev == nullptr),
                "%s: seen_ptr, seen_tiles, seen_ntiles go together (all or none)", who);
-    PK_REQUIRE(rows != nullptr || (user_bound_dev == nullptr) == (tile_bound_dev == nullptr),
-               "%s: user_bound and tile_bound go together (both or neither)", who);
     return PK_OK;
 }
 
-static int pk_score_candidates_impl(const char *who, void *stream, int64_t n_users, int64_t n_items, int32_t K,
-                                    const float *Vp_dev, const float *Ep_dev, const UserRows *rows, const int64_t *seen_ptr_dev,
-                                    const uint64_t *seen_tiles_dev, const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits,
-                                    float *cand_score_dev, int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
-                                    const float *user_bound_dev, const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                    const int32_t *seen_skip_dev, int32_t dense_tiles, const SettleExit *settle = nullptr) {
-    const int rc = pk_score_check_args(who, n_users, n_items, K, Vp_dev, Ep_dev, seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev,
-                                       state_dev, user_bound_dev, tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles, rows);
-    if (rc != PK_OK) return rc;
-    PK_REQUIRE(splits >= 1 && splits * KC <= 64, "%s: need 1 <= splits and splits*KC <= 64", who);
-    SeenDense dense{seen_dense_dev, seen_skip_dev, seen_ptr_dev ? dense_tiles : 0};
-    return pk_sweep_launches(pk_stream(stream), n_users, n_items, (int)pk_ceil_div(n_items, 32), K, Vp_dev, Ep_dev,
-                             seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, splits, splits, cand_score_dev, cand_idx_dev,
-                             state_dev, tiles_per_chunk, user_bound_dev, tile_bound_dev, dense, SweepPhase{0, 0, nullptr, 0},
-                             rows ? *rows : UserRows{nullptr, 0, 0, nullptr, 0, 0.0, nullptr}, settle);
+static UserRows pk_user_rows(const double *E_dev, int64_t lde, int32_t K, const double *extra_dev, int64_t extra_ld,
+                             double extra_scale, float *user_bound_out_dev) {
+    if (!E_dev) return UserRows{nullptr, 0, 0, nullptr, 0, 0.0, nullptr};
+    return UserRows{E_dev, lde, K, extra_dev, extra_ld, extra_scale, user_bound_out_dev};
 }
 
-extern "C" int pk_score_candidates_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K,
-                                       const float *Vp_dev, const float *Ep_dev, const int64_t *seen_ptr_dev,
-                                       const uint64_t *seen_tiles_dev, const int32_t *seen_ntiles_dev,
-                                       int32_t KC, int32_t splits,
-                                       float *cand_score_dev, int32_t *cand_idx_dev, void *state_dev,
-                                       int32_t tiles_per_chunk, const float *user_bound_dev,
-                                       const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                       const int32_t *seen_skip_dev, int32_t dense_tiles) {
-    return pk_score_candidates_impl("pk_score_candidates_f32", stream, n_users, n_items, K, Vp_dev, Ep_dev, nullptr, seen_ptr_dev,
-                                    seen_tiles_dev, seen_ntiles_dev, KC, splits, cand_score_dev, cand_idx_dev, state_dev,
-                                    tiles_per_chunk, user_bound_dev, tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles);
-}
-
-// The same sweep with the users' side taken from the fp64 rows of E (no packed copy of E, no packing launch: every wave
-// builds its 32 users' fragments and pruning bounds in its prologue — see UserRows).  tile_bound_dev == NULL: full sweep.
-// 1: this library's sweeps take the users' side from the rows of E (pk_score_*_rows_f32); a probe build of the experiment tree says 0
+// 1: this library's sweeps take the users' side from the rows of E (E_dev of the two entries); a probe build of the experiment tree says 0
 extern "C" int pk_sweep_takes_rows(void) { return 1; }
 
-// user_bound_out_dev (float [n_users], may be NULL): the users' side of the pruning bound as the sweep computed it, for
-// pk_rescore_f64
-extern "C" int pk_score_candidates_rows_bound_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
-                                                  const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
-                                                  double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                                                  const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits, float *cand_score_dev,
-                                                  int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
-                                                  const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                                  const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev) {
-    const UserRows rows{E_dev, lde, K, extra_dev, extra_ld, extra_scale, user_bound_out_dev};
-    return pk_score_candidates_impl("pk_score_candidates_rows_f32", stream, n_users, n_items, K, Vp_dev, nullptr, &rows,
-                                    seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, splits, cand_score_dev, cand_idx_dev,
-                                    state_dev, tiles_per_chunk, nullptr, tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles);
-}
-
-extern "C" int pk_score_candidates_rows_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
-                                            const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
-                                            double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                                            const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits, float *cand_score_dev,
-                                            int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
-                                            const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                            const int32_t *seen_skip_dev, int32_t dense_tiles) {
-    return pk_score_candidates_rows_bound_f32(stream, n_users, n_items, K, Vp_dev, E_dev, lde, extra_dev, extra_ld, extra_scale,
-                                              seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, splits, cand_score_dev, cand_idx_dev,
-                                              state_dev, tiles_per_chunk, tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles,
-                                              nullptr);
-}
-
 // 1: a single pruned sweep with this many candidates can settle its clear-cut users when they leave the sweep
-// (pk_score_candidates_rows_settle_f32) — lists in LDS (KC <= 32) and both options on: pk_set_option("sweep_settle", 0)
+// (pk_score_candidates_f32 with a settle block) — lists in LDS (KC <= 32) and both options on: pk_set_option("sweep_settle", 0)
 // sends a pass back to the tier of the first re-scoring, "rescore_settle" = 0 switches the rule off wherever it runs
 extern "C" int pk_sweep_settles(int32_t KC) {
     return (KC == 16 || KC == 32) && pk_option("sweep_settle", 1) && pk_option("rescore_settle", 1);
 }
 
-// The single pruned sweep from the rows of E (pk_score_candidates_rows_bound_f32 with splits = 1) that applies the settle rule
-// of the first re-scoring to a group's final lists when the group leaves the sweep: see PkSweepSettle (polara_hip.h) and
-// SettleExit above.  The first re-scoring then runs on open_list / open_count (pk_rescore_f64 with a row list: tier off).
-extern "C" int pk_score_candidates_rows_settle_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
-                                                   const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
-                                                   double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                                                   const int32_t *seen_ntiles_dev, int32_t KC, float *cand_score_dev,
-                                                   int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
-                                                   const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                                   const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev,
-                                                   const PkSweepSettle *settle) {
-    const char *who = "pk_score_candidates_rows_settle_f32";
-    PK_REQUIRE(settle != nullptr && (KC == 16 || KC == 32), "%s: needs the settle block and KC = 16 or 32", who);
-    PK_REQUIRE(n_users >= 1 && n_users <= 0x7fffffffLL, "%s: user ids must fit the int32 open list", who);
-    PK_REQUIRE(tile_bound_dev != nullptr && extra_dev != nullptr && extra_ld >= 1,
-               "%s: needs the pruning bound and the fold-in's error weights", who);
-    PK_REQUIRE(settle->topk >= 1 && settle->topk <= KC && settle->vmax >= 0.0, "%s: need 1 <= topk <= KC", who);
-    PK_REQUIRE(settle->out_idx && settle->flags && settle->open_list && settle->open_count, "%s: null outputs", who);
-    const UserRows rows{E_dev, lde, K, extra_dev, extra_ld, extra_scale, user_bound_out_dev};
-    const SettleExit sx{settle->topk, settle->vmax, settle->item_norm, settle->out_idx, settle->out_perm, settle->flags,
+// The single sweep: one launch sequence, `splits` lists per user.  The users' side is packed (Ep_dev, user_bound_dev) or taken
+// from the fp64 rows of E (no packed copy of E, no packing launch: every wave builds its 32 users' fragments and pruning
+// bounds in its prologue — see UserRows); tile_bound_dev == NULL: full sweep.  user_bound_out_dev (float [n_users], may be
+// NULL): the users' side of the pruning bound as the sweep computed it, for pk_rescore_f64.  settle (may be NULL): the
+// pruned sweep from the rows of E with splits = 1 applies the settle rule of the first re-scoring to a group's final lists
+// when the group leaves the sweep: see PkSweepSettle (polara_hip.h) and SettleExit above.  The first re-scoring then runs on
+// open_list / open_count (pk_rescore_f64 with a row list: tier off).
+extern "C" int pk_score_candidates_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                                       const float *Ep_dev, const float *user_bound_dev, const double *E_dev, int64_t lde,
+                                       const double *extra_dev, int64_t extra_ld, double extra_scale, float *user_bound_out_dev,
+                                       const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
+                                       const int32_t *seen_ntiles_dev, int32_t KC, int32_t splits, float *cand_score_dev,
+                                       int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
+                                       const float *tile_bound_dev, const uint32_t *seen_dense_dev,
+                                       const int32_t *seen_skip_dev, int32_t dense_tiles, const PkSweepSettle *settle) {
+    const char *who = "pk_score_candidates_f32";
+    const int rc = pk_score_check_args(who, n_users, n_items, K, Vp_dev, Ep_dev, user_bound_dev, E_dev, lde, extra_dev, extra_ld,
+                                       user_bound_out_dev, seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, state_dev,
+                                       tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles, settle != nullptr);
+    if (rc != PK_OK) return rc;
+    PK_REQUIRE(splits >= 1 && splits * KC <= 64, "%s: need 1 <= splits and splits*KC <= 64", who);
+    SettleExit sx{0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (settle) {
+        PK_REQUIRE(splits == 1 && (KC == 16 || KC == 32), "%s: settle needs splits = 1 and KC = 16 or 32", who);
+        PK_REQUIRE(n_users <= 0x7fffffffLL, "%s: settle: user ids must fit the int32 open list", who);
+        PK_REQUIRE(tile_bound_dev != nullptr && extra_dev != nullptr,
+                   "%s: settle needs the pruning bound and the fold-in's error weights", who);
+        PK_REQUIRE(settle->topk >= 1 && settle->topk <= KC && settle->vmax >= 0.0, "%s: settle: need 1 <= topk <= KC and vmax >= 0", who);
+        PK_REQUIRE(settle->out_idx && settle->flags && settle->open_list && settle->open_count, "%s: settle: null outputs", who);
+        sx = SettleExit{settle->topk, settle->vmax, settle->item_norm, settle->out_idx, settle->out_perm, settle->flags,
                         settle->open_list, settle->open_count};
-    return pk_score_candidates_impl(who, stream, n_users, n_items, K, Vp_dev, nullptr, &rows, seen_ptr_dev, seen_tiles_dev,
-                                    seen_ntiles_dev, KC, 1, cand_score_dev, cand_idx_dev, state_dev, tiles_per_chunk, nullptr,
-                                    tile_bound_dev, seen_dense_dev, seen_skip_dev, dense_tiles, &sx);
+    }
+    SeenDense dense{seen_dense_dev, seen_skip_dev, seen_ptr_dev ? dense_tiles : 0};
+    return pk_sweep_launches(pk_stream(stream), n_users, n_items, (int)pk_ceil_div(n_items, 32), K, Vp_dev, Ep_dev,
+                             seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, splits, splits, cand_score_dev, cand_idx_dev,
+                             state_dev, tiles_per_chunk, user_bound_dev, tile_bound_dev, dense, SweepPhase{0, 0, nullptr, 0},
+                             pk_user_rows(E_dev, lde, K, extra_dev, extra_ld, extra_scale, user_bound_out_dev),
+                             settle ? &sx : nullptr);
 }
 
 // ---- two-phase sweep -------------------------------------------------------------------------------------------------
@@ -1915,22 +1884,24 @@ extern "C" int pk_score_two_phase_plan(int64_t n_users, int64_t n_items, int32_t
 //   work_score / work_idx  [(splits + 1) * n_pad * KC]   the raw lists (slot 0: head), n_pad = n_users rounded up to 32
 //   cand_score / cand_idx  [n_pad * KC]                   the merged list: what pk_rescore_f64 takes with splits = 1
 //   state                  pk_score_state_bytes(n_users, splits + 1)
-static int pk_score_two_phase_impl(const char *who, void *stream, int64_t n_users, int64_t n_items, int32_t K,
-                                   const float *Vp_dev, const float *Ep_dev, const UserRows *rows_in, const int64_t *seen_ptr_dev,
-                                   const uint64_t *seen_tiles_dev, const int32_t *seen_ntiles_dev,
-                                   int32_t KC, int32_t head_tiles, int32_t splits,
-                                   float *work_score_dev, int32_t *work_idx_dev,
-                                   float *cand_score_dev, int32_t *cand_idx_dev, void *state_dev,
-                                   int32_t tiles_per_chunk, const float *user_bound_dev,
-                                   const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                   const int32_t *seen_skip_dev, int32_t dense_tiles) {
-    int rc = pk_score_check_args(who, n_users, n_items, K, Vp_dev, Ep_dev, seen_ptr_dev,
-                                 seen_tiles_dev, seen_ntiles_dev, state_dev, user_bound_dev, tile_bound_dev,
-                                 seen_dense_dev, seen_skip_dev, dense_tiles, rows_in);
+// The users' side as in pk_score_candidates_f32: packed, or from the rows of E (user_bound_out_dev as there).
+extern "C" int pk_score_two_phase_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
+                                      const float *Ep_dev, const float *user_bound_dev, const double *E_dev, int64_t lde,
+                                      const double *extra_dev, int64_t extra_ld, double extra_scale, float *user_bound_out_dev,
+                                      const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
+                                      const int32_t *seen_ntiles_dev, int32_t KC, int32_t head_tiles, int32_t splits,
+                                      float *work_score_dev, int32_t *work_idx_dev, float *cand_score_dev,
+                                      int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
+                                      const float *tile_bound_dev, const uint32_t *seen_dense_dev,
+                                      const int32_t *seen_skip_dev, int32_t dense_tiles) {
+    const char *who = "pk_score_two_phase_f32";
+    int rc = pk_score_check_args(who, n_users, n_items, K, Vp_dev, Ep_dev, user_bound_dev, E_dev, lde, extra_dev, extra_ld,
+                                 user_bound_out_dev, seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, state_dev, tile_bound_dev,
+                                 seen_dense_dev, seen_skip_dev, dense_tiles, false);
     if (rc != PK_OK) return rc;
-    const UserRows rows = rows_in ? *rows_in : UserRows{nullptr, 0, 0, nullptr, 0, 0.0, nullptr};
+    const UserRows rows = pk_user_rows(E_dev, lde, K, extra_dev, extra_ld, extra_scale, user_bound_out_dev);
     const int n_tiles = (int)pk_ceil_div(n_items, 32);
-    PK_REQUIRE((user_bound_dev || rows_in) && tile_bound_dev, "%s: needs the pruning bounds", who);
+    PK_REQUIRE((user_bound_dev || E_dev) && tile_bound_dev, "%s: needs the pruning bounds", who);
     PK_REQUIRE(KC >= 1 && KC <= 64 && splits >= 1 && (splits + 1) * KC <= 256 && head_tiles >= 1 && head_tiles < n_tiles,
                "%s: need 1 <= head_tiles < n_tiles and (splits + 1) * KC <= 256", who);
     PK_REQUIRE(work_score_dev && work_idx_dev && cand_score_dev && cand_idx_dev, "%s: null list buffers", who);
@@ -1961,51 +1932,6 @@ static int pk_score_two_phase_impl(const char *who, void *stream, int64_t n_user
 #undef PK_MERGE
     PK_CHECK_LAUNCH("merge_candidates_kernel");
     return PK_OK;
-}
-
-extern "C" int pk_score_two_phase_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K,
-                                      const float *Vp_dev, const float *Ep_dev, const int64_t *seen_ptr_dev,
-                                      const uint64_t *seen_tiles_dev, const int32_t *seen_ntiles_dev,
-                                      int32_t KC, int32_t head_tiles, int32_t splits,
-                                      float *work_score_dev, int32_t *work_idx_dev,
-                                      float *cand_score_dev, int32_t *cand_idx_dev, void *state_dev,
-                                      int32_t tiles_per_chunk, const float *user_bound_dev,
-                                      const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                      const int32_t *seen_skip_dev, int32_t dense_tiles) {
-    return pk_score_two_phase_impl("pk_score_two_phase_f32", stream, n_users, n_items, K, Vp_dev, Ep_dev, nullptr, seen_ptr_dev,
-                                   seen_tiles_dev, seen_ntiles_dev, KC, head_tiles, splits, work_score_dev, work_idx_dev,
-                                   cand_score_dev, cand_idx_dev, state_dev, tiles_per_chunk, user_bound_dev, tile_bound_dev,
-                                   seen_dense_dev, seen_skip_dev, dense_tiles);
-}
-
-// the two-phase sweep with the users' side from the rows of E (see pk_score_candidates_rows_f32)
-extern "C" int pk_score_two_phase_rows_bound_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
-                                                 const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
-                                                 double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                                                 const int32_t *seen_ntiles_dev, int32_t KC, int32_t head_tiles, int32_t splits,
-                                                 float *work_score_dev, int32_t *work_idx_dev, float *cand_score_dev,
-                                                 int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
-                                                 const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                                 const int32_t *seen_skip_dev, int32_t dense_tiles, float *user_bound_out_dev) {
-    const UserRows rows{E_dev, lde, K, extra_dev, extra_ld, extra_scale, user_bound_out_dev};
-    return pk_score_two_phase_impl("pk_score_two_phase_rows_f32", stream, n_users, n_items, K, Vp_dev, nullptr, &rows, seen_ptr_dev,
-                                   seen_tiles_dev, seen_ntiles_dev, KC, head_tiles, splits, work_score_dev, work_idx_dev,
-                                   cand_score_dev, cand_idx_dev, state_dev, tiles_per_chunk, nullptr, tile_bound_dev,
-                                   seen_dense_dev, seen_skip_dev, dense_tiles);
-}
-
-extern "C" int pk_score_two_phase_rows_f32(void *stream, int64_t n_users, int64_t n_items, int32_t K, const float *Vp_dev,
-                                           const double *E_dev, int64_t lde, const double *extra_dev, int64_t extra_ld,
-                                           double extra_scale, const int64_t *seen_ptr_dev, const uint64_t *seen_tiles_dev,
-                                           const int32_t *seen_ntiles_dev, int32_t KC, int32_t head_tiles, int32_t splits,
-                                           float *work_score_dev, int32_t *work_idx_dev, float *cand_score_dev,
-                                           int32_t *cand_idx_dev, void *state_dev, int32_t tiles_per_chunk,
-                                           const float *tile_bound_dev, const uint32_t *seen_dense_dev,
-                                           const int32_t *seen_skip_dev, int32_t dense_tiles) {
-    return pk_score_two_phase_rows_bound_f32(stream, n_users, n_items, K, Vp_dev, E_dev, lde, extra_dev, extra_ld, extra_scale,
-                                             seen_ptr_dev, seen_tiles_dev, seen_ntiles_dev, KC, head_tiles, splits, work_score_dev,
-                                             work_idx_dev, cand_score_dev, cand_idx_dev, state_dev, tiles_per_chunk, tile_bound_dev,
-                                             seen_dense_dev, seen_skip_dev, dense_tiles, nullptr);
 }
 
 // eager load of this translation unit's code object (pk_warm_up, api.cpp): the runtime loads a code object at the first

@@ -1284,74 +1284,77 @@ class HipOps:
         return (E.dtype == torch.float64 and E.dim() == 2 and E.stride(1) == 1 and E.stride(0) % 2 == 0 and E.data_ptr() % 16 == 0)
 
     @staticmethod
-    def _rows_args(E_rows, K):
+    def _users_side(Ep, user_bound, E_rows, bound_out, K, n_users):
+        """the users' side of a sweep entry, eight arguments: packed (Ep, user_bound), or from rows (E, lde, extra, extra_ld,
+        extra_scale, user_bound_out) — with `E_rows`, Ep and user_bound are not used"""
+        if E_rows is None:
+            return _ptr(Ep), _ptr(user_bound), None, 0, None, 0, 0.0, _ptr(bound_out)
         E, extra, scale = E_rows
         assert E.shape[1] >= K
+        assert bound_out is None or (bound_out.dtype == torch.float32 and bound_out.is_contiguous() and bound_out.numel() == n_users)
         e_ld = 0 if extra is None else extra.stride(0)      # a column of E's own block: one entry per row, rows `stride` apart
-        return _ptr(E), E.stride(0), _ptr(extra), int(e_ld), float(scale if extra is not None else 0.0)
+        return (None, None, _ptr(E), E.stride(0), _ptr(extra), int(e_ld), float(scale if extra is not None else 0.0),
+                _ptr(bound_out))
+
+    def _sweep_state(self, n_users, slots):
+        """the state buffer of a sweep with `slots` lists per user: one per launch stream, grown on demand"""
+        need = self.lib.pk_score_state_bytes(n_users, slots)
+        if self._score_states is None:
+            self._score_states = {}
+        skey = self.stream_key()
+        if skey not in self._score_states or self._score_states[skey].numel() < need:
+            self._score_states[skey] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._score_state = self._score_states[skey]
+        return self._score_state
+
+    @staticmethod
+    def _seen_side(seen_ptr, seen_tiles, seen_dense):
+        """(seen_ptr, tiles, ntiles) and (dense, skip, dense_tiles) of a sweep entry as pointers; no seen lists: nothing is masked"""
+        tiles = ntiles = dense = skip = None
+        dtiles = 0
+        if seen_ptr is not None:
+            tiles, ntiles = seen_tiles
+            if seen_dense is not None:
+                dense, skip, dtiles = seen_dense
+        return (_ptr(seen_ptr), _ptr(tiles), _ptr(ntiles)), (_ptr(dense), _ptr(skip), int(dtiles))
 
     def score_candidates(self, Vp, Ep, n_users, n_items, K, seen_ptr, seen_idx, KC, splits=1, tiles_per_chunk=0,
                          user_bound=None, tile_bound=None, seen_tiles=None, seen_dense=None, E_rows=None, bound_out=None,
                          settle=None):
-        """E_rows = (E fp64 [n_users x >= K], extra column or None, extra_scale): the users' fragments and pruning bounds are
-        built inside the sweep (pk_score_candidates_rows_f32; Ep and user_bound are not used, tile_bound alone switches the
-        pruning on).  bound_out (float32 [n_users], E_rows only): the sweep stores the users' bounds there
-        (pk_score_candidates_rows_bound_f32) — what `rescore_topk` takes as `user_norm`.
+        """The candidate sweep as one launch sequence (pk_score_candidates_f32).
+        E_rows = (E fp64 [n_users x >= K], extra column or None, extra_scale): the users' fragments and pruning bounds are
+        built inside the sweep (Ep and user_bound are not used, tile_bound alone switches the pruning on).  bound_out
+        (float32 [n_users], E_rows only): the sweep stores the users' bounds there — what `rescore_topk` takes as `user_norm`.
         settle (E_rows with its extra column, tile_bound, splits == 1, `sweep_settles(KC)`): dict(topk, vmax, item_norm, out_idx,
-        out_perm, flags, open_list, open_count) — the settle rule of the first re-scoring runs where a group leaves the sweep
-        (pk_score_candidates_rows_settle_f32): settled users get their ids and flag 8 there and no candidate row, everybody
-        else is appended to open_list behind the zeroed device counter open_count — the row list of the first re-scoring."""
+        out_perm, flags, open_list, open_count) — the settle rule of the first re-scoring runs where a group leaves the sweep:
+        settled users get their ids and flag 8 there and no candidate row, everybody else is appended to open_list behind the
+        zeroed device counter open_count — the row list of the first re-scoring."""
         n_pad = -(-n_users // 32) * 32
-        need = self.lib.pk_score_state_bytes(n_users, splits)
-        if self._score_states is None:
-            self._score_states = {}
-        skey = self.stream_key()   # one state buffer per launch stream
-        if skey not in self._score_states or self._score_states[skey].numel() < need:
-            self._score_states[skey] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        self._score_state = self._score_states[skey]
+        state = self._sweep_state(n_users, splits)
         cs = torch.empty(splits * n_pad * KC, dtype=torch.float32, device=self.device)
         ci = torch.empty(splits * n_pad * KC, dtype=torch.int32, device=self.device)
-        tiles = ntiles = dense = skip = None
-        dtiles = 0
-        if seen_ptr is not None:
-            tiles, ntiles = seen_tiles if seen_tiles is not None else self.seen_tiles(seen_ptr, seen_idx, n_users)
-            if seen_dense is not None:
-                dense, skip, dtiles = seen_dense
-        if E_rows is not None:
-            ep, lde, xp, xld, xs = self._rows_args(E_rows, K)
-            args = (self.stream(), n_users, n_items, K, _ptr(Vp), ep, lde, xp, xld, xs, _ptr(seen_ptr), _ptr(tiles), _ptr(ntiles),
-                    KC, splits, _ptr(cs), _ptr(ci), _ptr(self._score_state), tiles_per_chunk or self.score_tiles_per_chunk,
-                    _ptr(tile_bound), _ptr(dense), _ptr(skip), int(dtiles))
-            with self._timed('score_candidates', (n_users, n_items, K)):
-                if settle is not None:
-                    assert splits == 1 and tile_bound is not None and E_rows[1] is not None
-                    q = settle
-                    oi, fl, ol, oc = q['out_idx'], q['flags'], q['open_list'], q['open_count']
-                    assert oi.dtype == torch.int64 and oi.is_contiguous() and tuple(oi.shape) == (n_users, int(q['topk']))
-                    assert fl.dtype == torch.int32 and fl.is_contiguous() and fl.numel() == n_users
-                    assert ol.dtype == torch.int32 and ol.is_contiguous() and ol.numel() >= n_users
-                    assert oc.dtype == torch.int32 and oc.numel() == 1
-                    nrm, perm = q.get('item_norm'), q.get('out_perm')
-                    assert nrm is None or (nrm.dtype == torch.float32 and nrm.is_contiguous() and nrm.numel() == n_items)
-                    assert perm is None or (perm.dtype == torch.int64 and perm.is_contiguous() and perm.numel() == n_users)
-                    assert bound_out is None or (bound_out.dtype == torch.float32 and bound_out.is_contiguous() and bound_out.numel() == n_users)
-                    blk = _lib.PkSweepSettle(int(q['topk']), float(q['vmax']), _ptr(nrm), _ptr(oi), _ptr(perm), _ptr(fl), _ptr(ol), _ptr(oc))
-                    _lib.check(self.lib.pk_score_candidates_rows_settle_f32(*args[:14], *args[15:], _ptr(bound_out), C.byref(blk)),
-                               'pk_score_candidates_rows_settle_f32')
-                elif bound_out is None:
-                    _lib.check(self.lib.pk_score_candidates_rows_f32(*args), 'pk_score_candidates_rows_f32')
-                else:
-                    assert bound_out.dtype == torch.float32 and bound_out.is_contiguous() and bound_out.numel() == n_users
-                    _lib.check(self.lib.pk_score_candidates_rows_bound_f32(*args, _ptr(bound_out)),
-                               'pk_score_candidates_rows_bound_f32')
-            return cs, ci
+        if seen_ptr is not None and seen_tiles is None:
+            seen_tiles = self.seen_tiles(seen_ptr, seen_idx, n_users)
+        seen, dense = self._seen_side(seen_ptr, seen_tiles, seen_dense)
+        blk = None
+        if settle is not None:
+            assert E_rows is not None and splits == 1 and tile_bound is not None and E_rows[1] is not None
+            q = settle
+            oi, fl, ol, oc = q['out_idx'], q['flags'], q['open_list'], q['open_count']
+            assert oi.dtype == torch.int64 and oi.is_contiguous() and tuple(oi.shape) == (n_users, int(q['topk']))
+            assert fl.dtype == torch.int32 and fl.is_contiguous() and fl.numel() == n_users
+            assert ol.dtype == torch.int32 and ol.is_contiguous() and ol.numel() >= n_users
+            assert oc.dtype == torch.int32 and oc.numel() == 1
+            nrm, perm = q.get('item_norm'), q.get('out_perm')
+            assert nrm is None or (nrm.dtype == torch.float32 and nrm.is_contiguous() and nrm.numel() == n_items)
+            assert perm is None or (perm.dtype == torch.int64 and perm.is_contiguous() and perm.numel() == n_users)
+            blk = C.byref(_lib.PkSweepSettle(int(q['topk']), float(q['vmax']), _ptr(nrm), _ptr(oi), _ptr(perm), _ptr(fl), _ptr(ol),
+                                             _ptr(oc)))
+        users = self._users_side(Ep, user_bound, E_rows, bound_out, K, n_users)
         with self._timed('score_candidates', (n_users, n_items, K)):
-            _lib.check(self.lib.pk_score_candidates_f32(self.stream(), n_users, n_items, K, _ptr(Vp), _ptr(Ep),
-                                                        _ptr(seen_ptr), _ptr(tiles), _ptr(ntiles), KC, splits,
-                                                        _ptr(cs), _ptr(ci),
-                                                        _ptr(self._score_state),
-                                                        tiles_per_chunk or self.score_tiles_per_chunk,
-                                                        _ptr(user_bound), _ptr(tile_bound), _ptr(dense), _ptr(skip), int(dtiles)),
+            _lib.check(self.lib.pk_score_candidates_f32(self.stream(), n_users, n_items, K, _ptr(Vp), *users, *seen, KC, splits,
+                                                        _ptr(cs), _ptr(ci), _ptr(state),
+                                                        tiles_per_chunk or self.score_tiles_per_chunk, _ptr(tile_bound), *dense, blk),
                        'pk_score_candidates_f32')
         return cs, ci
 
@@ -1366,17 +1369,11 @@ class HipOps:
                         seen_tiles=None, seen_dense=None, tiles_per_chunk=0, E_rows=None, bound_out=None, work=None):
         """The pruned candidate sweep in two phases (pk_score_two_phase_f32): head sweep, `splits` sweeps of the tail from
         the head's thresholds, merge.  Returns the merged (scores, ids) [n_pad x KC] — a single list per user.
-        bound_out: as in `score_candidates`.  work = (float32, int32) [(splits + 1) * n_pad * KC]: the caller's arrays for the
-        raw lists (slot 0: head, then the splits) instead of scratch of the call's own — whoever wants to read them."""
+        E_rows, bound_out: as in `score_candidates`.  work = (float32, int32) [(splits + 1) * n_pad * KC]: the caller's arrays
+        for the raw lists (slot 0: head, then the splits) instead of scratch of the call's own — whoever wants to read them."""
         n_pad = -(-n_users // 32) * 32
         total = splits + 1
-        need = self.lib.pk_score_state_bytes(n_users, total)
-        if self._score_states is None:
-            self._score_states = {}
-        skey = self.stream_key()   # one state buffer per launch stream
-        if skey not in self._score_states or self._score_states[skey].numel() < need:
-            self._score_states[skey] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        self._score_state = self._score_states[skey]
+        state = self._sweep_state(n_users, total)
         if work is not None:
             ws, wi = work
             assert ws.dtype == torch.float32 and wi.dtype == torch.int32 and ws.is_contiguous() and wi.is_contiguous()
@@ -1386,31 +1383,13 @@ class HipOps:
             wi = torch.empty(total * n_pad * KC, dtype=torch.int32, device=self.device)
         cs = torch.empty(n_pad * KC, dtype=torch.float32, device=self.device)
         ci = torch.empty(n_pad * KC, dtype=torch.int32, device=self.device)
-        tiles = ntiles = dense = skip = None
-        dtiles = 0
-        if seen_ptr is not None:
-            tiles, ntiles = seen_tiles
-            if seen_dense is not None:
-                dense, skip, dtiles = seen_dense
-        if E_rows is not None:
-            ep, lde, xp, xld, xs = self._rows_args(E_rows, K)
-            args = (self.stream(), n_users, n_items, K, _ptr(Vp), ep, lde, xp, xld, xs, _ptr(seen_ptr), _ptr(tiles), _ptr(ntiles),
-                    KC, int(head_tiles), int(splits), _ptr(ws), _ptr(wi), _ptr(cs), _ptr(ci), _ptr(self._score_state),
-                    tiles_per_chunk or self.score_tiles_per_chunk, _ptr(tile_bound), _ptr(dense), _ptr(skip), int(dtiles))
-            with self._timed('score_candidates', (n_users, n_items, K)):
-                if bound_out is None:
-                    _lib.check(self.lib.pk_score_two_phase_rows_f32(*args), 'pk_score_two_phase_rows_f32')
-                else:
-                    assert bound_out.dtype == torch.float32 and bound_out.is_contiguous() and bound_out.numel() == n_users
-                    _lib.check(self.lib.pk_score_two_phase_rows_bound_f32(*args, _ptr(bound_out)),
-                               'pk_score_two_phase_rows_bound_f32')
-            return cs, ci
+        seen, dense = self._seen_side(seen_ptr, seen_tiles, seen_dense)
+        users = self._users_side(Ep, user_bound, E_rows, bound_out, K, n_users)
         with self._timed('score_candidates', (n_users, n_items, K)):
-            _lib.check(self.lib.pk_score_two_phase_f32(self.stream(), n_users, n_items, K, _ptr(Vp), _ptr(Ep), _ptr(seen_ptr),
-                                                       _ptr(tiles), _ptr(ntiles), KC, int(head_tiles), int(splits),
-                                                       _ptr(ws), _ptr(wi), _ptr(cs), _ptr(ci), _ptr(self._score_state),
-                                                       tiles_per_chunk or self.score_tiles_per_chunk,
-                                                       _ptr(user_bound), _ptr(tile_bound), _ptr(dense), _ptr(skip), int(dtiles)),
+            _lib.check(self.lib.pk_score_two_phase_f32(self.stream(), n_users, n_items, K, _ptr(Vp), *users, *seen, KC,
+                                                       int(head_tiles), int(splits), _ptr(ws), _ptr(wi), _ptr(cs), _ptr(ci),
+                                                       _ptr(state), tiles_per_chunk or self.score_tiles_per_chunk,
+                                                       _ptr(tile_bound), *dense),
                        'pk_score_two_phase_f32')
         return cs, ci
 

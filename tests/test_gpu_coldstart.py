@@ -8,6 +8,7 @@ import torch
 import coldstart_reference as ref
 from conftest import load_golden
 from i2i_reference import tie_aware_mismatches
+from recorded_calls import sweeps
 from test_coldstart_host import FACTOR_FIXTURES, check_model_against_fixture, model_for
 
 pytestmark = pytest.mark.gpu
@@ -188,5 +189,6 @@ def test_model_keeps_the_user_factors_on_the_device(hip_ops):
     names = [n for n, _, _ in rec.calls]
     assert np.array_equal(again, g['recs'])
     assert 'pk_spmm_csr_ex' in names and 'pk_tsmm_f64' in names and 'pk_map_ids_i64' in names
-    assert any(n in ('pk_score_candidates_rows_f32', 'pk_score_two_phase_rows_f32') for n in names)
-    assert 'pk_pack_frag_bound_f32' not in names and 'pk_score_candidates_f32' not in names and 'pk_score_two_phase_f32' not in names
+    swept = sweeps(rec.calls)
+    assert swept and all(s['E'] and not s['Ep'] and not s['user_bound'] for s in swept), swept       # from rows, not packed
+    assert 'pk_pack_frag_bound_f32' not in names

@@ -599,7 +599,7 @@ def test_two_phase_sweep_equals_single_sweep(hip_ops, cfg, monkeypatch, pk_optio
                                  dict(n_users=2100, n_items=2000, K=24, topk=10)])
 def test_sweep_from_the_rows_of_E_equals_the_packed_route(hip_ops, cfg, monkeypatch):
     """Round 5: the sweep's waves build their users' MFMA fragments and pruning bounds from the fp64 rows of E in their
-    prologue (pk_score_candidates_rows_f32 / pk_score_two_phase_rows_f32) instead of reading what pk_pack_frag_bound_f32
+    prologue (E_dev of pk_score_candidates_f32 / pk_score_two_phase_f32) instead of reading what pk_pack_frag_bound_f32
     wrote.  Kernel level: the raw candidate lists (scores bit for bit, ids) of both routes are EQUAL — pruned and full,
     with the error-weight column of an approximate fold-in in the bound, partial last groups, strided rows.  Pass level:
     `scoring.recommend` with the route switched off and on returns the same ids and scores (exact and ids-only passes,

@@ -9,6 +9,7 @@ import torch
 import lce_reference as ref
 from conftest import load_golden
 from i2i_reference import select, tie_aware_mismatches
+from recorded_calls import sweeps
 from test_lce_host import FIXTURES, TOL, check_lce_model_against_fixture, close
 
 pytestmark = pytest.mark.gpu
@@ -322,7 +323,8 @@ def test_cold_start_keeps_the_user_factors_and_maps_ids_on_the_device(hip_ops):
     names = launches(rec)
     assert np.array_equal(again, g['recs'])
     assert 'pk_spmm_csr_ex' in names and 'pk_tsmm_f64' in names and 'pk_clamp_min_f64' in names and 'pk_map_ids_i64' in names
-    assert any(n in ('pk_score_candidates_rows_f32', 'pk_score_two_phase_rows_f32') for n in names)
+    swept = sweeps(rec.calls)
+    assert swept and all(s['E'] and not s['Ep'] and not s['user_bound'] for s in swept), swept       # from rows, not packed
     assert 'pk_pack_frag_bound_f32' not in names and 'pk_row_norm_order_f64' not in names     # the image is the build's
 
 

@@ -11,6 +11,7 @@ import scipy.sparse as sps
 import torch
 
 from numpy_ops import NumpyOps
+from recorded_calls import given as _given, sweeps as _sweeps
 from test_gpu_kernels import rand_csr
 
 pytestmark = pytest.mark.gpu
@@ -169,11 +170,6 @@ def test_lists_written_in_the_callers_order_by_their_producers(hip_ops, name):
     assert np.array_equal(got, ops.to_host(scoring.recommend(ops, F, T, topk, True)))    # and again (tickets, counters)
 
 
-def _given(arg):
-    """is this recorded pointer argument (a ctypes pointer, or None) non-null?"""
-    return arg is not None and bool(getattr(arg, 'value', arg))
-
-
 def test_one_batch_pass_issues_neither_a_counter_reset_nor_a_scatter(hip_ops, pk_options):
     from polara_amd import scoring
     indptr, indices, values, V, shape, ref = pass_case('pruned')
@@ -196,35 +192,36 @@ def test_one_batch_pass_issues_neither_a_counter_reset_nor_a_scatter(hip_ops, pk
         rescorings = [args for name, _, args in rec.calls if name == 'pk_rescore_f64']
         tails = [args for name, _, args in rec.calls if name == 'pk_score_exact_list_f64']
         assert all(len(a) == 32 for a in rescorings) and all(len(a) == 17 for a in tails)
-        return names, ops.to_host(out), rescorings, tails
+        return names, ops.to_host(out), rescorings, tails, _sweeps(rec.calls)      # (the sweeps: argument counts checked there)
 
-    names, out, rescorings, tails = recorded()
+    names, out, rescorings, tails, swept = recorded()
     assert 'pk_zero_i32' not in names and 'pk_scatter_rows_i64' not in names and 'pk_exact_work_init' not in names, names
     assert 'pk_fold_q20_zero' in names and 'pk_fold_q20' not in names
     # two re-scorings and the exact tail, all three writing through out_perm: no scatter follows
     assert names.count('pk_rescore_f64') == 2 and names[-1] == 'pk_score_exact_list_f64' and len(tails) == 1, names
     assert all(_given(a[30]) for a in rescorings) and _given(tails[0][16])
     # this pass settles where its groups leave the sweep: the first re-scoring takes the open list and no norm bounds
-    assert 'pk_score_candidates_rows_settle_f32' in names, names
+    assert len(swept) == 1 and swept[0]['entry'] == 'pk_score_candidates_f32' and swept[0]['settle'], swept
     assert _given(rescorings[0][2]) and not _given(rescorings[0][31]) and not _given(rescorings[1][31])
     assert np.array_equal(out, ref)
     # ... and with the sweep's exit rule off the first re-scoring settles: everybody, with the bounds the sweep left, as
     # arguments of the same call that writes through out_perm
     pk_options('sweep_settle', 0)
-    names, out, rescorings, tails = recorded()
+    names, out, rescorings, tails, swept = recorded()
     pk_options('sweep_settle', 1)
-    assert 'pk_score_candidates_rows_bound_f32' in names and 'pk_scatter_rows_i64' not in names, names
+    assert len(swept) == 1 and swept[0]['entry'] == 'pk_score_candidates_f32', swept
+    assert not swept[0]['settle'] and swept[0]['user_bound_out'] and 'pk_scatter_rows_i64' not in names, (swept, names)
     assert names.count('pk_rescore_f64') == 2 and names[-1] == 'pk_score_exact_list_f64'
     assert all(_given(a[30]) for a in rescorings) and _given(tails[0][16])
     assert not _given(rescorings[0][2]) and _given(rescorings[0][31]) and not _given(rescorings[1][31])
     assert np.array_equal(out, ref)
     dest = torch.empty((shape[0], topk), dtype=torch.int64, device=ops.device)
-    names, out, rescorings, tails = recorded(out=dest)
+    names, out, rescorings, tails, swept = recorded(out=dest)
     assert names[-1] == 'pk_scatter_rows_i64' and 'pk_zero_i32' not in names, names
     assert len(rescorings) == 2 and not any(_given(a[30]) for a in rescorings) and not _given(tails[0][16])
     assert np.array_equal(out, ref)
     # a batched pass keeps the separate reset (its streams fork behind it) and the scatter
-    names, out, rescorings, tails = recorded(batches=2)
+    names, out, rescorings, tails, swept = recorded(batches=2)
     assert 'pk_zero_i32' in names and names[-1] == 'pk_scatter_rows_i64', names
     assert rescorings and not any(_given(a[30]) for a in rescorings) and not _given(tails[0][16])
     assert np.array_equal(out, ref)

@@ -291,3 +291,46 @@ def test_every_route_of_the_instance_keeps_the_sweeps_contract(hip_ops, monkeypa
     assert ops.sweep_settles(KC) == (KC <= 32)
     assert took_settle == [KC <= 32 and F.Kx <= 256] and (F.Kx <= 256) == (K < 256), (took_settle, KC, F.Kx)
     assert np.array_equal(ids_only[chk], want[chk]), np.flatnonzero((ids_only != want).any(axis=1) & chk)[:5]
+
+
+def test_the_users_bounds_are_stored_on_the_routes_no_pass_asks_them_of(hip_ops):
+    """`bound_out` with the settle block, and with the two-phase sweep: the arguments are independent in the two entries
+    (pk_score_candidates_f32, pk_score_two_phase_f32), but a pass of `scoring.recommend` that settles at the sweep's exit asks for
+    no bounds.  Rank 50, KC 16, top-10.  Each route gives what its neighbour without `bound_out` gives — the open users' lists
+    bit for bit, the settled users' ids, the flags, the open set — and the stored bounds are those of `ops.pack_frag_bound`.
+    The empty user (all scores tie) and the user with 5 unseen items never settle, whatever the scores."""
+    ops, K, KC, topk = hip_ops, 50, 16, 10
+    d = device_case(ops, host_case(K), K)
+    T, F = d['T'], d['F']
+    rows = (d['E'], d['w'], EXTRA_SCALE)
+
+    def bounds():
+        return torch.full((N_USERS,), -1.0, dtype=torch.float32, device=ops.device)
+
+    def settling_sweep(bound_out):
+        q = dict(topk=topk, vmax=F.vmax, item_norm=F.vnorm, out_perm=None, open_count=ops.zero_counters(1),
+                 out_idx=torch.full((N_USERS, topk), -7, dtype=torch.int64, device=ops.device),
+                 flags=torch.zeros(N_USERS, dtype=torch.int32, device=ops.device),
+                 open_list=torch.full((N_USERS,), -1, dtype=torch.int32, device=ops.device))
+        out = ops.score_candidates(F.Vp, None, N_USERS, N_ITEMS, K, T.indptr, T.indices, KC, tile_bound=F.tile_bound,
+                                   seen_tiles=d['st'], E_rows=rows, bound_out=bound_out, settle=q)
+        cs, ci = lists(ops, out, KC)
+        open_users = np.sort(ops.to_host(q['open_list'])[:int(ops.to_host(q['open_count'])[0])])
+        flags = ops.to_host(q['flags'])
+        assert np.array_equal(np.flatnonzero(flags == 0), open_users) and ((flags == 0) | (flags == 8)).all()
+        assert EMPTY_USER in open_users and FEW_USER in open_users
+        # (a settled user's candidate row is not written: only the open users' rows are compared)
+        return cs[0][open_users].view(np.int32), ci[0][open_users], ops.to_host(q['out_idx']), flags
+
+    un = bounds()
+    for got, want in zip(settling_sweep(un), settling_sweep(None)):
+        assert np.array_equal(got, want)
+    assert torch.equal(un, d['ub'])
+
+    def two_phase(bound_out):
+        return lists(ops, ops.score_two_phase(F.Vp, None, N_USERS, N_ITEMS, K, T.indptr, KC, HEAD_TILES, 3, None, F.tile_bound,
+                                              seen_tiles=d['st'], E_rows=rows, bound_out=bound_out), KC)
+
+    un = bounds()
+    assert same_bits(two_phase(un), two_phase(None))
+    assert torch.equal(un, d['ub'])

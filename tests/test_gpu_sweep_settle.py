@@ -1,4 +1,4 @@
-"""Settle at the sweep's exit (pk_score_candidates_rows_settle_f32): the rule of the first re-scoring's settle tier, applied by
+"""Settle at the sweep's exit (pk_score_candidates_f32 with a settle block): the rule of the first re-scoring's settle tier, applied by
 the candidate sweep to a group's final lists when the group leaves the sweep — settled users get their ids and flag 8 there
 and no candidate row, everybody else is appended to a device-side open list that the first re-scoring takes as its row list.
 The route (option "sweep_settle", default on) must give what the tier inside the re-scoring gives (option off): the same
@@ -23,6 +23,7 @@ import pytest
 import torch
 
 import rescore_settle_reference as R
+from recorded_calls import sweeps
 
 pytestmark = pytest.mark.gpu
 
@@ -306,13 +307,16 @@ def test_recorded_and_captured_passes_take_the_route(hip_ops, pk_options):
         ops.score_splits_override = 1
         rec = scoring.RecordedPass(ops, F, T, topk)
         names = [name for name, _, _ in rec.calls]
-        assert 'pk_score_candidates_rows_settle_f32' in names and 'pk_zero_i32' not in names, names
+        swept = sweeps(rec.calls)
+        assert len(swept) == 1 and swept[0]['entry'] == 'pk_score_candidates_f32' and swept[0]['settle'], swept
+        assert 'pk_zero_i32' not in names, names
         for _ in range(2):
             assert np.array_equal(ops.to_host(rec.replay()), ref)
         pk_options('sweep_settle', 0)
-        names = [name for name, _, _ in scoring.RecordedPass(ops, F, T, topk).calls]
+        swept = sweeps(scoring.RecordedPass(ops, F, T, topk).calls)
         pk_options('sweep_settle', 1)
-        assert 'pk_score_candidates_rows_settle_f32' not in names and 'pk_score_candidates_rows_bound_f32' in names, names
+        assert len(swept) == 1 and swept[0]['entry'] == 'pk_score_candidates_f32', swept
+        assert not swept[0]['settle'] and swept[0]['user_bound_out'] and swept[0]['E'], swept
         cap = scoring.CapturedPass(ops, F, T, topk)
         for _ in range(2):
             assert np.array_equal(ops.to_host(cap.replay()), ref)
