@@ -757,6 +757,30 @@ int pk_trmm_f64(void *stream, int32_t trans, int64_t n, int32_t nc, const double
 int pk_trsm_f64(void *stream, int64_t n, int32_t r, const double *L_dev, int64_t ld, double *B_dev, int64_t ldb);
 
 /* ------------------------------------------------------------------------------------------
+ * EASE (Steck 2019): B = I - P diag(1 / diag P), P = (X^T X + lambda I)^-1, through the Cholesky image above:
+ * pk_i2i_build_f64 writes X^T X (diagonal 0) into the image (ldc = ld), pk_ease_diag_f64 its diagonal, pk_chol_f64
+ * factors it, pk_trtri_f64 inverts the factor in place and pk_ease_weights_f64 forms the scoring image of B.
+ * Everything is fp64 with a fixed summation order: the results are the same bits from run to run.
+ * ------------------------------------------------------------------------------------------ */
+/* K[j][j] = sum_u x_uj^2 + lam for j < n_items, from the CSC image of X (t_indptr int64 [n_items + 1], values of
+ * val_kind): 16 lanes per item, lane l sums the entries l, l + 16, ... of the column in storage order, the 16 partial sums
+ * are added as a fixed tree. */
+int pk_ease_diag_f64(void *stream, int64_t n_items, const int64_t *t_indptr_dev, const void *t_values_dev, int val_kind,
+                     double lam, double *K_dev, int64_t ld);
+/* Scratch of pk_trtri_f64 (host function): the panel product of one block column, one partial block per chunk of 32
+ * tiles of a tile row. */
+int64_t pk_trtri_work_bytes(int64_t n);
+/* In place W = L^-1 of the lower factor pk_chol_f64 left in the image (padding: the identity, so the result is
+ * diag(W, I)); the strict upper triangle is not touched.  Block columns are taken last to first; 1 + 2 (n / 64 - 1)
+ * launches.  work >= pk_trtri_work_bytes(n). */
+int pk_trtri_f64(void *stream, int64_t n, double *L_dev, int64_t ld, void *work_dev);
+/* From W = L^-1 (the image of pk_trtri_f64): d_out[j] = P_jj = sum_k W_kj^2 (j < n), and the scoring image
+ * B [n x ldb], ldb >= n: B_ij = -P_ij / d_j with P = W^T W summed tile by tile and never stored, B_jj = 0 and the
+ * columns [n, ldb) 0. */
+int pk_ease_weights_f64(void *stream, int64_t n, const double *W_dev, int64_t ld, double *d_out_dev, double *B_dev,
+                        int64_t ldb);
+
+/* ------------------------------------------------------------------------------------------
  * Local Collective Embeddings (csrc/lce.hip).  Replace the NumPy element-wise updates and traces of
  * `local_collective_embeddings` (lib/optimize.py:347-379).  The factors are tall row-major fp64 blocks, the H factors
  * transposed ([labels x k], [users x k]), so the three multiplicative updates are one form:

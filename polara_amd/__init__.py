@@ -8,6 +8,7 @@
     from polara_amd import ProbabilisticMF                          # PMF trained by a blocked SGD sweep
     from polara_amd import ImplicitALS                              # iALS / WRMF: alternating least squares, exact per-row solves
     from polara_amd import ImplicitBPR                              # BPR-MF: pairwise ranking by a blocked triplet sweep
+    from polara_amd import EASEModel                                # EASE: closed-form item weights on a device SPD inverse
     from polara_amd import SVDModelSampled, RandomSampleArrayData   # sampled-negatives evaluation (1 holdout + n unseen items)
     from polara_amd import ArrayData, ShardedArrayData              # NumPy / on-disk data providers
 
@@ -98,6 +99,7 @@ _EXPORTS = {
     'ProbabilisticMF': 'pmf',
     'ImplicitALS': 'ials',
     'ImplicitBPR': 'bpr',
+    'EASEModel': 'ease',
     'SimilarityAggregation': 'simagg', 'SimilarityAggregationItemColdStart': 'simagg',
     'cosine_similarity': 'similarity', 'cosine_tfidf_similarity': 'similarity', 'jaccard_similarity': 'similarity',
     'jaccard_similarity_weighted': 'similarity', 'cross_similarity': 'similarity', 'combine_similarity': 'similarity',

@@ -158,6 +158,10 @@ PROTOTYPES = {
     'pk_chol_f64': (C.c_int, [_vp, _i64, _vp, _i64, _vp]),
     'pk_trmm_f64': (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     'pk_trsm_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64]),
+    'pk_ease_diag_f64': (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _f64, _vp, _i64]),
+    'pk_trtri_work_bytes': (_i64, [_i64]),
+    'pk_trtri_f64': (C.c_int, [_vp, _i64, _vp, _i64, _vp]),
+    'pk_ease_weights_f64': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64]),
     'pk_lce_fused_max_rank': (_i32, []),
     'pk_lce_update_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _vp, _i64, _f64, _f64, _f64, _vp]),
     'pk_lce_update_ew_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _f64, _vp]),

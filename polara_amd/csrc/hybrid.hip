@@ -13,7 +13,9 @@
 //     (each tile once, the next one fetched into registers while the current one runs on the matrix cores) and writes
 //     a partial block; a second kernel adds the partials of a row in a fixed order;
 //   * pk_trsm_f64: X = L^-T B, blocked back substitution: per block row (last to first) the diagonal block is solved
-//     (one lane per column), then the blocks above it are updated on the matrix cores.
+//     (one lane per column), then the blocks above it are updated on the matrix cores;
+//   * EASE on the same image (the section at the end): the Gram diagonal, pk_trtri_f64 (L^-1 in place) and
+//     pk_ease_weights_f64 (the scaled weights from L^-T L^-1, never stored).
 //
 // MFMA layout (MI355X guide, the same map as dense.hip's gram_kernel): D[16 x 16] += P[16 x 4] Q[4 x 16] with lane l
 // holding P[l & 15][l >> 4], Q[l >> 4][l & 15] and D[(l >> 4) + 4 r][l & 15] in register r.
@@ -439,6 +441,278 @@ extern "C" int pk_trsm_f64(void *stream, int64_t n, int32_t r, const double *L_d
         hipLaunchKernelGGL(hyb_trsm_update_kernel, dim3((unsigned)J, cchunks), dim3(256), 0, st, (int)r, L_dev, ld, J, B_dev, ldb);
         PK_CHECK_LAUNCH("hyb_trsm_update_kernel");
     }
+    return PK_OK;
+}
+
+// ---- EASE: Gram diagonal, triangular inverse, weights ------------------------------------------------------------------
+// B = I - P diag(1 / diag P), P = (X^T X + lambda I)^-1 = W^T W with W = L^-1.
+//   * pk_ease_diag_f64: the diagonal pk_i2i_build_f64 leaves at 0, from the CSC image of X;
+//   * pk_trtri_f64: W in place, block columns last to first (LAPACK's dtrtri('L') order).  All diagonal blocks are
+//     inverted first (they depend on nothing else: one workgroup each, one lane per column of the inverse).  At block
+//     column J the triangle below and to the right holds W already and the panel L[J + 1 :, J] is still L's:
+//         W[J + 1 :, J] = -(W[J + 1 :, J + 1 :] L[J + 1 :, J]) W_JJ
+//     the first product runs as tasks of up to 32 tiles of a tile row, each writing a partial block into the work buffer
+//     (the panel is read by every task and must not change under them); the second kernel adds the partials of a tile
+//     in chunk order, multiplies by the inverted diagonal block and writes the panel;
+//   * pk_ease_weights_f64: d_j = sum_k W_kj^2, then one workgroup per tile pair (I, J), I >= J, sums W_KI^T W_KJ over
+//     K >= I and writes both mirrored tiles of B, scaled, through LDS (both with unit-stride rows).
+#define PK_EASE_GROUP 16      // lanes per item of the Gram diagonal
+
+__device__ __forceinline__ double hyb_val(const void *v, int kind, int64_t p) {
+    return kind == PK_VAL_F32 ? (double)static_cast<const float *>(v)[p] : static_cast<const double *>(v)[p];
+}
+
+__global__ __launch_bounds__(256) void ease_diag_kernel(int64_t n, const int64_t *__restrict__ t_indptr,
+                                                        const void *__restrict__ t_values, int kind, double lam,
+                                                        double *__restrict__ K, int64_t ld) {
+    const int64_t j = (int64_t)blockIdx.x * (256 / PK_EASE_GROUP) + threadIdx.x / PK_EASE_GROUP;
+    const int l = threadIdx.x % PK_EASE_GROUP;
+    double s = 0.0;
+    if (j < n)
+        for (int64_t p = t_indptr[j] + l; p < t_indptr[j + 1]; p += PK_EASE_GROUP) {
+            const double x = hyb_val(t_values, kind, p);
+            s += x * x;
+        }
+#pragma unroll
+    for (int o = PK_EASE_GROUP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, PK_EASE_GROUP);      // a + b == b + a: every lane agrees
+    if (j < n && l == 0) K[j * ld + j] = s + lam;
+}
+
+extern "C" int pk_ease_diag_f64(void *stream, int64_t n_items, const int64_t *t_indptr_dev, const void *t_values_dev,
+                                int val_kind, double lam, double *K_dev, int64_t ld) {
+    PK_REQUIRE(n_items >= 1 && ld >= n_items, "pk_ease_diag_f64: bad sizes (n_items = %lld, ld = %lld)", (long long)n_items,
+               (long long)ld);
+    PK_REQUIRE(t_indptr_dev != nullptr && K_dev != nullptr && (val_kind == PK_VAL_F32 || val_kind == PK_VAL_F64),
+               "pk_ease_diag_f64: null pointer or bad val_kind");
+    hipLaunchKernelGGL(ease_diag_kernel, dim3((unsigned)pk_ceil_div(n_items, 256 / PK_EASE_GROUP)), dim3(256), 0,
+                       pk_stream(stream), n_items, t_indptr_dev, t_values_dev, val_kind, lam, K_dev, ld);
+    PK_CHECK_LAUNCH("ease_diag_kernel");
+    return PK_OK;
+}
+
+// diagonal block b: L_bb x = e_j per column j of the inverse (one lane per column, forward substitution in LDS)
+__global__ __launch_bounds__(256) void hyb_trtri_diag_kernel(double *__restrict__ A, int64_t ld) {
+    __shared__ double s[PK_HYB_NB][PK_HYB_S];
+    __shared__ double x[PK_HYB_NB][PK_HYB_S];
+    const int64_t k = (int64_t)blockIdx.x * PK_HYB_NB;
+    TileRegs r;
+    tile_fetch(r, A, ld, k, k);
+    tile_store(s, r, true);
+    __syncthreads();
+    const int j = threadIdx.x;
+    if (j >= PK_HYB_NB) return;
+    // x_i = (e_j[i] - sum over j <= q < i of L_iq x_q) / L_ii, q ascending; the column lives in LDS (x[q][j]: its own bank)
+    x[j][j] = 1.0 / s[j][j];
+    for (int i = j + 1; i < PK_HYB_NB; ++i) {
+        double v = 0.0;
+        for (int q = j; q < i; ++q) v -= s[i][q] * x[q][j];
+        x[i][j] = v / s[i][i];
+    }
+    for (int i = j; i < PK_HYB_NB; ++i) A[(k + i) * ld + k + j] = x[i][j];
+}
+
+// tile row s, chunk c of the panel product below diagonal block J: the partial sum over t in [32 c, min(32 c + 32, s + 1)) of
+// W[off + 64 s, off + 64 t] L[off + 64 t, 64 J], off = 64 (J + 1), both tiles of the next step fetched into registers while
+// the current pair is on the matrix cores
+__global__ __launch_bounds__(256) void hyb_trtri_prod_kernel(const double *__restrict__ A, int64_t ld, int64_t J, int64_t nbt,
+                                                             double *__restrict__ work) {
+    __shared__ double sW[PK_HYB_NB][PK_HYB_S];
+    __shared__ double sX[PK_HYB_NB][PK_HYB_S];
+    const int64_t s = blockIdx.x, c = blockIdx.y;
+    const int64_t t0 = c * PK_HYB_CHUNK, t1 = hyb_min(t0 + PK_HYB_CHUNK, s + 1);
+    if (t0 >= t1) return;
+    const int64_t col0 = J * PK_HYB_NB, off = col0 + PK_HYB_NB, row0 = off + s * PK_HYB_NB;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    f64x4 acc[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[b] = f64x4{0.0, 0.0, 0.0, 0.0};
+    TileRegs rw, rx;
+    tile_fetch(rw, A, ld, row0, off + t0 * PK_HYB_NB);
+    tile_fetch(rx, A, ld, off + t0 * PK_HYB_NB, col0);
+    for (int64_t t = t0; t < t1; ++t) {
+        tile_store(sW, rw, t == s);
+        tile_store(sX, rx, false);
+        __syncthreads();
+        if (t + 1 < t1) {
+            tile_fetch(rw, A, ld, row0, off + (t + 1) * PK_HYB_NB);
+            tile_fetch(rx, A, ld, off + (t + 1) * PK_HYB_NB, col0);
+        }
+#pragma unroll
+        for (int k0 = 0; k0 < PK_HYB_NB; k0 += 4) {
+            const double a = sW[16 * wave + (lane & 15)][k0 + (lane >> 4)];
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sX[k0 + (lane >> 4)][16 * b + (lane & 15)], acc[b], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    double *w = work + (c * nbt + s) * PK_HYB_NB * PK_HYB_NB;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) w[(16 * wave + (lane >> 4) + 4 * q) * PK_HYB_NB + 16 * b + (lane & 15)] = acc[b][q];
+}
+
+// tile s of the panel below diagonal block J (row0 = 64 (J + 1 + s), col0 = 64 J): -(sum of its partials) W_JJ
+__global__ __launch_bounds__(256) void hyb_trtri_panel_kernel(double *__restrict__ A, int64_t ld, int64_t J, int64_t nbt,
+                                                              const double *__restrict__ work) {
+    __shared__ double sY[PK_HYB_NB][PK_HYB_S];
+    __shared__ double sD[PK_HYB_NB][PK_HYB_S];
+    const int64_t s = blockIdx.x, col0 = J * PK_HYB_NB, row0 = col0 + PK_HYB_NB * (1 + s);
+    TileRegs r;
+    tile_fetch(r, A, ld, col0, col0);
+    tile_store(sD, r, true);
+    const int64_t cnt = (s + PK_HYB_CHUNK) / PK_HYB_CHUNK, cstride = nbt * PK_HYB_NB * PK_HYB_NB;
+    const double *w = work + s * PK_HYB_NB * PK_HYB_NB;
+    for (int e = threadIdx.x; e < PK_HYB_NB * PK_HYB_NB; e += 256) {
+        double v = w[e];
+        for (int64_t c = 1; c < cnt; ++c) v += w[c * cstride + e];
+        sY[e >> 6][e & 63] = v;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    f64x4 acc[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[b] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k0 = 0; k0 < PK_HYB_NB; k0 += 4) {
+        const double a = sY[16 * wave + (lane & 15)][k0 + (lane >> 4)];
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sD[k0 + (lane >> 4)][16 * b + (lane & 15)], acc[b], 0, 0, 0);
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int j = 16 * b + (lane & 15);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = 16 * wave + (lane >> 4) + 4 * q;
+            A[(row0 + i) * ld + col0 + j] = -acc[b][q];
+        }
+    }
+}
+
+static int64_t trtri_chunks(int64_t n) {
+    const int64_t below = pk_ceil_div(n, PK_HYB_NB) - 1;            // tile rows of the longest panel
+    return below > 0 ? pk_ceil_div(below, PK_HYB_CHUNK) : 0;
+}
+extern "C" int64_t pk_trtri_work_bytes(int64_t n) {
+    if (n < 1) return 0;
+    return trtri_chunks(n) * (pk_hybrid_ld(n) - PK_HYB_NB) * PK_HYB_NB * (int64_t)sizeof(double);
+}
+
+extern "C" int pk_trtri_f64(void *stream, int64_t n, double *L_dev, int64_t ld, void *work_dev) {
+    PK_REQUIRE(n >= 1 && ld % PK_HYB_NB == 0 && ld >= pk_hybrid_ld(n), "pk_trtri_f64: bad sizes (n = %lld, ld = %lld)",
+               (long long)n, (long long)ld);
+    PK_REQUIRE(L_dev != nullptr && aligned16(L_dev), "pk_trtri_f64: null or unaligned pointer");
+    const int64_t nb = pk_hybrid_ld(n) / PK_HYB_NB;
+    PK_REQUIRE(nb == 1 || work_dev != nullptr, "pk_trtri_f64: work buffer required (pk_trtri_work_bytes)");
+    hipStream_t st = pk_stream(stream);
+    double *work = static_cast<double *>(work_dev);
+    hipLaunchKernelGGL(hyb_trtri_diag_kernel, dim3((unsigned)nb), dim3(256), 0, st, L_dev, ld);
+    PK_CHECK_LAUNCH("hyb_trtri_diag_kernel");
+    for (int64_t J = nb - 2; J >= 0; --J) {
+        const int64_t nbt = nb - J - 1, nch = pk_ceil_div(nbt, PK_HYB_CHUNK);
+        // Y = W[off :, off :] L[off :, J]: chunk c of tile row s at work[(c nbt + s) 64 + i][j]
+        hipLaunchKernelGGL(hyb_trtri_prod_kernel, dim3((unsigned)nbt, (unsigned)nch), dim3(256), 0, st, L_dev, ld, J, nbt, work);
+        PK_CHECK_LAUNCH("hyb_trtri_prod_kernel");
+        hipLaunchKernelGGL(hyb_trtri_panel_kernel, dim3((unsigned)nbt), dim3(256), 0, st, L_dev, ld, J, nbt, work);
+        PK_CHECK_LAUNCH("hyb_trtri_panel_kernel");
+    }
+    return PK_OK;
+}
+
+// d[j] = sum_k W[k][j]^2 over the rows of tile row b and below: four row phases per column, added in a fixed order
+__global__ __launch_bounds__(256) void ease_colsq_kernel(int64_t n, int64_t npad, const double *__restrict__ W, int64_t ld,
+                                                         double *__restrict__ d) {
+    __shared__ double part[4][PK_HYB_NB];
+    const int c = threadIdx.x & 63, p = threadIdx.x >> 6;
+    const int64_t j = (int64_t)blockIdx.x * PK_HYB_NB + c;
+    double s = 0.0;
+#pragma unroll 4
+    for (int64_t k = (int64_t)blockIdx.x * PK_HYB_NB + p; k < npad; k += 4) {
+        const double w = W[k * ld + j];
+        s = fma(w, w, s);
+    }
+    part[p][c] = s;
+    __syncthreads();
+    if (p == 0 && j < n) d[j] = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
+}
+
+// tile pair x = (I, J), I >= J (I ascending with x: the long sums start first): P_IJ = sum over K >= I of W_KI^T W_KJ,
+// then B[I tile][J tile] = -P / d_J (columns) and B[J tile][I tile] = -P^T / d_I
+__global__ __launch_bounds__(256) void ease_weights_kernel(int64_t n, int64_t nb, const double *__restrict__ W, int64_t ld,
+                                                           const double *__restrict__ d, double *__restrict__ B, int64_t ldb) {
+    __shared__ double sA[PK_HYB_NB][PK_HYB_S];
+    __shared__ double sB[PK_HYB_NB][PK_HYB_S];
+    __shared__ double sdi[PK_HYB_NB], sdj[PK_HYB_NB];
+    const int64_t x = blockIdx.x;
+    int64_t I = (int64_t)((sqrt(8.0 * (double)x + 1.0) - 1.0) * 0.5);
+    while ((I + 1) * (I + 2) / 2 <= x) ++I;
+    while (I * (I + 1) / 2 > x) --I;
+    const int64_t J = x - I * (I + 1) / 2;
+    const int64_t i0 = I * PK_HYB_NB, j0 = J * PK_HYB_NB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    f64x4 acc[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[b] = f64x4{0.0, 0.0, 0.0, 0.0};
+    TileRegs ra, rb;
+    tile_fetch(ra, W, ld, i0, i0);
+    tile_fetch(rb, W, ld, i0, j0);
+    for (int64_t K = I; K < nb; ++K) {
+        tile_store(sA, ra, K == I);
+        tile_store(sB, rb, K == J);
+        __syncthreads();
+        if (K + 1 < nb) {
+            tile_fetch(ra, W, ld, (K + 1) * PK_HYB_NB, i0);
+            tile_fetch(rb, W, ld, (K + 1) * PK_HYB_NB, j0);
+        }
+#pragma unroll
+        for (int k0 = 0; k0 < PK_HYB_NB; k0 += 4) {
+            const double a = sA[k0 + (lane >> 4)][16 * wave + (lane & 15)];
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sB[k0 + (lane >> 4)][16 * b + (lane & 15)], acc[b], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    // P tile into sA (every wave is past its last read of it), the diagonal entries of both tiles next to it
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) sA[16 * wave + (lane >> 4) + 4 * q][16 * b + (lane & 15)] = acc[b][q];
+    if (tid < PK_HYB_NB) {
+        sdi[tid] = i0 + tid < n ? d[i0 + tid] : 1.0;
+        sdj[tid] = j0 + tid < n ? d[j0 + tid] : 1.0;
+    }
+    __syncthreads();
+    for (int e = tid; e < PK_HYB_NB * PK_HYB_NB; e += 256) {
+        const int r = e >> 6, c = e & 63;
+        const int64_t gi = i0 + r, gj = j0 + c;                   // B[I tile][J tile]: row r, column c = P[r][c]
+        if (gi < n && gj < n && (I != J || c <= r)) B[gi * ldb + gj] = (gi == gj) ? 0.0 : -sA[r][c] / sdj[c];
+        const int64_t hi = j0 + r, hj = i0 + c;                   // B[J tile][I tile]: row r, column c = P[c][r]
+        if (hi < n && hj < n && (I != J || c > r)) B[hi * ldb + hj] = -sA[c][r] / sdi[c];
+    }
+}
+
+extern "C" int pk_ease_weights_f64(void *stream, int64_t n, const double *W_dev, int64_t ld, double *d_out_dev, double *B_dev,
+                                   int64_t ldb) {
+    PK_REQUIRE(n >= 1 && ld % PK_HYB_NB == 0 && ld >= pk_hybrid_ld(n) && ldb >= n,
+               "pk_ease_weights_f64: bad sizes (n = %lld, ld = %lld, ldb = %lld)", (long long)n, (long long)ld, (long long)ldb);
+    PK_REQUIRE(W_dev != nullptr && d_out_dev != nullptr && B_dev != nullptr && aligned16(W_dev),
+               "pk_ease_weights_f64: null or unaligned pointer");
+    const int64_t npad = pk_hybrid_ld(n), nb = npad / PK_HYB_NB, pairs = nb * (nb + 1) / 2;
+    PK_REQUIRE(pairs <= 0x7fffffff, "pk_ease_weights_f64: catalogue too large for the grid");
+    hipStream_t st = pk_stream(stream);
+    if (ldb > n && hipMemset2DAsync(B_dev + n, (size_t)ldb * sizeof(double), 0, (size_t)(ldb - n) * sizeof(double), (size_t)n,
+                                    st) != hipSuccess) {
+        pk_set_error("pk_ease_weights_f64: memset failed");
+        return PK_E_LAUNCH;
+    }
+    hipLaunchKernelGGL(ease_colsq_kernel, dim3((unsigned)nb), dim3(256), 0, st, n, npad, W_dev, ld, d_out_dev);
+    PK_CHECK_LAUNCH("ease_colsq_kernel");
+    hipLaunchKernelGGL(ease_weights_kernel, dim3((unsigned)pairs), dim3(256), 0, st, n, nb, W_dev, ld, d_out_dev, B_dev, ldb);
+    PK_CHECK_LAUNCH("ease_weights_kernel");
     return PK_OK;
 }
 

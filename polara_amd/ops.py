@@ -1894,6 +1894,47 @@ class HipOps:
             _lib.check(self.lib.pk_trsm_f64(self.stream(), n, r, _ptr(L), L.stride(0), _ptr(W), W.stride(0)), 'pk_trsm_f64')
         return W[:n]
 
+    # ---- EASE: closed-form item weights on the Cholesky image (csrc/hybrid.hip) ------------------------------------------
+    def ease_gram(self, A, lam):
+        """The Cholesky image [ld x ld] of K = A^T A + lam I for the device CSR A: pk_i2i_build_f64 writes the rows of
+        A^T A (diagonal 0) straight into the image, pk_ease_diag_f64 the diagonal from A's CSC image.  Raises MemoryError
+        before allocating when this image and the weights image together would take more than half of the free device
+        memory (ease.check_build_memory)."""
+        from . import ease
+        n_users, n_items = (int(x) for x in A.shape)
+        ease.check_build_memory(n_items, self.free_bytes())
+        ld = ease.chol_leading_dim(n_items)
+        T = A.T
+        K = torch.empty(ld, ld, dtype=torch.float64, device=self.device)
+        with self._timed('ease_gram', (n_users, n_items, A.nnz)):
+            _lib.check(self.lib.pk_i2i_build_f64(self.stream(), n_users, n_items, _ptr(A.indptr), _ptr(A.indices),
+                                                 _ptr(A.values), A.val_kind, _ptr(T.indptr), _ptr(T.indices),
+                                                 _ptr(T.values), _ptr(K), ld), 'pk_i2i_build_f64')
+            _lib.check(self.lib.pk_ease_diag_f64(self.stream(), n_items, _ptr(T.indptr), _ptr(T.values), T.val_kind,
+                                                 float(lam), _ptr(K), ld), 'pk_ease_diag_f64')
+        return K
+
+    def trtri(self, img, n):
+        """In place W = L^-1 of the lower factor `chol` left in the image (pk_trtri_f64); the padding stays the identity."""
+        n = int(n)
+        work = self._work(self.lib.pk_trtri_work_bytes(n))
+        with self._timed('trtri', (n,)):
+            _lib.check(self.lib.pk_trtri_f64(self.stream(), n, _ptr(img), img.stride(0), _ptr(work)), 'pk_trtri_f64')
+        return img
+
+    def ease_weights(self, img, n):
+        """(B, d) from the image of `trtri`: the scoring image B [n x i2i.leading_dim(n)] of the EASE weights (diagonal and
+        pad columns 0) and d = diag (K^-1) [n], both fp64 on the device (pk_ease_weights_f64)."""
+        from . import i2i
+        n = int(n)
+        ldb = i2i.leading_dim(n)
+        B = torch.empty(n, ldb, dtype=torch.float64, device=self.device)
+        d = torch.empty(n, dtype=torch.float64, device=self.device)
+        with self._timed('ease_weights', (n,)):
+            _lib.check(self.lib.pk_ease_weights_f64(self.stream(), n, _ptr(img), img.stride(0), _ptr(d), _ptr(B), ldb),
+                       'pk_ease_weights_f64')
+        return B, d
+
     # ---- item cold start -----------------------------------------------------------------------------------------
     def coldstart_queries(self, F, W, G):
         """E = (F W) G for the cold items of a DeviceCSR over the training labels, fp64: the SpMM and the tall-skinny product
