@@ -45,6 +45,7 @@ int pk_version(void);
  *   "score_boot_tiles"     tiles of the sweep's threshold bootstrap (default 16; 0 = off)
  *   "score_head_tiles"     head of the two-phase sweep whatever the user count (default: pk_score_two_phase_plan's rule; 0 = off)
  *   "score_phase2_splits"  item splits of its second phase
+ *   "slim_r_global"        pk_slim_solve_f64 keeps the residual rows in HBM at every n (default 0: only beyond pk_slim_lds_items())
  * unset != 0 returns the option to its default.  Unknown names: PK_E_INVALID. */
 int pk_set_option(const char *name, int32_t value, int32_t unset);
 /* hipMemcpyAsync device -> host on `stream` (pinned destination: asynchronous): the hand-over of a pass's lists as one more
@@ -779,6 +780,54 @@ int pk_trtri_f64(void *stream, int64_t n, double *L_dev, int64_t ld, void *work_
  * columns [n, ldb) 0. */
 int pk_ease_weights_f64(void *stream, int64_t n, const double *W_dev, int64_t ld, double *d_out_dev, double *B_dev,
                         int64_t ldb);
+
+/* ------------------------------------------------------------------------------------------
+ * SLIM (Ning & Karypis, ICDM 2011; csrc/slim.hip): the sparse item x item weights W, column by column,
+ *     w_j = argmin 1/2 |x_j - X w|^2 + l1 |w|_1 + l2 / 2 |w|^2   subject to w_j[j] = 0 and, with `positive`, w >= 0,
+ * by elastic-net coordinate descent over the dense Gram image G = X^T X [n x ldg] WITH its diagonal (pk_i2i_build_f64 +
+ * pk_ease_diag_f64 with lam = 0).  The arithmetic is fixed, so that the result does not depend on how it is parallelised
+ * (tests/slim_reference.py restates it in NumPy and the device's bits are compared with that).  Everything is fp64 and
+ * every product, sum and quotient is rounded on its own (no contraction).  Per target column j, reading row k of the image,
+ * G[k][i], wherever a column of G is meant:
+ *     w = 0;  r[i] = G[j][i] for all i
+ *     for sweep = 1 .. max_sweeps:
+ *         dmax = 0; wmax = 0
+ *         for k = 0 .. n - 1 in ascending order, k != j:
+ *             den = G[k][k] + l2;  if not (den > 0): continue
+ *             old = w[k];  rho = r[k] + G[k][k] * old
+ *             positive:      t = rho - l1;    new = t > 0 ? t / den : 0
+ *             not positive:  t = |rho| - l1;  new = t > 0 ? copysign(t / den, rho) : 0
+ *             d = new - old
+ *             if d != 0:  r[i] = r[i] - d * G[k][i] for ALL i (k and j included);  w[k] = new
+ *             dmax = max(dmax, |d|);  wmax = max(wmax, |new|)
+ *         if wmax == 0 or dmax <= tol * wmax: stop
+ *     outputs: w, the number of sweeps run
+ * A coordinate's update reads one element of r and no reduction, the update of r is element-wise and both maxima are
+ * order-free: any implementation that visits the CHANGING coordinates in ascending order produces these bits.  The kernel
+ * evaluates 1024 coordinates at once (between two changes r is constant), applies the lowest changing one and continues
+ * behind it.
+ * ------------------------------------------------------------------------------------------ */
+/* Limits and planning (host functions): the largest n of pk_slim_solve_f64 (65 536), the largest n whose residual row r
+ * lives in LDS (19 456; beyond it, or with pk_set_option("slim_r_global", 1), r lives in one scratch row per workgroup), the
+ * default number of columns of a batch (min(n, 1024)) and the scratch of a solve of nc columns: the diagonal of G
+ * (n doubles rounded up to 256 bytes) and, with r in HBM, nc rows of n doubles. */
+int64_t pk_slim_max_items(void);
+int64_t pk_slim_lds_items(void);
+int64_t pk_slim_batch_columns(int64_t n);
+int64_t pk_slim_work_bytes(int64_t n, int64_t nc);
+/* The target columns [j0, j0 + nc): row c of Wt_block [nc x ldw] (ldw >= n) becomes w_(j0 + c), i.e. row j0 + c of W^T, its
+ * columns [n, ldw) exactly 0; sweeps[c] (int32) the sweeps run.  One workgroup per column.  The result of a column does not
+ * depend on the batch it is solved in.  work >= pk_slim_work_bytes(n, nc). */
+int pk_slim_solve_f64(void *stream, int64_t n, const double *G_dev, int64_t ldg, int64_t j0, int64_t nc, double l1, double l2,
+                      double tol, int32_t max_sweeps, int32_t positive, double *Wt_block_dev, int64_t ldw, int32_t *sweeps_dev,
+                      void *work_dev);
+/* A block [nc x ldw] of rows of W^T as CSR rows: an entry is stored when it is != 0, in ascending index order.
+ * pk_slim_csr_count: indptr [nc + 1] (int64, indptr[0] = 0) of the block alone; work >= 8 nc bytes.  pk_slim_csr_fill:
+ * indices (int32) and values (fp64) [nnz = indptr[nc]] of the same, unchanged block. */
+int pk_slim_csr_count(void *stream, int64_t nc, int64_t n, const double *Wt_block_dev, int64_t ldw, int64_t *indptr_dev,
+                      void *work_dev);
+int pk_slim_csr_fill(void *stream, int64_t nc, int64_t n, const double *Wt_block_dev, int64_t ldw, const int64_t *indptr_dev,
+                     int64_t nnz, int32_t *indices_dev, double *values_dev);
 
 /* ------------------------------------------------------------------------------------------
  * Local Collective Embeddings (csrc/lce.hip).  Replace the NumPy element-wise updates and traces of

@@ -9,6 +9,7 @@
     from polara_amd import ImplicitALS                              # iALS / WRMF: alternating least squares, exact per-row solves
     from polara_amd import ImplicitBPR                              # BPR-MF: pairwise ranking by a blocked triplet sweep
     from polara_amd import EASEModel                                # EASE: closed-form item weights on a device SPD inverse
+    from polara_amd import SLIMModel                                # SLIM: sparse item weights by device coordinate descent
     from polara_amd import SVDModelSampled, RandomSampleArrayData   # sampled-negatives evaluation (1 holdout + n unseen items)
     from polara_amd import ArrayData, ShardedArrayData              # NumPy / on-disk data providers
 
@@ -100,6 +101,7 @@ _EXPORTS = {
     'ImplicitALS': 'ials',
     'ImplicitBPR': 'bpr',
     'EASEModel': 'ease',
+    'SLIMModel': 'slim',
     'SimilarityAggregation': 'simagg', 'SimilarityAggregationItemColdStart': 'simagg',
     'cosine_similarity': 'similarity', 'cosine_tfidf_similarity': 'similarity', 'jaccard_similarity': 'similarity',
     'jaccard_similarity_weighted': 'similarity', 'cross_similarity': 'similarity', 'combine_similarity': 'similarity',

@@ -162,6 +162,13 @@ PROTOTYPES = {
     'pk_trtri_work_bytes': (_i64, [_i64]),
     'pk_trtri_f64': (C.c_int, [_vp, _i64, _vp, _i64, _vp]),
     'pk_ease_weights_f64': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64]),
+    'pk_slim_max_items': (_i64, []),
+    'pk_slim_lds_items': (_i64, []),
+    'pk_slim_batch_columns': (_i64, [_i64]),
+    'pk_slim_work_bytes': (_i64, [_i64, _i64]),
+    'pk_slim_solve_f64': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _f64, _f64, _f64, _i32, _i32, _vp, _i64, _vp, _vp]),
+    'pk_slim_csr_count': (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp]),
+    'pk_slim_csr_fill': (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     'pk_lce_fused_max_rank': (_i32, []),
     'pk_lce_update_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _vp, _i64, _f64, _f64, _f64, _vp]),
     'pk_lce_update_ew_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _f64, _vp]),

@@ -18,7 +18,7 @@ extern "C" const char *pk_last_error(void) { return g_err; }
 namespace {
 struct Option { const char *name; std::atomic<int> value; std::atomic<bool> set; };
 Option g_options[] = {{"score_boot_tiles", {0}, {false}}, {"score_head_tiles", {0}, {false}}, {"score_phase2_splits", {0}, {false}},
-                      {"rescore_settle", {0}, {false}}, {"sweep_settle", {0}, {false}}};
+                      {"rescore_settle", {0}, {false}}, {"sweep_settle", {0}, {false}}, {"slim_r_global", {0}, {false}}};
 }
 int pk_option(const char *name, int dflt) {
     for (auto &o : g_options)
@@ -104,12 +104,13 @@ hipError_t pk_tu_load_rescore();
 hipError_t pk_tu_load_sampled();
 hipError_t pk_tu_load_score();
 hipError_t pk_tu_load_simagg();
+hipError_t pk_tu_load_slim();
 hipError_t pk_tu_load_spgemm();
 hipError_t pk_tu_load_spmm();
 hipError_t pk_tu_load_ttm();
 
 extern "C" int pk_warm_up(void) {
-    hipError_t (*const loaders[])() = {pk_tu_load_bpr, pk_tu_load_dense, pk_tu_load_driver, pk_tu_load_eigh, pk_tu_load_eigh_top, pk_tu_load_evalmetrics, pk_tu_load_foldq, pk_tu_load_hybrid, pk_tu_load_i2i, pk_tu_load_ials, pk_tu_load_ingest, pk_tu_load_kpmf, pk_tu_load_lce, pk_tu_load_pmf, pk_tu_load_rescore, pk_tu_load_sampled, pk_tu_load_score, pk_tu_load_simagg, pk_tu_load_spgemm, pk_tu_load_spmm, pk_tu_load_ttm};
+    hipError_t (*const loaders[])() = {pk_tu_load_bpr, pk_tu_load_dense, pk_tu_load_driver, pk_tu_load_eigh, pk_tu_load_eigh_top, pk_tu_load_evalmetrics, pk_tu_load_foldq, pk_tu_load_hybrid, pk_tu_load_i2i, pk_tu_load_ials, pk_tu_load_ingest, pk_tu_load_kpmf, pk_tu_load_lce, pk_tu_load_pmf, pk_tu_load_rescore, pk_tu_load_sampled, pk_tu_load_score, pk_tu_load_simagg, pk_tu_load_slim, pk_tu_load_spgemm, pk_tu_load_spmm, pk_tu_load_ttm};
     for (auto f : loaders) {
         const hipError_t e = f();
         if (e != hipSuccess) {

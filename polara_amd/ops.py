@@ -1935,6 +1935,67 @@ class HipOps:
                        'pk_ease_weights_f64')
         return B, d
 
+    # ---- SLIM: sparse item weights by coordinate descent over the Gram image (csrc/slim.hip) ----------------------------
+    def slim_gram(self, A, column_batch=None):
+        """The Gram image [n_items x slim.gram_leading_dim(n_items)] of G = A^T A WITH its diagonal for the device CSR A
+        (pk_i2i_build_f64, then pk_ease_diag_f64 with lam = 0); the pad columns are 0.  Raises ValueError beyond
+        pk_slim_max_items() and MemoryError before allocating when the image and one batch block of `column_batch` columns
+        (default: the default rule) would take more than half of the free device memory (slim.check_build_memory)."""
+        from . import slim
+        n_users, n_items = (int(x) for x in A.shape)
+        slim.check_build_memory(n_items, self.free_bytes(), column_batch)
+        ld = slim.gram_leading_dim(n_items)
+        T = A.T
+        G = torch.empty(n_items, ld, dtype=torch.float64, device=self.device)
+        with self._timed('slim_gram', (n_users, n_items, A.nnz)):
+            _lib.check(self.lib.pk_i2i_build_f64(self.stream(), n_users, n_items, _ptr(A.indptr), _ptr(A.indices),
+                                                 _ptr(A.values), A.val_kind, _ptr(T.indptr), _ptr(T.indices),
+                                                 _ptr(T.values), _ptr(G), ld), 'pk_i2i_build_f64')
+            _lib.check(self.lib.pk_ease_diag_f64(self.stream(), n_items, _ptr(T.indptr), _ptr(T.values), T.val_kind,
+                                                 0.0, _ptr(G), ld), 'pk_ease_diag_f64')
+        return G
+
+    def slim_solve(self, G, n, j0, nc, l1, l2, tol, max_sweeps, positive=True, out=None):
+        """(Wt_block, sweeps): the target columns [j0, j0 + nc) of the SLIM problem over the Gram image G of n items, as the
+        rows of a dense fp64 device block [nc x slim.gram_leading_dim(n)] of W^T (pad columns exactly 0), and the int32
+        device vector of the sweeps run per column (pk_slim_solve_f64: the contract of include/polara_hip.h).  `out`: a
+        block of at least nc rows to write into."""
+        from . import slim
+        n, j0, nc = int(n), int(j0), int(nc)
+        slim.check_items(n)
+        l1, l2, tol, max_sweeps = slim.check_parameters(l1, l2, tol, max_sweeps)
+        if not 0 <= j0 <= j0 + nc <= n:
+            raise ValueError('slim_solve: columns [%d, %d) outside the %d items' % (j0, j0 + nc, n))
+        ldw = slim.gram_leading_dim(n)
+        if out is None:
+            out = torch.empty(max(nc, 1), ldw, dtype=torch.float64, device=self.device)
+        if out.dtype != torch.float64 or out.shape[0] < nc or out.stride(0) < n or out.stride(1) != 1:
+            raise ValueError('slim_solve: the output block does not hold %d rows of %d fp64 columns' % (nc, n))
+        block = out[:nc]
+        sweeps = torch.empty(max(nc, 1), dtype=torch.int32, device=self.device)[:nc]
+        work = self._work(self.lib.pk_slim_work_bytes(n, nc))
+        with self._timed('slim_solve', (n, nc)):
+            _lib.check(self.lib.pk_slim_solve_f64(self.stream(), n, _ptr(G), G.stride(0), j0, nc, l1, l2, tol, max_sweeps,
+                                                  1 if positive else 0, _ptr(block), out.stride(0), _ptr(sweeps), _ptr(work)),
+                       'pk_slim_solve_f64')
+        return block, sweeps
+
+    def slim_csr(self, Wt_block, n):
+        """(indptr int64 [nc + 1], indices int32, values fp64), all on the device: the rows of the block of `slim_solve` as
+        CSR rows — an entry is stored when it is != 0, in ascending index order (pk_slim_csr_count, pk_slim_csr_fill)."""
+        n, nc = int(n), int(Wt_block.shape[0])
+        indptr = torch.empty(nc + 1, dtype=torch.int64, device=self.device)
+        work = self._work(8 * nc)
+        with self._timed('slim_csr', (n, nc)):
+            _lib.check(self.lib.pk_slim_csr_count(self.stream(), nc, n, _ptr(Wt_block), Wt_block.stride(0), _ptr(indptr),
+                                                  _ptr(work)), 'pk_slim_csr_count')
+            nnz = int(indptr[-1].item())
+            indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=self.device)[:nnz]
+            values = torch.empty(max(nnz, 1), dtype=torch.float64, device=self.device)[:nnz]
+            _lib.check(self.lib.pk_slim_csr_fill(self.stream(), nc, n, _ptr(Wt_block), Wt_block.stride(0), _ptr(indptr), nnz,
+                                                 _ptr(indices), _ptr(values)), 'pk_slim_csr_fill')
+        return indptr, indices, values
+
     # ---- item cold start -----------------------------------------------------------------------------------------
     def coldstart_queries(self, F, W, G):
         """E = (F W) G for the cold items of a DeviceCSR over the training labels, fp64: the SpMM and the tall-skinny product
