@@ -7,6 +7,7 @@ DESIGN.md 8l.  Scores are s_u = t_u B through the item-to-item scoring pass (pk_
 
 The first part of the module is the host-side planning (pure Python: the shapes the kernels work with and the memory guard
 of the build; tests/test_ease_host.py holds it against the library's own pk_* planning functions), the second the model."""
+from functools import partial
 from timeit import default_timer as timer
 
 import numpy as np
@@ -69,69 +70,42 @@ def check_regularization(value):
 
 
 # ---- model -----------------------------------------------------------------------------------------------------------
-from .models import _DenseItemModel, _SparseScoresMixin     # noqa: E402  (the planning part above needs neither)
+from .models import _ItemWeightModel, _setting     # noqa: E402  (the planning part above needs neither)
 
 
-class EASEModel(_SparseScoresMixin, _DenseItemModel):
+def _dense_only(value):
+    if not value:
+        raise NotImplementedError('EASE scores are dense: the sparse branch of the item-to-item models is not offered '
+                                  '(dense_output is fixed at True)')
+    return True
+
+
+class EASEModel(_ItemWeightModel):
     """EASE: `item_weights` is the device image of B [n_items x leading dim] (fp64; diagonal and pad columns 0),
     `precision_diagonal` the host vector d = diag (X^T X + lambda I)^-1.  `regularization` is lambda (a change renews the
     model); `implicit` replaces training and test feedback by their sign, as in CooccurrenceModel.  Every item is a
     candidate (the dense branch of the item-to-item scoring): under `filter_seen` seen items come after all unseen ones,
     ties go to the lower item index.  Single process; INTEGRATION.md has the semantics."""
     _topk_limit = MAX_TOPK
+    _weight_slots = ('_weights', 'precision_diagonal')
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.method = 'EASE'
         self._regularization = DEFAULT_REGULARIZATION
-        self._implicit = False
-        self._pad_const = -1
-        self._weights = None
-        self.precision_diagonal = None
-        self.build_stats = {}
+        self._dense_output = True
 
-    @property
-    def regularization(self):
-        """lambda of the objective: a change renews the model"""
-        return self._regularization
-
-    @regularization.setter
-    def regularization(self, value):
-        lam = check_regularization(value)
-        if lam != self._regularization:
-            self._regularization = lam
-            self._renew_model()
-
-    @property
-    def implicit(self):
-        """feedback values replaced by their sign (training and test): a change renews the model"""
-        return self._implicit
-
-    @implicit.setter
-    def implicit(self, value):
-        if bool(value) != self._implicit:
-            self._implicit = bool(value)
-            self._renew_model()
-
-    @property
-    def dense_output(self):
-        """Always True: EASE scores are dense (B has no zero off the diagonal)."""
-        return True
-
-    @dense_output.setter
-    def dense_output(self, value):
-        if not value:
-            raise NotImplementedError('EASE scores are dense: the sparse branch of the item-to-item models is not offered '
-                                      '(dense_output is fixed at True)')
-
-    def _renew_model(self):
-        super()._renew_model()
-        self._weights = None               # the dense image is large: freed at once, not when the next build replaces it
-        self.precision_diagonal = None
+    regularization = _setting('regularization', '_renew_model', 'lambda of the objective: a change renews the model',
+                              check=check_regularization)
+    dense_output = _setting('dense_output', '_refresh_model', 'Always True: EASE scores are dense (B has no zero off the '
+                            'diagonal).', check=_dense_only)
 
     @property
     def item_weights(self):
         """The device image of B [n_items x leading dim] (columns beyond n_items are 0)."""
+        return self._weights
+
+    def _operand(self):
         return self._weights
 
     def build(self):
@@ -140,22 +114,11 @@ class EASEModel(_SparseScoresMixin, _DenseItemModel):
         entries) raises numpy.linalg.LinAlgError naming the item's column."""
         self._single_process()
         ops = self.ops
-        self._weights = self.precision_diagonal = None
-        rows, cols, val, shp = self._training_triplets()
-        n_items = int(shp[1])
-        A = ops.csr_from_coo(rows, cols, val, shp)
-        if self.implicit:
-            import torch
-            A = A.with_columns(A.indices, torch.sign(A.values))
+        self._release_weights()
+        A = self._training_device_csr()
+        n_items = A.shape[1]
         stages = {}
-
-        def stage(name, fn):
-            t0 = timer()
-            res = fn()
-            ops.synchronize()
-            stages[name + '_s'] = timer() - t0
-            return res
-
+        stage = partial(self._stage, stages)
         start = timer()
         img = stage('gram', lambda: ops.ease_gram(A, self.regularization))
         try:
@@ -175,19 +138,3 @@ class EASEModel(_SparseScoresMixin, _DenseItemModel):
         self.precision_diagonal = ops.to_host(d)
         self.build_stats = dict(stages, n_items=n_items, nnz=int(A.nnz), image_bytes=int(B.numel() * B.element_size()),
                                 chol_image_bytes=chol_image_bytes(n_items))
-
-    def _test_values(self, T):
-        if not self.implicit:
-            return T
-        import torch
-        return T.with_columns(T.indices, torch.sign(T.values))
-
-    def _score(self, T, n_items, want_scores=False):
-        recs, scores = self.ops.i2i_topk(self._test_values(T), self._weights, n_items, self.topk, self.filter_seen,
-                                         sparse=False, want_scores=want_scores)
-        return (recs, scores) if want_scores else recs
-
-    _implicit_values = staticmethod(np.sign)
-
-    def _slice_scores(self, T, n_items):
-        return self.ops.to_host(self.ops.spmm(T, self._weights))[:, :n_items]      # pk_spmm_csr_ex over B's image

@@ -35,15 +35,18 @@ def _format_elapsed(seconds_total):
     return f'{hours:.0f}h:{minutes:>02.0f}m:{seconds:>02.0f}s'
 
 
-def _setting(name, on_change, doc):
+def _setting(name, on_change, doc, check=None):
     """A configuration attribute stored as `_<name>` whose CHANGE (assigning an equal value is a no-op) calls the
-    model method `on_change` — the reference's cache rules (models.py:119-148, 870-887, 930-940) in one place."""
+    model method `on_change` — the reference's cache rules (models.py:119-148, 870-887, 930-940) in one place.  `check`
+    maps an assigned value to the one that is stored and compared, or raises."""
     slot = '_' + name
 
     def get(self):
         return getattr(self, slot)
 
     def put(self, value):
+        if check is not None:
+            value = check(value)
         if getattr(self, slot) != value:
             setattr(self, slot, value)
             getattr(self, on_change)()
@@ -1086,11 +1089,79 @@ class _DenseItemModel(RecommenderModel):
         return recs
 
 
-class _SparseScoresMixin:
-    """`downvote_seen_items` and `get_topk_elements` that also take the SciPy score matrices of a sparse branch
-    (CooccurrenceModel, SimilarityAggregation: what their `slice_recommendations` returns without `dense_output`), and the
-    two entry points those models share.  A model provides `_score`, `_implicit_values` (the host counterpart of its
-    `_test_values`) and `_slice_scores` (the host score block of a slice's device CSR)."""
+class _ItemWeightModel(_DenseItemModel):
+    """The layer the item-weight models share (CooccurrenceModel, EASEModel, SLIMModel, SimilarityAggregation): scores are
+    s_u = t_u B for weights B kept on the device.  A model supplies `build()` and `_operand()`, the B to score with: a
+    dense image [n_items x leading dim] goes through the item-to-item pass (pk_i2i_topk, pk_spmm_csr_ex), a canonical
+    device CSR through the sparse x sparse one (pk_spsp_topk, pk_spsp_rows_f64).  It names the attributes that hold its
+    weights in `_weight_slots` (dropped whenever the model is renewed) and, where it differs, its `_implicit_rule`.  The
+    layer owns the `implicit` and `dense_output` settings, the scoring entry points, and `downvote_seen_items` and
+    `get_topk_elements` that also take the SciPy score matrices `slice_recommendations` returns without `dense_output`."""
+    _weight_slots = ()
+    _operand_noun = 'weights'                      # what the item-count check calls B
+    _implicit_rule = staticmethod(torch.sign)      # what `implicit` makes of feedback values (a device or a host tensor)
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._implicit = False
+        self._dense_output = False
+        self._pad_const = -1
+        self.build_stats = {}
+        self._release_weights()
+
+    implicit = _setting('implicit', '_renew_model', 'feedback values replaced by their sign (training and test): a new model')
+    dense_output = _setting('dense_output', '_refresh_model', 'the dense or the sparse branch of the scoring: new lists')
+
+    def _release_weights(self):
+        for slot in self._weight_slots:    # dense images are large: freed at once, not when the next build replaces them
+            setattr(self, slot, None)
+
+    def _renew_model(self):
+        super()._renew_model()
+        self._release_weights()
+
+    # ---- build helpers --------------------------------------------------------------------------------------------
+    def _training_device_csr(self):
+        """The training matrix above `feedback_threshold` as a device CSR in the data's item order, under the implicit
+        rule when `implicit`."""
+        rows, cols, val, shp = self._training_triplets()
+        return self._test_values(self.ops.csr_from_coo(rows, cols, val, shp))
+
+    def _stage(self, stages, name, fn):
+        """fn() run to completion on the device, its wall time added to stages['<name>_s']."""
+        t0 = timer()
+        res = fn()
+        self.ops.synchronize()
+        stages[name + '_s'] = stages.get(name + '_s', 0.0) + (timer() - t0)
+        return res
+
+    # ---- scoring --------------------------------------------------------------------------------------------------
+    def _test_values(self, T):
+        """The device CSR T under the implicit rule: the test rows, and the training rows where the rule covers them."""
+        return T.with_columns(T.indices, self._implicit_rule(T.values)) if self.implicit else T
+
+    def _implicit_values(self, vals):
+        """`_test_values` for a host fp64 vector."""
+        return self._implicit_rule(torch.tensor(vals)).numpy() if self.implicit else vals
+
+    def _score(self, T, n_items, want_scores=False):
+        ops, B = self.ops, self._operand()
+        if torch.is_tensor(B):
+            recs, scores = ops.i2i_topk(self._test_values(T), B, n_items, self.topk, self.filter_seen,
+                                        sparse=not self.dense_output, want_scores=want_scores)
+        else:
+            if n_items != B.shape[0]:
+                raise ValueError('test data over %d items, the %s over %d' % (n_items, self._operand_noun, B.shape[0]))
+            recs, scores = ops.spsp_topk(self._test_values(T), B, self.topk, self.filter_seen,
+                                         sparse=not self.dense_output, want_scores=want_scores)
+        return (recs, scores) if want_scores else recs
+
+    def _slice_scores(self, T, n_items):
+        """The host score block of a slice's device CSR."""
+        ops, B = self.ops, self._operand()
+        if torch.is_tensor(B):
+            return ops.to_host(ops.spmm(T, B))[:, :n_items]        # pk_spmm_csr_ex over the image
+        return ops.to_host(ops.spsp_rows(T, B))                    # pk_spsp_rows_f64
 
     def recommend_with_scores(self):
         """(lists, their fp64 scores) of every test user, both host arrays (pads: item -1, score 0)."""
@@ -1109,9 +1180,7 @@ class _SparseScoresMixin:
         from scipy.sparse import csr_matrix
         stop = min(stop, shape[0])
         users, items, fdbk = self._slice_test_data(test_data, start, stop)
-        vals = np.asarray(fdbk, dtype=np.float64)
-        if self.implicit:
-            vals = self._implicit_values(vals)
+        vals = self._implicit_values(np.asarray(fdbk, dtype=np.float64))
         indptr, indices, values = scoring.test_csr_from_triplet((users, items, vals), (stop - start, shape[1]), None)
         T = self.ops.csr(indptr, indices, values, (stop - start, shape[1]))
         scores = np.ascontiguousarray(self._slice_scores(T, shape[1]))
@@ -1152,7 +1221,7 @@ class _SparseScoresMixin:
         return out
 
 
-class CooccurrenceModel(_SparseScoresMixin, _DenseItemModel):
+class CooccurrenceModel(_ItemWeightModel):
     """Item-to-item (models.py:699-725): C = A^T A with the diagonal set to 0, scores s_u = sum_i t_ui C[i, :].
 
     C is built on the device and kept there as a dense image, fp32 when every entry survives the rounding (integer
@@ -1162,27 +1231,19 @@ class CooccurrenceModel(_SparseScoresMixin, _DenseItemModel):
     the seen ones under `filter_seen`, rows with fewer than `topk` of them padded with -1.  Ties go to the lower item
     index.  INTEGRATION.md lists where this differs from the reference."""
     _topk_limit = 1024
+    _weight_slots = ('_i2i',)
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.method = 'item-to-item'
-        self._implicit = False
-        self._dense_output = False
-        self._pad_const = -1
-        self._i2i = None
         self.i2i_dtype = None
-        self.build_stats = {}
-
-    implicit = _setting('implicit', '_renew_model', 'feedback values replaced by their sign (training and test): a new model')
-    dense_output = _setting('dense_output', '_refresh_model', 'the dense or the sparse branch of the scoring: new lists')
-
-    def _renew_model(self):
-        super()._renew_model()
-        self._i2i = None                   # the dense image is large: freed at once, not when the next build replaces it
 
     @property
     def i2i_matrix(self):
         """The device image of C [n_items x leading dim] (columns beyond n_items are 0)."""
+        return self._i2i
+
+    def _operand(self):
         return self._i2i
 
     def build(self):
@@ -1190,31 +1251,15 @@ class CooccurrenceModel(_SparseScoresMixin, _DenseItemModel):
         certified fp32 image."""
         self._single_process()
         ops = self.ops
-        self._i2i = None
-        rows, cols, val, shp = self._training_triplets()
-        A = ops.csr_from_coo(rows, cols, val, shp)
-        if self.implicit:
-            A = A.with_columns(A.indices, torch.sign(A.values))
+        self._release_weights()
+        A = self._training_device_csr()
         start = timer()
         C, dtype = ops.i2i_build(A)
         ops.synchronize()
         self._track(start)
         self._i2i, self.i2i_dtype = C, dtype
-        self.build_stats = {'n_items': int(shp[1]), 'nnz': int(A.nnz), 'i2i_dtype': dtype,
+        self.build_stats = {'n_items': A.shape[1], 'nnz': int(A.nnz), 'i2i_dtype': dtype,
                             'image_bytes': int(C.numel() * C.element_size())}
-
-    def _test_values(self, T):
-        return T.with_columns(T.indices, torch.sign(T.values)) if self.implicit else T
-
-    def _score(self, T, n_items, want_scores=False):
-        recs, scores = self.ops.i2i_topk(self._test_values(T), self._i2i, n_items, self.topk, self.filter_seen,
-                                         sparse=not self.dense_output, want_scores=want_scores)
-        return (recs, scores) if want_scores else recs
-
-    _implicit_values = staticmethod(np.sign)
-
-    def _slice_scores(self, T, n_items):
-        return self.ops.to_host(self.ops.spmm(T, self._i2i))[:, :n_items]      # pk_spmm_csr_ex over C's image
 
 
 class PopularityModel(_DenseItemModel):

@@ -1594,21 +1594,33 @@ class HipOps:
         return out
 
     # ---- item-to-item / most popular (csrc/i2i.hip) ------------------------------------------------------------
-    def i2i_build(self, A):
-        """C = A^T A with the diagonal set to 0 as a dense device image [n_items x i2i.leading_dim(n_items)]
-        (pk_i2i_build_f64 on A's CSR and its CSC image), then certified: fp32 when every entry survives the rounding
-        (pk_i2i_image_f32), else fp64.  Raises MemoryError before allocating when the fp64 image would take more than
-        half of the free device memory.  Returns (C, 'float32' | 'float64')."""
-        from . import i2i
-        n_users, n_items = A.shape
-        ld = i2i.leading_dim(n_items)
-        i2i.check_build_memory(n_items, torch.cuda.mem_get_info(self.device)[0])
+    def _gram_image(self, name, A, rows, ld, diag=None):
+        """The fp64 device image [rows x ld] of A^T A for the device CSR A [n_users x n_items]: pk_i2i_build_f64 writes
+        rows [0, n_items) from A's CSR and its CSC image, diagonal and pad columns 0; with `diag` pk_ease_diag_f64 then
+        sets the diagonal to the items' sums of squares + diag.  Rows beyond n_items are left as allocated.  `name`: the
+        kernel-timer entry the launches are recorded under."""
+        n_users, n_items = (int(x) for x in A.shape)
         T = A.T
-        C64 = torch.empty(n_items, ld, dtype=torch.float64, device=self.device)
-        with self._timed('i2i_build', (n_users, n_items, A.nnz)):
+        G = torch.empty(rows, ld, dtype=torch.float64, device=self.device)
+        with self._timed(name, (n_users, n_items, A.nnz)):
             _lib.check(self.lib.pk_i2i_build_f64(self.stream(), n_users, n_items, _ptr(A.indptr), _ptr(A.indices),
                                                  _ptr(A.values), A.val_kind, _ptr(T.indptr), _ptr(T.indices),
-                                                 _ptr(T.values), _ptr(C64), ld), 'pk_i2i_build_f64')
+                                                 _ptr(T.values), _ptr(G), ld), 'pk_i2i_build_f64')
+            if diag is not None:
+                _lib.check(self.lib.pk_ease_diag_f64(self.stream(), n_items, _ptr(T.indptr), _ptr(T.values), T.val_kind,
+                                                     float(diag), _ptr(G), ld), 'pk_ease_diag_f64')
+        return G
+
+    def i2i_build(self, A):
+        """C = A^T A with the diagonal set to 0 as a dense device image [n_items x i2i.leading_dim(n_items)]
+        (`_gram_image`), then certified: fp32 when every entry survives the rounding (pk_i2i_image_f32), else fp64.
+        Raises MemoryError before allocating when the fp64 image would take more than half of the free device memory.
+        Returns (C, 'float32' | 'float64')."""
+        from . import i2i
+        n_items = int(A.shape[1])
+        ld = i2i.leading_dim(n_items)
+        i2i.check_build_memory(n_items, self.free_bytes())
+        C64 = self._gram_image('i2i_build', A, n_items, ld)
         C32 = torch.empty(n_items, ld, dtype=torch.float32, device=self.device)
         flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         _lib.check(self.lib.pk_i2i_image_f32(self.stream(), C64.numel(), _ptr(C64), _ptr(C32), _ptr(flag)),
@@ -1896,23 +1908,14 @@ class HipOps:
 
     # ---- EASE: closed-form item weights on the Cholesky image (csrc/hybrid.hip) ------------------------------------------
     def ease_gram(self, A, lam):
-        """The Cholesky image [ld x ld] of K = A^T A + lam I for the device CSR A: pk_i2i_build_f64 writes the rows of
-        A^T A (diagonal 0) straight into the image, pk_ease_diag_f64 the diagonal from A's CSC image.  Raises MemoryError
-        before allocating when this image and the weights image together would take more than half of the free device
-        memory (ease.check_build_memory)."""
+        """The Cholesky image [ld x ld] of K = A^T A + lam I for the device CSR A: the rows of A^T A and the diagonal go
+        straight into the image (`_gram_image`).  Raises MemoryError before allocating when this image and the weights
+        image together would take more than half of the free device memory (ease.check_build_memory)."""
         from . import ease
-        n_users, n_items = (int(x) for x in A.shape)
+        n_items = int(A.shape[1])
         ease.check_build_memory(n_items, self.free_bytes())
         ld = ease.chol_leading_dim(n_items)
-        T = A.T
-        K = torch.empty(ld, ld, dtype=torch.float64, device=self.device)
-        with self._timed('ease_gram', (n_users, n_items, A.nnz)):
-            _lib.check(self.lib.pk_i2i_build_f64(self.stream(), n_users, n_items, _ptr(A.indptr), _ptr(A.indices),
-                                                 _ptr(A.values), A.val_kind, _ptr(T.indptr), _ptr(T.indices),
-                                                 _ptr(T.values), _ptr(K), ld), 'pk_i2i_build_f64')
-            _lib.check(self.lib.pk_ease_diag_f64(self.stream(), n_items, _ptr(T.indptr), _ptr(T.values), T.val_kind,
-                                                 float(lam), _ptr(K), ld), 'pk_ease_diag_f64')
-        return K
+        return self._gram_image('ease_gram', A, ld, ld, diag=lam)
 
     def trtri(self, img, n):
         """In place W = L^-1 of the lower factor `chol` left in the image (pk_trtri_f64); the padding stays the identity."""
@@ -1938,22 +1941,13 @@ class HipOps:
     # ---- SLIM: sparse item weights by coordinate descent over the Gram image (csrc/slim.hip) ----------------------------
     def slim_gram(self, A, column_batch=None):
         """The Gram image [n_items x slim.gram_leading_dim(n_items)] of G = A^T A WITH its diagonal for the device CSR A
-        (pk_i2i_build_f64, then pk_ease_diag_f64 with lam = 0); the pad columns are 0.  Raises ValueError beyond
+        (`_gram_image` with 0 added to the diagonal); the pad columns are 0.  Raises ValueError beyond
         pk_slim_max_items() and MemoryError before allocating when the image and one batch block of `column_batch` columns
         (default: the default rule) would take more than half of the free device memory (slim.check_build_memory)."""
         from . import slim
-        n_users, n_items = (int(x) for x in A.shape)
+        n_items = int(A.shape[1])
         slim.check_build_memory(n_items, self.free_bytes(), column_batch)
-        ld = slim.gram_leading_dim(n_items)
-        T = A.T
-        G = torch.empty(n_items, ld, dtype=torch.float64, device=self.device)
-        with self._timed('slim_gram', (n_users, n_items, A.nnz)):
-            _lib.check(self.lib.pk_i2i_build_f64(self.stream(), n_users, n_items, _ptr(A.indptr), _ptr(A.indices),
-                                                 _ptr(A.values), A.val_kind, _ptr(T.indptr), _ptr(T.indices),
-                                                 _ptr(T.values), _ptr(G), ld), 'pk_i2i_build_f64')
-            _lib.check(self.lib.pk_ease_diag_f64(self.stream(), n_items, _ptr(T.indptr), _ptr(T.values), T.val_kind,
-                                                 0.0, _ptr(G), ld), 'pk_ease_diag_f64')
-        return G
+        return self._gram_image('slim_gram', A, n_items, slim.gram_leading_dim(n_items), diag=0.0)
 
     def slim_solve(self, G, n, j0, nc, l1, l2, tol, max_sweeps, positive=True, out=None):
         """(Wt_block, sweeps): the target columns [j0, j0 + nc) of the SLIM problem over the Gram image G of n items, as the

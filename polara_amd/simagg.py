@@ -12,7 +12,7 @@ import numpy as np
 
 from . import i2i
 from .coldstart import ItemColdStartEvaluationMixin
-from .models import RecommenderModel, _DenseItemModel, _setting, _SparseScoresMixin
+from .models import RecommenderModel, _ItemWeightModel, _setting
 
 MAX_TOPK = i2i.MAX_TOPK        # the window candidates are merged by the item-to-item merge kernel: its limit
 WINDOW = i2i.WINDOW            # columns of the product one workgroup accumulates in LDS (2048 fp64 accumulators, 16 KiB)
@@ -63,12 +63,12 @@ def stored_csr(m, shape=None):
     return m
 
 
-def _ones(T):
-    """Every nonzero value of the device CSR replaced by 1 (stored zeros stay: seen, no score)."""
-    return T.with_columns(T.indices, (T.values != 0).to(T.values.dtype))
+def _ones(values):
+    """Every nonzero value replaced by 1 (stored zeros stay: seen, no score)."""
+    return (values != 0).to(values.dtype)
 
 
-class SimilarityAggregation(_SparseScoresMixin, _DenseItemModel):
+class SimilarityAggregation(_ItemWeightModel):
     """'SIM' (hybrid/models.py:25-44): the scores of a test user are its known feedback aggregated over the item
     similarity S = `data.item_relations` with the diagonal set to 0.  `dense_output=False` computes T S^T like the
     reference's `T.dot(S.T)` and keeps the sparse branch's candidates (nonzero scores, minus the seen items under
@@ -78,23 +78,15 @@ class SimilarityAggregation(_SparseScoresMixin, _DenseItemModel):
     negative feedback counts as 1, zero feedback only as seen).  Candidate rules,
     tie order and `topk` checks are CooccurrenceModel's; INTEGRATION.md §11 lists the differences from the reference."""
     _topk_limit = MAX_TOPK
+    _weight_slots = ('_S', '_St')
+    _operand_noun = 'similarity'
+    _implicit_rule = staticmethod(_ones)
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.method = 'SIM'
-        self._implicit = False
-        self._dense_output = False
-        self._pad_const = -1
-        self._S = None
-        self._St = None
-        self.build_stats = {}
 
     implicit = _setting('implicit', '_refresh_model', 'nonzero test feedback replaced by 1: new lists, same model')
-    dense_output = _setting('dense_output', '_refresh_model', 'the dense or the sparse branch of the scoring: new lists')
-
-    def _renew_model(self):
-        super()._renew_model()
-        self._S = self._St = None
 
     @property
     def item_similarity_matrix(self):
@@ -124,23 +116,6 @@ class SimilarityAggregation(_SparseScoresMixin, _DenseItemModel):
 
     def _operand(self):
         return self._S if self.dense_output else self._St
-
-    def _test_values(self, T):
-        return _ones(T) if self.implicit else T
-
-    def _score(self, T, n_items, want_scores=False):
-        if n_items != self._S.shape[0]:
-            raise ValueError('test data over %d items, the similarity over %d' % (n_items, self._S.shape[0]))
-        recs, scores = self.ops.spsp_topk(self._test_values(T), self._operand(), self.topk, self.filter_seen,
-                                          sparse=not self.dense_output, want_scores=want_scores)
-        return (recs, scores) if want_scores else recs
-
-    @staticmethod
-    def _implicit_values(vals):
-        return (vals != 0).astype(np.float64)
-
-    def _slice_scores(self, T, n_items):
-        return self.ops.to_host(self.ops.spsp_rows(T, self._operand()))         # pk_spsp_rows_f64
 
 
 class SimilarityAggregationItemColdStart(ItemColdStartEvaluationMixin, RecommenderModel):

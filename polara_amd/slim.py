@@ -11,6 +11,7 @@ whole is transposed on the device; DESIGN.md 8m.  Scores are s_u = t_u W through
 The first part of the module is the host-side planning (pure Python: shapes, the batch rule, the memory guard and the
 parameter checks; tests/test_slim_host.py holds it against the library's own pk_slim_* planning functions), the second the
 model."""
+from functools import partial
 from timeit import default_timer as timer
 
 import numpy as np
@@ -123,7 +124,7 @@ def check_parameters(l1, l2, tol, max_sweeps):
 
 
 # ---- model -----------------------------------------------------------------------------------------------------------
-from .models import _DenseItemModel, _setting, _SparseScoresMixin     # noqa: E402  (the planning part above needs neither)
+from .models import _ItemWeightModel, _setting     # noqa: E402  (the planning part above needs neither)
 
 
 def _parameter(name, index, doc):
@@ -143,7 +144,7 @@ def _parameter(name, index, doc):
     return property(fget, fset, doc=doc)
 
 
-class SLIMModel(_SparseScoresMixin, _DenseItemModel):
+class SLIMModel(_ItemWeightModel):
     """SLIM: `item_weights` is the canonical device CSR of W [n_items x n_items] (W[i, j]: the weight of source item i for
     target item j; sorted indices, no stored zeros, no diagonal), `sweeps` the host int32 vector of the sweeps every
     column ran.  `l1_regularization` (1.0), `l2_regularization` (10.0), `tolerance` (1e-4: a column stops when the largest
@@ -155,6 +156,7 @@ class SLIMModel(_SparseScoresMixin, _DenseItemModel):
     -1 pads, exactly as SimilarityAggregation; a change re-scores and does not rebuild.  Ties go to the lower item
     index.  Single process; INTEGRATION.md has the semantics."""
     _topk_limit = MAX_TOPK
+    _weight_slots = ('_W', 'sweeps')
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -164,13 +166,8 @@ class SLIMModel(_SparseScoresMixin, _DenseItemModel):
         self._tolerance = DEFAULT_TOLERANCE
         self._max_sweeps = DEFAULT_MAX_SWEEPS
         self._positive = True
-        self._implicit = False
         self._column_batch = None
         self._dense_output = True
-        self._pad_const = -1
-        self._W = None
-        self.sweeps = None
-        self.build_stats = {}
 
     l1_regularization = _parameter('l1_regularization', 0, 'l1 of the objective (>= 0): a change renews the model')
     l2_regularization = _parameter('l2_regularization', 1, 'l2 of the objective (>= 0): a change renews the model')
@@ -178,29 +175,15 @@ class SLIMModel(_SparseScoresMixin, _DenseItemModel):
                            'change renews the model')
     max_sweeps = _parameter('max_sweeps', 3, 'the cap on the sweeps of a column (>= 1): a change renews the model')
     positive = _setting('positive', '_renew_model', 'weights constrained to be >= 0: a new model')
-    implicit = _setting('implicit', '_renew_model', 'feedback values replaced by their sign (training and test): a new model')
-    dense_output = _setting('dense_output', '_refresh_model', 'the dense or the sparse branch of the scoring: new lists')
-
-    @property
-    def column_batch(self):
-        """columns solved per launch (None: default_batch_columns): a change renews the model, the weights stay the same"""
-        return self._column_batch
-
-    @column_batch.setter
-    def column_batch(self, value):
-        nc = check_column_batch(value)
-        if nc != self._column_batch:
-            self._column_batch = nc
-            self._renew_model()
-
-    def _renew_model(self):
-        super()._renew_model()
-        self._W = None                     # freed at once, not when the next build replaces it
-        self.sweeps = None
+    column_batch = _setting('column_batch', '_renew_model', 'columns solved per launch (None: default_batch_columns): a '
+                            'change renews the model, the weights stay the same', check=check_column_batch)
 
     @property
     def item_weights(self):
         """The canonical device CSR of W [n_items x n_items] (None before the build)."""
+        return self._W
+
+    def _operand(self):
         return self._W
 
     def build(self):
@@ -211,20 +194,11 @@ class SLIMModel(_SparseScoresMixin, _DenseItemModel):
         from .ops import DeviceCSR
         self._single_process()
         ops = self.ops
-        self._W = self.sweeps = None
-        rows, cols, val, shp = self._training_triplets()
-        n_items = check_items(shp[1])
-        A = ops.csr_from_coo(rows, cols, val, shp)
-        if self.implicit:
-            A = A.with_columns(A.indices, torch.sign(A.values))
+        self._release_weights()
+        A = self._training_device_csr()
+        n_items = check_items(A.shape[1])
         stages = {'gram_s': 0.0, 'solve_s': 0.0, 'csr_s': 0.0}
-
-        def stage(name, fn):
-            t0 = timer()
-            res = fn()
-            ops.synchronize()
-            stages[name + '_s'] += timer() - t0
-            return res
+        stage = partial(self._stage, stages)
 
         start = timer()
         free = ops.free_bytes()
@@ -257,21 +231,3 @@ class SLIMModel(_SparseScoresMixin, _DenseItemModel):
                                 fill=nnz_w / float(n_items * n_items), max_sweeps=int(self.sweeps.max()),
                                 mean_sweeps=float(self.sweeps.mean()),
                                 capped_columns=int((self.sweeps >= self.max_sweeps).sum()), column_batch=int(batch))
-
-    def _test_values(self, T):
-        if not self.implicit:
-            return T
-        import torch
-        return T.with_columns(T.indices, torch.sign(T.values))
-
-    def _score(self, T, n_items, want_scores=False):
-        if n_items != self._W.shape[0]:
-            raise ValueError('test data over %d items, the weights over %d' % (n_items, self._W.shape[0]))
-        recs, scores = self.ops.spsp_topk(self._test_values(T), self._W, self.topk, self.filter_seen,
-                                          sparse=not self.dense_output, want_scores=want_scores)
-        return (recs, scores) if want_scores else recs
-
-    _implicit_values = staticmethod(np.sign)
-
-    def _slice_scores(self, T, n_items):
-        return self.ops.to_host(self.ops.spsp_rows(T, self._W))                 # pk_spsp_rows_f64

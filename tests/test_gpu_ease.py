@@ -4,14 +4,13 @@ residual, determinism, the failure path of a singular Gram matrix, and the model
 
 Every bound compares with what the reference routine achieves on the same input (printed next to the device's figure:
 run with -s to see the ratios DESIGN.md 8l quotes)."""
-import functools
-
 import numpy as np
 import pytest
 import scipy.linalg
 
 import ease_reference as ref
 import i2i_reference as i2i_ref
+from item_model_helpers import cached_fixture, device_csr as _device_csr, limits_case, model
 from test_gpu_hybrid import _spd
 
 pytestmark = pytest.mark.gpu
@@ -42,11 +41,6 @@ def test_triangular_inverse_against_scipy(n, beta, hip_ops):
 
 
 # ---- weights -----------------------------------------------------------------------------------------------------------
-def _device_csr(hip_ops, idx, val, shape, implicit=False):
-    v = np.sign(val) if implicit else val
-    return hip_ops.csr_from_coo(idx[:, 0], idx[:, 1], v, shape)
-
-
 def _device_weights(hip_ops, idx, val, shape, lam, implicit=False):
     """(B image, d) on the host through the four stages of the build."""
     n = shape[1]
@@ -106,10 +100,7 @@ def test_weights_at_the_tile_edges(n, hip_ops):
     _check_weights('weights n=%d' % n, Bimg, d, ref.training_matrix(idx, val, shape), 10.0, floor=2.0 ** -52)
 
 
-@functools.lru_cache(maxsize=None)
-def _fixture(name, implicit):
-    idx, val, shape = ref.training(name)
-    return idx, val, shape, ref.training_matrix(idx, val, shape, implicit)
+_fixture = cached_fixture(ref)
 
 
 @pytest.mark.parametrize('name', sorted(ref.FIXTURES))
@@ -138,14 +129,7 @@ def test_gram_image_is_exact(name, half_steps, hip_ops):
 
 # ---- determinism and the failure path -----------------------------------------------------------------------------------
 def _model(hip_ops, idx, val, shape, test=None, holdout=None, lam=10.0, implicit=False):
-    from polara_amd import EASEModel
-    from polara_amd.data import ArrayData
-    data = ArrayData((idx[:, 0], idx[:, 1], val), n_users=shape[0], n_items=shape[1], test=test, holdout=holdout,
-                     warm_start=test is not None)
-    m = EASEModel(data, ops=hip_ops)
-    m.verbose = False
-    m.regularization, m.implicit = lam, implicit
-    return m
+    return model('EASEModel', hip_ops, idx, val, shape, test, holdout, regularization=lam, implicit=implicit)
 
 
 def test_two_builds_give_the_same_bits(hip_ops):
@@ -237,17 +221,8 @@ def test_lifecycle(hip_ops):
 
 def test_stated_limits(hip_ops, monkeypatch):
     from polara_amd import ease
-    rng = np.random.default_rng(3)
-    n_users, n_items = 40, 1030
-    u = np.repeat(np.arange(n_users), 30)
-    pairs = np.unique(np.stack([u, rng.integers(0, n_items, len(u))], 1), axis=0)
-    val = rng.integers(1, 6, len(pairs)).astype(np.float64)
-    hold = (np.arange(n_users), rng.integers(0, n_items, n_users), np.ones(n_users))
-    from polara_amd import EASEModel
-    from polara_amd.data import ArrayData
-    data = ArrayData((pairs[:, 0], pairs[:, 1], val), n_users=n_users, n_items=n_items, holdout=hold, warm_start=False)
-    m = EASEModel(data, ops=hip_ops)
-    m.verbose, m.regularization = False, 1.0
+    pairs, val, (n_users, n_items), hold = limits_case()
+    m = _model(hip_ops, pairs, val, (n_users, n_items), holdout=hold, lam=1.0)
     m.topk = 1024
     assert m.recommendations.shape == (n_users, 1024)
     m.topk = 1025

@@ -12,16 +12,12 @@ import scipy.sparse as sps
 
 import i2i_reference as i2i_ref
 import slim_reference as ref
+from item_model_helpers import cached_fixture, device_csr as _device_csr, limits_case, model
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [1, 2, 17, 63, 64, 65, 257, 1025, 2050]        # around the wave (64) and the 1024-thread workgroup
 RESIDENCES = ['lds', 'global']                         # where the residual row of a column lives
-
-
-def _device_csr(hip_ops, idx, val, shape, implicit=False):
-    v = np.sign(val) if implicit else val
-    return hip_ops.csr_from_coo(idx[:, 0], idx[:, 1], v, shape)
 
 
 def _device_gram(hip_ops, idx, val, shape, implicit=False):
@@ -99,10 +95,7 @@ def test_solver_at_the_tile_edges(n, positive, residence, hip_ops, pk_options):
 
 
 # ---- the fixtures ------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _fixture(name, implicit):
-    idx, val, shape = ref.training(name)
-    return idx, val, shape, ref.training_matrix(idx, val, shape, implicit)
+_fixture = cached_fixture(ref)
 
 
 def _fixture_columns(name):
@@ -216,16 +209,8 @@ def test_compaction_of_a_block(n, nc, hip_ops):
 
 # ---- model ---------------------------------------------------------------------------------------------------------------
 def _model(hip_ops, idx, val, shape, test=None, holdout=None, l1=1.0, l2=5.0, implicit=False, **settings):
-    from polara_amd import SLIMModel
-    from polara_amd.data import ArrayData
-    data = ArrayData((idx[:, 0], idx[:, 1], val), n_users=shape[0], n_items=shape[1], test=test, holdout=holdout,
-                     warm_start=test is not None)
-    m = SLIMModel(data, ops=hip_ops)
-    m.verbose = False
-    m.l1_regularization, m.l2_regularization, m.implicit = l1, l2, implicit
-    for key, value in settings.items():
-        setattr(m, key, value)
-    return m
+    return model('SLIMModel', hip_ops, idx, val, shape, test, holdout, l1_regularization=l1, l2_regularization=l2,
+                 implicit=implicit, **settings)
 
 
 def _csr_arrays(hip_ops, W):
@@ -378,17 +363,8 @@ def test_lifecycle(hip_ops):
 
 def test_stated_limits(hip_ops, monkeypatch):
     from polara_amd import slim
-    rng = np.random.default_rng(3)
-    n_users, n_items = 40, 1030
-    u = np.repeat(np.arange(n_users), 30)
-    pairs = np.unique(np.stack([u, rng.integers(0, n_items, len(u))], 1), axis=0)
-    val = rng.integers(1, 6, len(pairs)).astype(np.float64)
-    hold = (np.arange(n_users), rng.integers(0, n_items, n_users), np.ones(n_users))
-    from polara_amd import SLIMModel
-    from polara_amd.data import ArrayData
-    data = ArrayData((pairs[:, 0], pairs[:, 1], val), n_users=n_users, n_items=n_items, holdout=hold, warm_start=False)
-    m = SLIMModel(data, ops=hip_ops)
-    m.verbose, m.column_batch = False, 7
+    pairs, val, (n_users, n_items), hold = limits_case()
+    m = _model(hip_ops, pairs, val, (n_users, n_items), holdout=hold, l2=slim.DEFAULT_L2, column_batch=7)
     m.topk = 1024
     assert m.recommendations.shape == (n_users, 1024)
     m.topk = 1025
