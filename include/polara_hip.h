@@ -972,6 +972,72 @@ int pk_bpr_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, co
                      int64_t *counts_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * LightFM with the WARP loss (csrc/warp.hip; polara_amd/warp.py): rank k plus a bias, per-parameter adagrad, fp64, C = k + 1.
+ * P [n_users x C]: column k is the constant 1 and is never written.  E_id [n_items x C]: the items' identity embeddings,
+ * column k the bias.  E_lab [n_labels x C]: the label embeddings, column k the label's bias.  AP, AE, AL: the adagrad state
+ * of the three blocks, same shapes, 1 at build start and kept over the epochs (column k of AP is never touched).
+ * Item features: item i with m_i labels has a[i] = 1 / (1 + m_i); F_lab = diag(a) one_hot [n_items x n_labels], given as CSR
+ * (row_*: labels ascending within an item) and CSC (col_*: items ascending within a label).  The representation of item i is
+ *     q_i = a[i] * E_id[i] + S[i],   S[i] = (+0.0 + F[i,l1] * E_lab[l1]) + F[i,l2] * E_lab[l2] + ...  (storage order)
+ * Without features (a_dev == NULL) q_i = E_id[i]: no multiplication, no S, no G, no label launches.
+ * The positives, the schedule, the item order, the parts and perm are BPR's above.
+ *   Candidates (pk_warp_draw_candidates, one thread per position and draw):  D = max_sampled, 1 <= D <= PK_WARP_MAX_SAMPLED,
+ *     h = mix64(seed * 2^32 + epoch);  for t = 0 .. D - 1:  w = mix64(h + 64 * e + t) >> 32;  x = (w * n_c) >> 32;
+ *     j = item_order[item_ptr[c] + x]  (c, n_c: the positive's item part and its size);  cand[p * D + t] = j, or -1 when j lies
+ *     in row u of the CSR.  A -1 counts as a draw and is passed over.
+ *   Loss table (host, NumPy fp64, D doubles):  table[t] = min(10, log(max(1, floor((n_items - 1) / (t + 1))))).
+ *   One epoch (pk_warp_epoch_f64), per stratum s in stream order:
+ *     1. with features: S = F_lab E_lab over all items as above, and G [n_items x C] is cleared  (one launch)
+ *     2. the sweep (one launch): a block is swept sequentially by one group of w lanes, w = the smallest of 16, 32, 64 that is
+ *        >= C; lane c holds column c.  Per sample (u, i) in IEEE fp64 without contraction, division and square root
+ *        correctly rounded, tree = the halving tree of PMF above over C columns:
+ *          x_pos = tree(P[u] * q_i)
+ *          for t = 0 .. D - 1:  j = cand[t];  draws += 1;  if j < 0: continue
+ *              x_neg = tree(P[u] * q_j);   if not (x_neg > x_pos - 1): continue
+ *              L   = table[t]
+ *              g_u = L * (q_j - q_i)  (c < k);   g_i = -(L * P_old[u])  (c <= k);   g_j = L * P_old[u]  (c <= k)
+ *              adagrad per element:  step = lr / sqrt(A);  x <- x - step * g;  A <- A + g * g
+ *                on P[u] with g_u (state AP[u]), on E_id[i] with a[i] * g_i (AE[i]), on E_id[j] with a[j] * g_j (AE[j]);
+ *                without features the gradients of E_id are g_i and g_j themselves
+ *              with features:  G[i] <- G[i] + g_i;  G[j] <- G[j] + g_j
+ *              trained += 1;  stop
+ *          no violator: quiet += 1, nothing is stored.
+ *        q_i and q_j are formed from the LIVE identity rows (a row stays in registers while the next sample of the block
+ *        uses it again) and from the S of step 1.
+ *     3. with features, the label step (one launch; pk_warp_label_step_f64 is this step alone, followed by clearing G):
+ *          g_l = (+0.0 + F[i1,l] * G[i1]) + F[i2,l] * G[i2] + ...  over the items of label l ascending, per column c <= k;
+ *          the adagrad step above on E_lab[l] with g_l (state AL[l]).
+ *   After the last stratum G is cleared (with features) and the 64-bit block counters are added per stratum and then per
+ *   epoch: counts_dev[0..2] = trained, quiet, draws.  No atomics, no flags: E_lab is read-only while a stratum runs, the rows
+ *   of P, E_id, their states and G that a block writes are its own, and stream order separates the launches.  The label
+ *   embeddings therefore take `blocks` steps per epoch, each on one stratum's summed gradient.
+ * pk_warp_label_image_f64: S alone (step 1 without clearing G).
+ * work_dev: pk_warp_work_bytes(blocks) bytes.  The kernels trust the plan, the candidates and the feature matrices (indices
+ * in range, pointers ascending). */
+#define PK_WARP_MAX_SAMPLED 64
+int32_t pk_warp_max_rank(void);
+int64_t pk_warp_work_bytes(int32_t blocks);
+int pk_warp_draw_candidates(void *stream, int64_t nnz, int64_t n_users, int64_t n_items, int32_t blocks, int32_t max_sampled,
+                            const int32_t *users_dev, const int32_t *items_dev, const int64_t *perm_dev,
+                            const int32_t *item_order_dev, const int32_t *item_part_dev, const int64_t *item_ptr_dev,
+                            const int64_t *indptr_dev, const int32_t *indices_dev, uint32_t seed, uint32_t epoch,
+                            int32_t *cand_dev);
+int pk_warp_label_image_f64(void *stream, int32_t rank, int64_t n_items, int64_t n_labels, const int64_t *row_ptr_dev,
+                            const int32_t *row_idx_dev, const double *row_val_dev, const double *L_dev, int64_t ldl,
+                            double *S_dev, int64_t lds);
+int pk_warp_label_step_f64(void *stream, int32_t rank, int64_t n_items, int64_t n_labels, const int64_t *col_ptr_dev,
+                           const int32_t *col_idx_dev, const double *col_val_dev, double *G_dev, int64_t ldg, double *L_dev,
+                           int64_t ldl, double *AL_dev, int64_t ldal, double learning_rate);
+int pk_warp_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, int64_t n_items, int64_t n_labels,
+                      int32_t max_sampled, const int64_t *block_ptr_dev, const int32_t *users_dev, const int32_t *items_dev,
+                      const int32_t *cand_dev, const double *loss_table_dev, double *P_dev, int64_t ldp, double *E_dev,
+                      int64_t lde, double *AP_dev, int64_t ldap, double *AE_dev, int64_t ldae, double learning_rate,
+                      const double *a_dev, const int64_t *row_ptr_dev, const int32_t *row_idx_dev, const double *row_val_dev,
+                      const int64_t *col_ptr_dev, const int32_t *col_idx_dev, const double *col_val_dev, double *L_dev,
+                      int64_t ldl, double *AL_dev, int64_t ldal, double *S_dev, int64_t lds, double *G_dev, int64_t ldg,
+                      void *work_dev, int64_t *counts_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Implicit ALS (csrc/ials.hip): the alternating least squares of Hu, Koren and Volinsky for a CSR of confidences C
  * [n_rows x n_cols] (fp64 values, int64 row pointers, int32 column ids).  One half-step fixes Y [n_cols x rank] and solves
  * for every row u

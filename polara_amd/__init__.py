@@ -8,6 +8,7 @@
     from polara_amd import ProbabilisticMF                          # PMF trained by a blocked SGD sweep
     from polara_amd import ImplicitALS                              # iALS / WRMF: alternating least squares, exact per-row solves
     from polara_amd import ImplicitBPR                              # BPR-MF: pairwise ranking by a blocked triplet sweep
+    from polara_amd import LightFMWrapper, LightFMItemColdStart     # LightFM (WARP, item features), standard and item cold start
     from polara_amd import EASEModel                                # EASE: closed-form item weights on a device SPD inverse
     from polara_amd import SLIMModel                                # SLIM: sparse item weights by device coordinate descent
     from polara_amd import SVDModelSampled, RandomSampleArrayData   # sampled-negatives evaluation (1 holdout + n unseen items)
@@ -100,6 +101,7 @@ _EXPORTS = {
     'ProbabilisticMF': 'pmf',
     'ImplicitALS': 'ials',
     'ImplicitBPR': 'bpr',
+    'LightFMWrapper': 'warp', 'LightFMItemColdStart': 'warp',
     'EASEModel': 'ease',
     'SLIMModel': 'slim',
     'SimilarityAggregation': 'simagg', 'SimilarityAggregationItemColdStart': 'simagg',

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get('POLARA_HIP_LIB') or os.path.join(_HERE, 'libpolarahip
 
 PK_VAL_F32, PK_VAL_F64 = 0, 1
 PK_PMF_MAX_BLOCKS = 4096      # include/polara_hip.h
+PK_WARP_MAX_SAMPLED = 64      # include/polara_hip.h
 
 _vp, _i32, _i64, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 
@@ -188,6 +189,15 @@ PROTOTYPES = {
     'pk_bpr_draw_negatives': (C.c_int, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32,
                                         _vp]),
     'pk_bpr_epoch_f64': (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f64, _f64, _vp, _vp]),
+    'pk_warp_max_rank': (_i32, []),
+    'pk_warp_work_bytes': (_i64, [_i32]),
+    'pk_warp_draw_candidates': (C.c_int, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32,
+                                          C.c_uint32, _vp]),
+    'pk_warp_label_image_f64': (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64]),
+    'pk_warp_label_step_f64': (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f64]),
+    'pk_warp_epoch_f64': (C.c_int, [_vp, _i32, _i32, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
+                                    _vp, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                    _vp, _vp]),
     'pk_ials_max_rank': (_i32, []),
     'pk_ials_work_bytes': (_i64, [_i64, _i32]),
     'pk_ials_half_step_f64': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _i64, _vp, _vp]),

@@ -2328,6 +2328,145 @@ class HipOps:
         _lib.check(self.lib.pk_bpr_sigmoid_f64(self.stream(), x.numel(), _ptr(x), _ptr(out)), 'pk_bpr_sigmoid_f64')
         return out
 
+    # ---- LightFM with the WARP loss (csrc/warp.hip) ----------------------------------------------------------------------
+    def warp_max_rank(self):
+        return int(self.lib.pk_warp_max_rank())
+
+    def warp_plan(self, A, blocks, item_order=None, features=None):
+        """bpr_plan(A, blocks, item_order) plus plan['features']: None, or for a SciPy one-hot matrix `features` [n_items x
+        n_labels] a dict on the device — a (fp64 [n_items]: 1 / (1 + labels of the item)), F_lab = diag(a) one_hot as CSR
+        (row_ptr int64, row_idx int32, row_val fp64) and as CSC (col_ptr, col_idx: items ascending, col_val), n_labels."""
+        from . import warp
+        plan = self.bpr_plan(A, blocks, item_order)
+        plan['features'] = None
+        if features is not None:
+            n_items = plan['shape'][1]
+            if int(features.shape[0]) != n_items:
+                raise ValueError('LightFM: features for %d items, the training matrix has %d' % (features.shape[0], n_items))
+            a, F = warp.feature_weights(features)
+            Fc = F.tocsc()
+            Fc.sort_indices()
+            up = lambda x, dt: self.to_device(np.ascontiguousarray(x, dtype=dt))
+            plan['features'] = dict(n_labels=int(F.shape[1]), a=up(a, np.float64), row_ptr=up(F.indptr, np.int64),
+                                    row_idx=up(F.indices, np.int32), row_val=up(F.data, np.float64), col_ptr=up(Fc.indptr, np.int64),
+                                    col_idx=up(Fc.indices, np.int32), col_val=up(Fc.data, np.float64))
+        return plan
+
+    def _warp_check_plan(self, plan):
+        B = self._bpr_check_plan(plan)
+        f = plan.get('features', None)
+        if f is not None:
+            n_items = plan['shape'][1]
+            if (f['a'].numel() != n_items or f['row_ptr'].numel() != n_items + 1 or f['col_ptr'].numel() != f['n_labels'] + 1
+                    or f['row_idx'].numel() != f['row_val'].numel() or f['col_idx'].numel() != f['row_idx'].numel()
+                    or f['col_val'].numel() != f['row_idx'].numel()):
+                raise ValueError('LightFM: not a plan of warp_plan (item features)')
+        return B, f
+
+    def warp_draw(self, plan, seed, epoch, max_sampled):
+        """int32 [nnz x max_sampled] (device): the candidates of every position of the plan's schedule, -1 where the draw is an
+        item of the user's row (pk_warp_draw_candidates; the stream is spelled out in include/polara_hip.h)."""
+        B, _ = self._warp_check_plan(plan)
+        seed, epoch, D = int(seed), int(epoch), int(max_sampled)
+        if not (0 <= seed < 2 ** 32 and 0 <= epoch < 2 ** 32):
+            raise ValueError('LightFM: seed %d and epoch %d must fit 32 unsigned bits' % (seed, epoch))
+        if D < 1 or D > _lib.PK_WARP_MAX_SAMPLED:
+            raise ValueError('LightFM: max_sampled %d outside 1..%d' % (D, _lib.PK_WARP_MAX_SAMPLED))
+        n_users, n_items = plan['shape']
+        A, nnz = plan['matrix'], int(plan['nnz'])
+        cand = torch.empty(max(nnz, 1), D, dtype=torch.int32, device=self.device)[:nnz]
+        with self._timed('warp_draw', (nnz, D, B)):
+            _lib.check(self.lib.pk_warp_draw_candidates(self.stream(), nnz, n_users, n_items, B, D, _ptr(plan['users']),
+                                                        _ptr(plan['items']), _ptr(plan['perm']), _ptr(plan['item_order']),
+                                                        _ptr(plan['item_part']), _ptr(plan['item_ptr']), _ptr(A.indptr),
+                                                        _ptr(A.indices), seed, epoch, _ptr(cand)), 'pk_warp_draw_candidates')
+        return cand
+
+    def warp_label_image(self, plan, L):
+        """S = F_lab L [n_items x (k + 1)] in the storage-order sum of the sweep (pk_warp_label_image_f64)"""
+        _, f = self._warp_check_plan(plan)
+        if f is None:
+            raise ValueError('LightFM: the plan has no item features')
+        n_items = plan['shape'][1]
+        k = int(L.shape[1]) - 1
+        self._check_row_blocks('LightFM', (L,), (f['n_labels'],), k + 1)
+        S = self.empty(n_items, k + 1)
+        _lib.check(self.lib.pk_warp_label_image_f64(self.stream(), k, n_items, f['n_labels'], _ptr(f['row_ptr']), _ptr(f['row_idx']),
+                                                    _ptr(f['row_val']), _ptr(L), L.stride(0), _ptr(S), S.stride(0)),
+                   'pk_warp_label_image_f64')
+        return S
+
+    def warp_representation(self, plan, E, L=None):
+        """Q = a o E_id + F_lab E_lab (a copy of E_id without item features): every product and sum rounded on its own"""
+        if plan.get('features', None) is None:
+            return E.clone()
+        return E * plan['features']['a'][:, None] + self.warp_label_image(plan, L)
+
+    def warp_epoch(self, plan, cand, table, P, E, state, learning_rate, L=None, work=None):
+        """One WARP sweep over the plan's positives with the candidates `cand` and the loss table `table` (host, fp64
+        [max_sampled]) — pk_warp_epoch_f64: per stratum the sweep's launch and, with item features, one before it (the label
+        image) and one after (the label step); then the counters.  P [n_users x (k + 1)] (column k: the constant 1), E
+        [n_items x (k + 1)] and, with features, L [n_labels x (k + 1)] are updated in place, and so is state = (AP, AE, AL),
+        their adagrad state (AL None without features).  work = (S, G), two [n_items x (k + 1)] blocks (allocated here when
+        None; G is zero when the epoch ends).  Returns a device tensor of three int64: trained, quiet, draws."""
+        n_users, n_items = plan['shape']
+        k = int(P.shape[1]) - 1
+        if k < 1 or k > self.warp_max_rank():
+            raise ValueError('LightFM: rank %d outside 1..%d' % (k, self.warp_max_rank()))
+        B, f = self._warp_check_plan(plan)
+        if len(state) != 3:
+            raise ValueError('LightFM: state = (AP, AE, AL)')
+        AP, AE, AL = state
+        self._check_row_blocks('LightFM', (P, E, AP, AE), (n_users, n_items), k + 1)
+        nnz = int(plan['nnz'])
+        if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != nnz or not cand.is_contiguous():
+            raise ValueError('LightFM: the candidates must be int32 [%d x max_sampled] (warp_draw)' % nnz)
+        D = int(cand.shape[1])
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.shape != (D,) or D < 1 or D > _lib.PK_WARP_MAX_SAMPLED:
+            raise ValueError('LightFM: a loss table of shape %s for %d candidates per positive (1..%d)'
+                             % (table.shape, D, _lib.PK_WARP_MAX_SAMPLED))
+        table_dev = self.to_device(table)
+        n_labels, S, G = 0, None, None
+        names = ('a', 'row_ptr', 'row_idx', 'row_val', 'col_ptr', 'col_idx', 'col_val')
+        if f is not None:
+            n_labels = f['n_labels']
+            if L is None or AL is None:
+                raise ValueError('LightFM: item features need the label embeddings L and their state AL')
+            self._check_row_blocks('LightFM', (L, AL), (n_labels,), k + 1)
+            S, G = work if work is not None else (self.empty(n_items, k + 1), self.empty(n_items, k + 1))
+            self._check_row_blocks('LightFM', (S, G), (n_items,), k + 1)
+            feats = [_ptr(f[name]) for name in names]
+        else:
+            if L is not None:
+                raise ValueError('LightFM: label embeddings without item features in the plan')
+            L = AL = None
+            feats = [None] * len(names)
+        ld = lambda X: X.stride(0) if X is not None else 0
+        counters = self._work(self.lib.pk_warp_work_bytes(B))         # the counters of every block
+        out = torch.empty(3, dtype=torch.int64, device=self.device)
+        with self._timed('warp_epoch', (nnz, k, B, D, n_labels)):
+            _lib.check(self.lib.pk_warp_epoch_f64(self.stream(), B, k, nnz, n_items, n_labels, D, _ptr(plan['block_ptr']),
+                                                  _ptr(plan['users']), _ptr(plan['items']), _ptr(cand), _ptr(table_dev), _ptr(P),
+                                                  P.stride(0), _ptr(E), E.stride(0), _ptr(AP), AP.stride(0), _ptr(AE), AE.stride(0),
+                                                  float(learning_rate), *feats, _ptr(L), ld(L), _ptr(AL), ld(AL), _ptr(S), ld(S),
+                                                  _ptr(G), ld(G), _ptr(counters), _ptr(out)), 'pk_warp_epoch_f64')
+        return out
+
+    def warp_label_step(self, plan, G, L, AL, learning_rate):
+        """The label step alone (pk_warp_label_step_f64): every label's gradient summed from G over its items in ascending
+        order, one adagrad step on L with the state AL, and G cleared — all in place."""
+        _, f = self._warp_check_plan(plan)
+        if f is None:
+            raise ValueError('LightFM: the plan has no item features')
+        n_items = plan['shape'][1]
+        k = int(L.shape[1]) - 1
+        self._check_row_blocks('LightFM', (G,), (n_items,), k + 1)
+        self._check_row_blocks('LightFM', (L, AL), (f['n_labels'],), k + 1)
+        _lib.check(self.lib.pk_warp_label_step_f64(self.stream(), k, n_items, f['n_labels'], _ptr(f['col_ptr']), _ptr(f['col_idx']),
+                                                   _ptr(f['col_val']), _ptr(G), G.stride(0), _ptr(L), L.stride(0), _ptr(AL),
+                                                   AL.stride(0), float(learning_rate)), 'pk_warp_label_step_f64')
+
     # ---- Implicit ALS (csrc/ials.hip) ----------------------------------------------------------------------------------
     def ials_max_rank(self):
         return int(self.lib.pk_ials_max_rank())
