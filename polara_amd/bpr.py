@@ -58,6 +58,49 @@ def initial_factors(n_users, n_items, rank, seed=None):
     return P0, Q0
 
 
+def pairwise_fit(model, ops, matrix, limits, begin, num_epochs, seed, blocks, default_blocks, reshuffle_items, share, history,
+                 iter_time, comm):
+    """What bpr_fit and warp.warp_fit share: the driver of a pairwise model on the blocked schedule.  Refused under the name
+    `model`, in this order: several processes (before `matrix` is touched); every (what, value, most) of `limits` outside
+    1..most; the blocks (None: `default_blocks(nnz, n_users, n_items)`); the seed (None: one draw from NumPy's global generator).
+    Then `begin(blocks, seed)` makes the model's own checks and its device state and returns (state, plan_for, run_epoch):
+    plan_for(order) is the schedule along a host item order (None: the identity), run_epoch(plan, epoch) draws, sweeps and
+    returns the device tensor of the epoch's three counters.  An epoch is: the plan (once, or every epoch when
+    `reshuffle_items`), run_epoch, ONE host read of the counters; `history` receives share(counts), `iter_time` the span of all
+    that.  Returns (state, blocks, seed, the last plan or None, the time spent planning, the three counters as lists per epoch)."""
+    if comm is not None and getattr(comm, 'world', 1) > 1:
+        raise NotImplementedError('%s: multi-process builds are not supported (comm.world = %d)' % (model, comm.world))
+    n_users, n_items = (int(x) for x in matrix.shape)
+    for what, value, most in limits:
+        if value < 1 or value > most:
+            raise ValueError('%s: %s %d outside 1..%d' % (model, what, value, most))
+    if blocks is None:
+        blocks = default_blocks(matrix.nnz, n_users, n_items)
+    blocks = int(blocks)
+    if blocks < 1 or blocks > min(n_users, n_items):
+        raise ValueError('%s: %d blocks for %d users and %d items (1 .. min of the two)' % (model, blocks, n_users, n_items))
+    if seed is None:
+        seed = int(np.random.randint(0, 2 ** 32, dtype=np.uint64))
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError('%s: the seed %d does not fit 32 unsigned bits' % (model, seed))
+    state, plan_for, run_epoch = begin(blocks, seed)
+    plan, plan_time, totals = None, 0.0, ([], [], [])
+    for epoch in range(int(num_epochs)):
+        start = timer()
+        if plan is None or reshuffle_items:
+            plan = plan_for(item_order(seed, epoch, n_items) if reshuffle_items else None)
+            plan_time += timer() - start
+        counts = [int(c) for c in ops.to_host(run_epoch(plan, epoch))]         # the epoch's one host read
+        for total, count in zip(totals, counts):
+            total.append(count)
+        if history is not None:
+            history.append(share(counts))
+        if iter_time is not None:
+            iter_time.append(timer() - start)
+    return state, blocks, seed, plan, plan_time, totals
+
+
 def bpr_fit(ops, matrix, rank, learning_rate, regularization, num_epochs, seed=None, blocks=None, reshuffle_items=True, init=None,
             auc_history=None, iter_time=None, stats=None, comm=None):
     """`num_epochs` LearnBPR sweeps over the stored entries of the ops-level canonical CSR `matrix` [n_users x n_items] (its
@@ -65,43 +108,21 @@ def bpr_fit(ops, matrix, rank, learning_rate, regularization, num_epochs, seed=N
     global generator, reported in `stats`); it seeds the initial factors, the item orders and the negatives.  auc_history
     receives correct / trained of every epoch; stats the schedule's figures and trained / skipped samples per epoch.
     init = (P0, Q0) host arrays of k + 1 columns instead of the seeded draw."""
-    if comm is not None and getattr(comm, 'world', 1) > 1:
-        raise NotImplementedError('BPR: multi-process builds are not supported (comm.world = %d)' % comm.world)
-    n_users, n_items = (int(x) for x in matrix.shape)
     rank = int(rank)
-    if rank < 1 or rank > ops.bpr_max_rank():
-        raise ValueError('BPR: rank %d outside 1..%d' % (rank, ops.bpr_max_rank()))
-    if blocks is None:
-        blocks = default_blocks(matrix.nnz, n_users, n_items)
-    blocks = int(blocks)
-    if blocks < 1 or blocks > min(n_users, n_items):
-        raise ValueError('BPR: %d blocks for %d users and %d items (1 .. min of the two)' % (blocks, n_users, n_items))
-    if seed is None:
-        seed = int(np.random.randint(0, 2 ** 32, dtype=np.uint64))
-    seed = int(seed)
-    if not 0 <= seed < 2 ** 32:
-        raise ValueError('BPR: the seed %d does not fit 32 unsigned bits' % seed)
-    if init is None:
-        init = initial_factors(n_users, n_items, rank, seed)
-    P0, Q0 = (np.asarray(a, dtype=np.float64) for a in init)
-    if P0.shape != (n_users, rank + 1) or Q0.shape != (n_items, rank + 1):
-        raise ValueError('BPR: initial factors of shapes %s, %s for (%d x %d), (%d x %d)'
-                         % (P0.shape, Q0.shape, n_users, rank + 1, n_items, rank + 1))
-    P, Q = ops.to_device(np.ascontiguousarray(P0)), ops.to_device(np.ascontiguousarray(Q0))
-    plan, plan_time, trained, skipped = None, 0.0, [], []
-    for epoch in range(int(num_epochs)):
-        start = timer()
-        if plan is None or reshuffle_items:
-            plan = ops.bpr_plan(matrix, blocks, item_order(seed, epoch, n_items) if reshuffle_items else None)
-            plan_time += timer() - start
-        neg = ops.bpr_draw_negatives(plan, seed, epoch)
-        counts = [int(c) for c in ops.to_host(ops.bpr_epoch(plan, neg, P, Q, learning_rate, regularization))]   # the epoch's one host read
-        trained.append(counts[0])
-        skipped.append(counts[1])
-        if auc_history is not None:
-            auc_history.append(counts[2] / counts[0] if counts[0] else float('nan'))
-        if iter_time is not None:
-            iter_time.append(timer() - start)
+
+    def begin(blocks, seed):
+        n_users, n_items = (int(x) for x in matrix.shape)
+        P0, Q0 = (np.asarray(a, dtype=np.float64) for a in (initial_factors(n_users, n_items, rank, seed) if init is None else init))
+        if P0.shape != (n_users, rank + 1) or Q0.shape != (n_items, rank + 1):
+            raise ValueError('BPR: initial factors of shapes %s, %s for (%d x %d), (%d x %d)'
+                             % (P0.shape, Q0.shape, n_users, rank + 1, n_items, rank + 1))
+        P, Q = ops.to_device(np.ascontiguousarray(P0)), ops.to_device(np.ascontiguousarray(Q0))
+        return ((P, Q), lambda order: ops.bpr_plan(matrix, blocks, order),
+                lambda plan, epoch: ops.bpr_epoch(plan, ops.bpr_draw_negatives(plan, seed, epoch), P, Q, learning_rate, regularization))
+
+    (P, Q), blocks, seed, _, plan_time, (trained, skipped, _) = pairwise_fit(
+        'BPR', ops, matrix, [('rank', rank, ops.bpr_max_rank())], begin, num_epochs, seed, blocks, default_blocks, reshuffle_items,
+        lambda counts: counts[2] / counts[0] if counts[0] else float('nan'), auc_history, iter_time, comm)
     if stats is not None:
         stats.update(blocks=blocks, strata=blocks, launches_per_epoch=blocks + 2, reshuffle_items=bool(reshuffle_items), seed=seed,
                      epochs=len(trained), plan_time=plan_time, trained=trained, skipped=skipped)
@@ -143,9 +164,6 @@ class ImplicitBPR(FactorQueriesMixin, RecommenderModel):
     def seed(self, value):
         self.random_state = value
 
-    def _clean_metadata(self):
-        self._factors_dev = None
-
     def _check_serving(self):
         if self.data.warm_start:
             raise NotImplementedError('%s has no fold-in: BPR cannot serve warm-start users (the reference\'s wrapper asks the '
@@ -166,7 +184,4 @@ class ImplicitBPR(FactorQueriesMixin, RecommenderModel):
         ops.synchronize()
         self._track(start)
         self.build_stats = stats
-        userid, itemid = self.data.fields.userid, self.data.fields.itemid
-        self.factors = {userid: ops.to_host(P), itemid: ops.to_host(Q)}
-        self._factors_dev = (self.factors[userid], P)
-        self._set_item_serving_index(Q)
+        self._set_factors(P, Q)

@@ -1,8 +1,9 @@
-// The skeleton of the blocked SGD sweeps (pmf.hip, kpmf.hip, bpr.hip), once: a lane group's block and the wave's longest one,
-// the halving tree of the dot, the 16 / 32 / 64 width rule, the stratum loop of an epoch and the argument checks of its entry;
-// and what the two PMF sweeps share beyond that: the arguments of a stratum launch, the gradient adjusters, the body of a
+// The skeleton of the blocked SGD sweeps (pmf.hip, kpmf.hip, bpr.hip, warp.hip), once: a lane group's block and the wave's
+// longest one, the halving tree of the dot, the 16 / 32 / 64 width rule, the stratum loop of an epoch and the argument checks of
+// its entry; what the two PMF sweeps share beyond that: the arguments of a stratum launch, the gradient adjusters, the body of a
 // sample (pmf_stratum_kernel, with the kernelized pieces of kpmf.hip behind `if constexpr`) and the launch of the squared
-// error's reduction (defined once, in pmf.hip).
+// error's reduction (defined once, in pmf.hip); and what the two pairwise sweeps share: the block counters with the launch of
+// their reduction (defined once, in bpr.hip) and the pieces of a draw inside an item part.
 //
 // Include this AFTER `#pragma clang fp contract(off)`: every sweep switches contraction off for its whole translation unit,
 // and what is compiled from here must round every product and sum on its own too.
@@ -250,3 +251,56 @@ static int pmf_launch(hipStream_t st, int adjust, unsigned grid, const Args &a, 
 
 // block sums -> stratum sums (block order) -> the epoch's sum (stratum order): pmf_sse_kernel of pmf.hip on `st`, checked
 int pmf_launch_sse(hipStream_t st, int blocks, const double *block_sse_dev, double *sse_dev);
+
+// ---- the pairwise sweeps (bpr.hip, warp.hip) --------------------------------------------------------------------------------
+// A sample is a stored positive and items drawn inside the positive's own item part.  Shared: the three counters every block
+// keeps and their reduction, and the pieces of a draw.  Each model's draw kernel keeps its own thread mapping, its own counter
+// stride per position and its own treatment of the answer.
+
+// bytes of an epoch's work buffer: the [3][B * B] counters of every block
+static inline int64_t pair_work_bytes(int32_t blocks) {
+    const int64_t b = blocks < 1 ? 1 : blocks;
+    return 3 * b * b * (int64_t)sizeof(int64_t);
+}
+
+// (A block's three stores into that buffer stay spelled out at the end of each stratum kernel: behind a helper the compiler
+// orders them differently, and the kernels' instruction streams are kept equal to what was measured.)
+
+// block counts -> stratum counts (block order) -> the epoch's three counts (stratum order): pair_counts_kernel of bpr.hip on
+// `st`, checked
+int pair_launch_counts(hipStream_t st, int blocks, const int64_t *block_counts_dev, int64_t *counts_dev);
+
+// the key of an epoch's draw stream: mix64(seed * 2^32 + epoch)
+static inline uint64_t pair_stream_key(uint32_t seed, uint32_t epoch) { return pk_mix64(((uint64_t)seed << 32) + (uint64_t)epoch); }
+
+// the item the 32-bit draw w picks among the n_c items of the part that starts at item_order[lo_c]
+__device__ __forceinline__ int32_t pair_draw_in_part(const int32_t *item_order, int64_t lo_c, uint64_t n_c, uint64_t w) {
+    return item_order[lo_c + (int64_t)((w * n_c) >> 32)];
+}
+
+// whether the sorted row indices[r0 .. r1) holds item j: its lower bound
+__device__ __forceinline__ bool pair_row_holds(const int32_t *indices, int64_t r0, int64_t r1, int32_t j) {
+    int64_t lo = r0, hi = r1;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (indices[mid] < j)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo < r1 && indices[lo] == j;
+}
+
+// The checks both draw entries make, in their order and under the entry's name; `draws` per position between the blocks and the
+// pointers (BPR's are fixed, WARP's are its max_sampled).  `parts`: the plan's and the matrix's pointers, `samples`: the arrays
+// that are there when nnz > 0.
+static inline int pair_draw_check(const char *entry, int64_t nnz, int64_t n_users, int64_t n_items, int blocks, int draws,
+                                  int max_draws, bool parts, bool samples) {
+    PK_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31) && n_users >= 1 && n_items >= 1 && n_items < ((int64_t)1 << 31), "%s: bad sizes",
+               entry);
+    PK_REQUIRE(blocks >= 1 && blocks <= PK_PMF_MAX_BLOCKS, "%s: %d blocks outside 1..%d", entry, blocks, PK_PMF_MAX_BLOCKS);
+    PK_REQUIRE(draws >= 1 && draws <= max_draws, "%s: max_sampled %d outside 1..%d", entry, draws, max_draws);
+    PK_REQUIRE(parts, "%s: bad pointers", entry);
+    PK_REQUIRE(samples, "%s: no interactions given", entry);
+    return PK_OK;
+}

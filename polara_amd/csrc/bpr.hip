@@ -75,17 +75,8 @@ __global__ __launch_bounds__(256) void bpr_draw_kernel(int64_t nnz, const int32_
     const uint64_t base = key + 4ull * (uint64_t)perm[p];
     int32_t found = -1;
     for (int t = 0; t < PK_BPR_DRAWS && found < 0; ++t) {
-        const uint64_t w = pk_mix64(base + (uint64_t)t) >> 32;
-        const int32_t j = item_order[lo_c + (int64_t)((w * n_c) >> 32)];
-        int64_t lo = r0, hi = r1;                                 // lower bound of j in the user's sorted row
-        while (lo < hi) {
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            if (indices[mid] < j)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        if (!(lo < r1 && indices[lo] == j)) found = j;
+        const int32_t j = pair_draw_in_part(item_order, lo_c, n_c, pk_mix64(base + (uint64_t)t) >> 32);
+        if (!pair_row_holds(indices, r0, r1, j)) found = j;
     }
     neg[p] = found;
 }
@@ -95,15 +86,14 @@ extern "C" int pk_bpr_draw_negatives(void *stream, int64_t nnz, int64_t n_users,
                                      const int32_t *item_order_dev, const int32_t *item_part_dev, const int64_t *item_ptr_dev,
                                      const int64_t *indptr_dev, const int32_t *indices_dev, uint32_t seed, uint32_t epoch,
                                      int32_t *neg_dev) {
-    PK_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31) && n_users >= 1 && n_items >= 1 && n_items < ((int64_t)1 << 31),
-               "pk_bpr_draw_negatives: bad sizes");
-    PK_REQUIRE(blocks >= 1 && blocks <= PK_PMF_MAX_BLOCKS, "pk_bpr_draw_negatives: %d blocks outside 1..%d", (int)blocks, PK_PMF_MAX_BLOCKS);
-    PK_REQUIRE(item_order_dev && item_part_dev && item_ptr_dev && indptr_dev, "pk_bpr_draw_negatives: bad pointers");
-    PK_REQUIRE(nnz == 0 || (users_dev && items_dev && perm_dev && indices_dev && neg_dev), "pk_bpr_draw_negatives: no interactions given");
+    const int rc = pair_draw_check("pk_bpr_draw_negatives", nnz, n_users, n_items, blocks, PK_BPR_DRAWS, PK_BPR_DRAWS,
+                                   item_order_dev && item_part_dev && item_ptr_dev && indptr_dev,
+                                   nnz == 0 || (users_dev && items_dev && perm_dev && indices_dev && neg_dev));
+    if (rc != PK_OK) return rc;
     if (nnz == 0) return PK_OK;
-    const uint64_t key = pk_mix64(((uint64_t)seed << 32) + (uint64_t)epoch);
     hipLaunchKernelGGL(bpr_draw_kernel, dim3((unsigned)pk_ceil_div(nnz, 256)), dim3(256), 0, pk_stream(stream), nnz, users_dev, items_dev,
-                       perm_dev, item_order_dev, item_part_dev, item_ptr_dev, indptr_dev, indices_dev, key, neg_dev);
+                       perm_dev, item_order_dev, item_part_dev, item_ptr_dev, indptr_dev, indices_dev, pair_stream_key(seed, epoch),
+                       neg_dev);
     PK_CHECK_LAUNCH("bpr_draw_kernel");
     return PK_OK;
 }
@@ -186,8 +176,9 @@ __global__ __launch_bounds__(BPR_THREADS) void bpr_stratum_kernel(BprArgs a, int
     }
 }
 
-// block counts -> stratum counts (block order) -> the epoch's counts (stratum order): integers, fixed order, no atomics
-__global__ __launch_bounds__(256) void bpr_counts_kernel(int B, const int64_t *__restrict__ counts, int64_t *__restrict__ out) {
+// block counts -> stratum counts (block order) -> the epoch's counts (stratum order): integers, fixed order, no atomics; the
+// pairwise sweeps' one reduction (pair_launch_counts of blocked_sweep.h)
+__global__ __launch_bounds__(256) void pair_counts_kernel(int B, const int64_t *__restrict__ counts, int64_t *__restrict__ out) {
     __shared__ int64_t stratum_counts[PK_PMF_MAX_BLOCKS];
     const int64_t BB = (int64_t)B * B;
     for (int q = 0; q < 3; ++q) {
@@ -206,11 +197,14 @@ __global__ __launch_bounds__(256) void bpr_counts_kernel(int B, const int64_t *_
     }
 }
 
-extern "C" int32_t pk_bpr_max_rank(void) { return BPR_MAX_RANK; }
-extern "C" int64_t pk_bpr_work_bytes(int32_t blocks) {
-    const int64_t b = blocks < 1 ? 1 : blocks;
-    return 3 * b * b * (int64_t)sizeof(int64_t);
+int pair_launch_counts(hipStream_t st, int blocks, const int64_t *block_counts_dev, int64_t *counts_dev) {
+    hipLaunchKernelGGL(pair_counts_kernel, dim3(1), dim3(256), 0, st, blocks, block_counts_dev, counts_dev);
+    PK_CHECK_LAUNCH("pair_counts_kernel");
+    return PK_OK;
 }
+
+extern "C" int32_t pk_bpr_max_rank(void) { return BPR_MAX_RANK; }
+extern "C" int64_t pk_bpr_work_bytes(int32_t blocks) { return pair_work_bytes(blocks); }
 
 extern "C" int pk_bpr_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, const int64_t *block_ptr_dev,
                                 const int32_t *users_dev, const int32_t *items_dev, const int32_t *neg_dev, double *P_dev, int64_t ldp,
@@ -234,15 +228,11 @@ extern "C" int pk_bpr_epoch_f64(void *stream, int32_t blocks, int32_t rank, int6
             PK_CHECK_LAUNCH("bpr_stratum_kernel");
             return PK_OK;
         },
-        [&]() -> int {
-            hipLaunchKernelGGL(bpr_counts_kernel, dim3(1), dim3(256), 0, st, (int)blocks, (const int64_t *)work_dev, counts_dev);
-            PK_CHECK_LAUNCH("bpr_counts_kernel");
-            return PK_OK;
-        });
+        [&] { return pair_launch_counts(st, (int)blocks, (const int64_t *)work_dev, counts_dev); });
 }
 
 // eager load of this translation unit's code object (pk_warm_up, api.cpp)
 hipError_t pk_tu_load_bpr() {
     hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&bpr_counts_kernel));
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&pair_counts_kernel));
 }

@@ -33,17 +33,8 @@ __global__ __launch_bounds__(256) void warp_draw_kernel(int64_t total, int D, co
     const int64_t lo_c = item_ptr[c];
     const uint64_t n_c = (uint64_t)(item_ptr[c + 1] - lo_c);
     const int64_t r1 = indptr[u + 1];
-    const uint64_t w = pk_mix64(key + 64ull * (uint64_t)perm[p] + (uint64_t)t) >> 32;
-    const int32_t j = item_order[lo_c + (int64_t)((w * n_c) >> 32)];
-    int64_t lo = indptr[u], hi = r1;                              // lower bound of j in the user's sorted row
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (indices[mid] < j)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    cand[x] = (lo < r1 && indices[lo] == j) ? -1 : j;
+    const int32_t j = pair_draw_in_part(item_order, lo_c, n_c, pk_mix64(key + 64ull * (uint64_t)perm[p] + (uint64_t)t) >> 32);
+    cand[x] = pair_row_holds(indices, indptr[u], r1, j) ? -1 : j;
 }
 
 extern "C" int pk_warp_draw_candidates(void *stream, int64_t nnz, int64_t n_users, int64_t n_items, int32_t blocks, int32_t max_sampled,
@@ -51,19 +42,15 @@ extern "C" int pk_warp_draw_candidates(void *stream, int64_t nnz, int64_t n_user
                                        const int32_t *item_order_dev, const int32_t *item_part_dev, const int64_t *item_ptr_dev,
                                        const int64_t *indptr_dev, const int32_t *indices_dev, uint32_t seed, uint32_t epoch,
                                        int32_t *cand_dev) {
-    PK_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31) && n_users >= 1 && n_items >= 1 && n_items < ((int64_t)1 << 31),
-               "pk_warp_draw_candidates: bad sizes");
-    PK_REQUIRE(blocks >= 1 && blocks <= PK_PMF_MAX_BLOCKS, "pk_warp_draw_candidates: %d blocks outside 1..%d", (int)blocks,
-               PK_PMF_MAX_BLOCKS);
-    PK_REQUIRE(max_sampled >= 1 && max_sampled <= PK_WARP_MAX_SAMPLED, "pk_warp_draw_candidates: max_sampled %d outside 1..%d",
-               (int)max_sampled, PK_WARP_MAX_SAMPLED);
-    PK_REQUIRE(item_order_dev && item_part_dev && item_ptr_dev && indptr_dev, "pk_warp_draw_candidates: bad pointers");
-    PK_REQUIRE(nnz == 0 || (users_dev && items_dev && perm_dev && indices_dev && cand_dev), "pk_warp_draw_candidates: no interactions given");
+    const int rc = pair_draw_check("pk_warp_draw_candidates", nnz, n_users, n_items, blocks, max_sampled, PK_WARP_MAX_SAMPLED,
+                                   item_order_dev && item_part_dev && item_ptr_dev && indptr_dev,
+                                   nnz == 0 || (users_dev && items_dev && perm_dev && indices_dev && cand_dev));
+    if (rc != PK_OK) return rc;
     if (nnz == 0) return PK_OK;
-    const uint64_t key = pk_mix64(((uint64_t)seed << 32) + (uint64_t)epoch);
     const int64_t total = nnz * max_sampled;
     hipLaunchKernelGGL(warp_draw_kernel, dim3((unsigned)pk_ceil_div(total, 256)), dim3(256), 0, pk_stream(stream), total, (int)max_sampled,
-                       users_dev, items_dev, perm_dev, item_order_dev, item_part_dev, item_ptr_dev, indptr_dev, indices_dev, key, cand_dev);
+                       users_dev, items_dev, perm_dev, item_order_dev, item_part_dev, item_ptr_dev, indptr_dev, indices_dev,
+                       pair_stream_key(seed, epoch), cand_dev);
     PK_CHECK_LAUNCH("warp_draw_kernel");
     return PK_OK;
 }
@@ -311,31 +298,8 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_stratum_kernel(WarpArgs a, 
     }
 }
 
-// block counts -> stratum counts (block order) -> the epoch's counts (stratum order): integers, fixed order, no atomics
-__global__ __launch_bounds__(256) void warp_counts_kernel(int B, const int64_t *__restrict__ counts, int64_t *__restrict__ out) {
-    __shared__ int64_t stratum_counts[PK_PMF_MAX_BLOCKS];
-    const int64_t BB = (int64_t)B * B;
-    for (int q = 0; q < 3; ++q) {
-        for (int s = threadIdx.x; s < B; s += 256) {
-            int64_t acc = 0;
-            for (int b = 0; b < B; ++b) acc += counts[q * BB + (int64_t)s * B + b];
-            stratum_counts[s] = acc;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int64_t total = 0;
-            for (int s = 0; s < B; ++s) total += stratum_counts[s];
-            out[q] = total;
-        }
-        __syncthreads();
-    }
-}
-
 extern "C" int32_t pk_warp_max_rank(void) { return WARP_MAX_RANK; }
-extern "C" int64_t pk_warp_work_bytes(int32_t blocks) {
-    const int64_t b = blocks < 1 ? 1 : blocks;
-    return 3 * b * b * (int64_t)sizeof(int64_t);
-}
+extern "C" int64_t pk_warp_work_bytes(int32_t blocks) { return pair_work_bytes(blocks); }
 
 extern "C" int pk_warp_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, int64_t n_items, int64_t n_labels,
                                  int32_t max_sampled, const int64_t *block_ptr_dev, const int32_t *users_dev, const int32_t *items_dev,
@@ -398,14 +362,12 @@ extern "C" int pk_warp_epoch_f64(void *stream, int32_t blocks, int32_t rank, int
                 const int zrc = warp_launch_zero(st, f, cols);                     // G is zero when the epoch ends
                 if (zrc != PK_OK) return zrc;
             }
-            hipLaunchKernelGGL(warp_counts_kernel, dim3(1), dim3(256), 0, st, (int)blocks, (const int64_t *)work_dev, counts_dev);
-            PK_CHECK_LAUNCH("warp_counts_kernel");
-            return PK_OK;
+            return pair_launch_counts(st, (int)blocks, (const int64_t *)work_dev, counts_dev);
         });
 }
 
 // eager load of this translation unit's code object (pk_warm_up, api.cpp)
 hipError_t pk_tu_load_warp() {
     hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&warp_counts_kernel));
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&warp_zero_kernel));
 }

@@ -1,8 +1,9 @@
-"""Serving for models that carry explicit user factors (ProbabilisticMF, ImplicitALS, LCEModel): the rows of the user factors
-go into the scoring pass as ready-made queries (`scoring.recommend(queries=...)`), and `slice_recommendations` is the dense
-product of those rows with the item factors.  The model provides `_rank`, `factors` ({userid: host array, itemid: host
-array}), `_factors_dev` ((host user factors, their device copy, then what `_extra_factors_device` names) or None),
-`_item_inv` and the item image of `_item_factors_device`."""
+"""Serving for models that carry explicit user factors (ProbabilisticMF, ImplicitALS, ImplicitBPR, LCEModel, LightFMWrapper):
+the rows of the user factors go into the scoring pass as ready-made queries (`scoring.recommend(queries=...)`), and
+`slice_recommendations` is the dense product of those rows with the item factors.  A build ends with `_set_factors`, which
+leaves `factors` ({userid: host array, itemid: host array, ...}), `_factors_dev` ((host user factors, their device copy, then
+what `_extra_factors_device` names) or None), `_item_inv` and the item image of `_item_factors_device`; the model provides
+`_rank`."""
 import numpy as np
 
 from . import scoring
@@ -25,6 +26,20 @@ class FactorQueriesMixin:
     def _training_device_csr(self):
         """what these models factorise: the training matrix in the data's own item order"""
         return self._data_order_training_csr()
+
+    def _clean_metadata(self):
+        """the data changed (every model subscribes this in its `__init__`): what the last build left on the device is stale"""
+        self._factors_dev = None
+
+    def _set_factors(self, P, Q, kept=(), **named):
+        """The tail of a build from the device blocks P (users) and Q (items, the data's item order): `factors` on the host —
+        with f'{itemid}_{name}' for every further device block `named` —, `_factors_dev` with the blocks `kept` on the device
+        behind P (what `_extra_factors_device` uploads again), and the serving index over Q."""
+        userid, itemid = self.data.fields.userid, self.data.fields.itemid
+        to_host = self.ops.to_host
+        self.factors = {userid: to_host(P), itemid: to_host(Q), **{f'{itemid}_{name}': to_host(X) for name, X in named.items()}}
+        self._factors_dev = (self.factors[userid], P, *kept)
+        self._set_item_serving_index(Q)
 
     def _extra_factors_device(self):
         """uploads of further `factors` that stay on the device with the user factors (the tail of `_factors_dev`)"""

@@ -88,7 +88,7 @@ class ImplicitALS(FactorQueriesMixin, RecommenderModel):
         self.data.subscribe(self.data.on_change_event, self._clean_metadata)
 
     def _clean_metadata(self):
-        self._factors_dev = None
+        super()._clean_metadata()
         self._items_dev = None
 
     @staticmethod
@@ -127,11 +127,8 @@ class ImplicitALS(FactorQueriesMixin, RecommenderModel):
                         iter_time=self.iterations_time)
         ops.synchronize()
         self._track(start)
-        userid, itemid = self.data.fields.userid, self.data.fields.itemid
-        self.factors = {userid: ops.to_host(X), itemid: ops.to_host(Y)}
-        self._factors_dev = (self.factors[userid], X)
-        self._items_dev = (self.factors[itemid], Y, None)
-        self._set_item_serving_index(Y)
+        self._set_factors(X, Y)
+        self._items_dev = (self.factors[self.data.fields.itemid], Y, None)
 
     # ---- warm start: the fold-in ----------------------------------------------------------------------------------------
     def _item_factors_block(self):

@@ -169,8 +169,8 @@ class LCEModel(FactorQueriesMixin, RecommenderModel):
         self.data.subscribe(self.data.on_change_event, self._clean_metadata)
 
     def _clean_metadata(self):
+        super()._clean_metadata()
         self.item_features_labels = None
-        self._factors_dev = None
 
     def encode_item_features(self):
         """The one-hot matrix of the (training) items in the model's item order [n_items x n_labels] (SciPy CSR); a data
@@ -228,10 +228,7 @@ class LCEModel(FactorQueriesMixin, RecommenderModel):
         ops.synchronize()
         self._track(start)
         self.build_stats = stats
-        userid, itemid = self.data.fields.userid, self.data.fields.itemid
-        self.factors = {userid: ops.to_host(HuT), itemid: ops.to_host(W), f'{itemid}_features': ops.to_host(HsT)}
-        self._factors_dev = (self.factors[userid], HuT, HsT)
-        self._set_item_serving_index(W)
+        self._set_factors(HuT, W, kept=(HsT,), features=HsT)
 
     def _extra_factors_device(self):
         HsT = self.factors[f'{self.data.fields.itemid}_features']

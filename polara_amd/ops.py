@@ -2282,31 +2282,41 @@ class HipOps:
         return self._check_plan(plan, 'BPR', items=('item_order', 'item_part'), entries=('users', 'items', 'perm'),
                                 item_ptr=int(plan['blocks']) + 1)
 
+    def _pair_draw(self, what, name, entry, B, plan, seed, epoch, draws=()):
+        """bpr_draw_negatives and warp_draw (`name`) behind their plan checks: seed and epoch checked under the model's name
+        `what`, the int32 output [nnz (x draws)] allocated, then `entry` with `draws` in its place among the arguments both take"""
+        seed, epoch = int(seed), int(epoch)
+        if not (0 <= seed < 2 ** 32 and 0 <= epoch < 2 ** 32):
+            raise ValueError('%s: seed %d and epoch %d must fit 32 unsigned bits' % (what, seed, epoch))
+        n_users, n_items = plan['shape']
+        A, nnz = plan['matrix'], int(plan['nnz'])
+        out = torch.empty(max(nnz, 1), *draws, dtype=torch.int32, device=self.device)[:nnz]
+        with self._timed(name, (nnz, *draws, B)):
+            _lib.check(getattr(self.lib, entry)(
+                self.stream(), nnz, n_users, n_items, B, *draws, _ptr(plan['users']), _ptr(plan['items']), _ptr(plan['perm']),
+                _ptr(plan['item_order']), _ptr(plan['item_part']), _ptr(plan['item_ptr']), _ptr(A.indptr), _ptr(A.indices), seed, epoch,
+                _ptr(out)), entry)
+        return out
+
+    @staticmethod
+    def _rank_of_columns(what, P, max_rank):
+        """k of a block of k + 1 columns (the pairwise sweeps' [P | 1]), in range under the model's name `what`"""
+        k = int(P.shape[1]) - 1
+        if k < 1 or k > max_rank:
+            raise ValueError('%s: rank %d outside 1..%d' % (what, k, max_rank))
+        return k
+
     def bpr_draw_negatives(self, plan, seed, epoch):
         """int32 [nnz] (device): the negative of every position of the plan's schedule, -1 where all PK_BPR_DRAWS draws were
         seen items (pk_bpr_draw_negatives; the stream is spelled out in include/polara_hip.h)."""
-        B = self._bpr_check_plan(plan)
-        seed, epoch = int(seed), int(epoch)
-        if not (0 <= seed < 2 ** 32 and 0 <= epoch < 2 ** 32):
-            raise ValueError('BPR: seed %d and epoch %d must fit 32 unsigned bits' % (seed, epoch))
-        n_users, n_items = plan['shape']
-        A, nnz = plan['matrix'], int(plan['nnz'])
-        neg = torch.empty(max(nnz, 1), dtype=torch.int32, device=self.device)[:nnz]
-        with self._timed('bpr_draw_negatives', (nnz, B)):
-            _lib.check(self.lib.pk_bpr_draw_negatives(self.stream(), nnz, n_users, n_items, B, _ptr(plan['users']), _ptr(plan['items']),
-                                                      _ptr(plan['perm']), _ptr(plan['item_order']), _ptr(plan['item_part']),
-                                                      _ptr(plan['item_ptr']), _ptr(A.indptr), _ptr(A.indices), seed, epoch, _ptr(neg)),
-                       'pk_bpr_draw_negatives')
-        return neg
+        return self._pair_draw('BPR', 'bpr_draw_negatives', 'pk_bpr_draw_negatives', self._bpr_check_plan(plan), plan, seed, epoch)
 
     def bpr_epoch(self, plan, neg, P, Q, learning_rate, regularization):
         """One LearnBPR sweep over the plan's positives with the negatives `neg` (pk_bpr_epoch_f64: one launch per stratum and
         one for the counters), P [n_users x (k + 1)] (column k: the constant 1) and Q [n_items x (k + 1)] (column k: the bias)
         updated in place.  Returns a device tensor of three int64: trained, skipped, correct."""
         n_users, n_items = plan['shape']
-        k = int(P.shape[1]) - 1
-        if k < 1 or k > self.bpr_max_rank():
-            raise ValueError('BPR: rank %d outside 1..%d' % (k, self.bpr_max_rank()))
+        k = self._rank_of_columns('BPR', P, self.bpr_max_rank())
         self._check_row_blocks('BPR', (P, Q), (n_users, n_items), k + 1)
         B = self._bpr_check_plan(plan)
         if neg.dtype != torch.int32 or neg.dim() != 1 or neg.numel() != plan['nnz'] or (neg.numel() and neg.stride(0) != 1):
@@ -2367,20 +2377,10 @@ class HipOps:
         """int32 [nnz x max_sampled] (device): the candidates of every position of the plan's schedule, -1 where the draw is an
         item of the user's row (pk_warp_draw_candidates; the stream is spelled out in include/polara_hip.h)."""
         B, _ = self._warp_check_plan(plan)
-        seed, epoch, D = int(seed), int(epoch), int(max_sampled)
-        if not (0 <= seed < 2 ** 32 and 0 <= epoch < 2 ** 32):
-            raise ValueError('LightFM: seed %d and epoch %d must fit 32 unsigned bits' % (seed, epoch))
+        D = int(max_sampled)
         if D < 1 or D > _lib.PK_WARP_MAX_SAMPLED:
             raise ValueError('LightFM: max_sampled %d outside 1..%d' % (D, _lib.PK_WARP_MAX_SAMPLED))
-        n_users, n_items = plan['shape']
-        A, nnz = plan['matrix'], int(plan['nnz'])
-        cand = torch.empty(max(nnz, 1), D, dtype=torch.int32, device=self.device)[:nnz]
-        with self._timed('warp_draw', (nnz, D, B)):
-            _lib.check(self.lib.pk_warp_draw_candidates(self.stream(), nnz, n_users, n_items, B, D, _ptr(plan['users']),
-                                                        _ptr(plan['items']), _ptr(plan['perm']), _ptr(plan['item_order']),
-                                                        _ptr(plan['item_part']), _ptr(plan['item_ptr']), _ptr(A.indptr),
-                                                        _ptr(A.indices), seed, epoch, _ptr(cand)), 'pk_warp_draw_candidates')
-        return cand
+        return self._pair_draw('LightFM', 'warp_draw', 'pk_warp_draw_candidates', B, plan, seed, epoch, (D,))
 
     def warp_label_image(self, plan, L):
         """S = F_lab L [n_items x (k + 1)] in the storage-order sum of the sweep (pk_warp_label_image_f64)"""
@@ -2410,9 +2410,7 @@ class HipOps:
         their adagrad state (AL None without features).  work = (S, G), two [n_items x (k + 1)] blocks (allocated here when
         None; G is zero when the epoch ends).  Returns a device tensor of three int64: trained, quiet, draws."""
         n_users, n_items = plan['shape']
-        k = int(P.shape[1]) - 1
-        if k < 1 or k > self.warp_max_rank():
-            raise ValueError('LightFM: rank %d outside 1..%d' % (k, self.warp_max_rank()))
+        k = self._rank_of_columns('LightFM', P, self.warp_max_rank())
         B, f = self._warp_check_plan(plan)
         if len(state) != 3:
             raise ValueError('LightFM: state = (AP, AE, AL)')

@@ -212,9 +212,6 @@ class ProbabilisticMF(FactorQueriesMixin, RecommenderModel):
         self._factors_dev = None            # (host user factors of `factors`, P on the device) of the last build
         self.data.subscribe(self.data.on_change_event, self._clean_metadata)
 
-    def _clean_metadata(self):
-        self._factors_dev = None
-
     _device_optimizer = staticmethod(pmf_sgd)
 
     def _solve(self, ops, train, **config):
@@ -240,7 +237,4 @@ class ProbabilisticMF(FactorQueriesMixin, RecommenderModel):
         ops.synchronize()
         self._track(start)
         self.build_stats = stats
-        userid, itemid = self.data.fields.userid, self.data.fields.itemid
-        self.factors = {userid: ops.to_host(P), itemid: ops.to_host(Q)}
-        self._factors_dev = (self.factors[userid], P)
-        self._set_item_serving_index(Q)
+        self._set_factors(P, Q)

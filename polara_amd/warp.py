@@ -81,59 +81,35 @@ def warp_fit(ops, matrix, rank, learning_rate, max_sampled, num_epochs, seed=Non
     Q) of k + 1 columns (E_lab None without features).  seed: 32 unsigned bits; it seeds the initial embeddings, the item orders
     and the candidates.  history receives quiet / positives of every epoch.  init = (P0, E_id0, E_lab0) host arrays instead of
     the seeded draw.  The adagrad state starts at 1 and is kept over the epochs."""
-    if comm is not None and getattr(comm, 'world', 1) > 1:
-        raise NotImplementedError('LightFM: multi-process builds are not supported (comm.world = %d)' % comm.world)
-    n_users, n_items = (int(x) for x in matrix.shape)
     rank, D = int(rank), int(max_sampled)
-    if rank < 1 or rank > ops.warp_max_rank():
-        raise ValueError('LightFM: rank %d outside 1..%d' % (rank, ops.warp_max_rank()))
-    if D < 1 or D > MAX_SAMPLED:
-        raise ValueError('LightFM: max_sampled %d outside 1..%d' % (D, MAX_SAMPLED))
-    if blocks is None:
-        blocks = default_blocks(matrix.nnz, n_users, n_items)
-    blocks = int(blocks)
-    if blocks < 1 or blocks > min(n_users, n_items):
-        raise ValueError('LightFM: %d blocks for %d users and %d items (1 .. min of the two)' % (blocks, n_users, n_items))
-    if seed is None:
-        seed = int(np.random.randint(0, 2 ** 32, dtype=np.uint64))
-    seed = int(seed)
-    if not 0 <= seed < 2 ** 32:
-        raise ValueError('LightFM: the seed %d does not fit 32 unsigned bits' % seed)
-    n_labels = 0
-    if item_features is not None:
-        if int(item_features.shape[0]) != n_items:
-            raise ValueError('LightFM: features for %d items, the training matrix has %d' % (item_features.shape[0], n_items))
-        n_labels = int(item_features.shape[1])
-    candidate_bytes = int(matrix.nnz) * D * 4
-    if hasattr(ops, 'free_bytes') and candidate_bytes > ops.free_bytes() / 2:
-        raise MemoryError('LightFM: the candidates of an epoch (%d positives x %d draws) need %d bytes (%.2f GB), more than half '
-                          'of the %.2f GB of free device memory' % (matrix.nnz, D, candidate_bytes, candidate_bytes / 1e9,
-                                                                   ops.free_bytes() / 1e9))
-    if init is None:
-        init = initial_embeddings(n_users, n_items, n_labels, rank, seed)
-    P0, E0, L0 = (np.asarray(a, dtype=np.float64) for a in init)
-    if P0.shape != (n_users, rank + 1) or E0.shape != (n_items, rank + 1) or L0.shape != (n_labels, rank + 1):
-        raise ValueError('LightFM: initial embeddings of shapes %s, %s, %s for (%d x %d), (%d x %d), (%d x %d)'
-                         % (P0.shape, E0.shape, L0.shape, n_users, rank + 1, n_items, rank + 1, n_labels, rank + 1))
-    P, E = ops.to_device(np.ascontiguousarray(P0)), ops.to_device(np.ascontiguousarray(E0))
-    L = ops.to_device(np.ascontiguousarray(L0)) if item_features is not None else None
-    state = tuple(None if X is None else ops.to_device(np.ones(tuple(X.shape))) for X in (P, E, L))
-    table = loss_table(n_items, D)
-    plan, plan_time, trained, quiet, draws = None, 0.0, [], [], []
-    for epoch in range(int(num_epochs)):
-        start = timer()
-        if plan is None or reshuffle_items:
-            plan = ops.warp_plan(matrix, blocks, bpr.item_order(seed, epoch, n_items) if reshuffle_items else None, item_features)
-            plan_time += timer() - start
-        cand = ops.warp_draw(plan, seed, epoch, D)
-        counts = [int(c) for c in ops.to_host(ops.warp_epoch(plan, cand, table, P, E, state, learning_rate, L))]   # the epoch's one host read
-        trained.append(counts[0])
-        quiet.append(counts[1])
-        draws.append(counts[2])
-        if history is not None:
-            history.append(counts[1] / matrix.nnz if matrix.nnz else float('nan'))
-        if iter_time is not None:
-            iter_time.append(timer() - start)
+
+    def begin(blocks, seed):
+        n_users, n_items = (int(x) for x in matrix.shape)
+        n_labels = 0
+        if item_features is not None:
+            if int(item_features.shape[0]) != n_items:
+                raise ValueError('LightFM: features for %d items, the training matrix has %d' % (item_features.shape[0], n_items))
+            n_labels = int(item_features.shape[1])
+        candidate_bytes = int(matrix.nnz) * D * 4
+        if hasattr(ops, 'free_bytes') and candidate_bytes > ops.free_bytes() / 2:
+            raise MemoryError('LightFM: the candidates of an epoch (%d positives x %d draws) need %d bytes (%.2f GB), more than half '
+                              'of the %.2f GB of free device memory' % (matrix.nnz, D, candidate_bytes, candidate_bytes / 1e9,
+                                                                       ops.free_bytes() / 1e9))
+        P0, E0, L0 = (np.asarray(a, dtype=np.float64)
+                      for a in (initial_embeddings(n_users, n_items, n_labels, rank, seed) if init is None else init))
+        if P0.shape != (n_users, rank + 1) or E0.shape != (n_items, rank + 1) or L0.shape != (n_labels, rank + 1):
+            raise ValueError('LightFM: initial embeddings of shapes %s, %s, %s for (%d x %d), (%d x %d), (%d x %d)'
+                             % (P0.shape, E0.shape, L0.shape, n_users, rank + 1, n_items, rank + 1, n_labels, rank + 1))
+        P, E = ops.to_device(np.ascontiguousarray(P0)), ops.to_device(np.ascontiguousarray(E0))
+        L = ops.to_device(np.ascontiguousarray(L0)) if item_features is not None else None
+        state = tuple(None if X is None else ops.to_device(np.ones(tuple(X.shape))) for X in (P, E, L))
+        table = loss_table(n_items, D)
+        return ((P, E, L, candidate_bytes), lambda order: ops.warp_plan(matrix, blocks, order, item_features),
+                lambda plan, epoch: ops.warp_epoch(plan, ops.warp_draw(plan, seed, epoch, D), table, P, E, state, learning_rate, L))
+
+    (P, E, L, candidate_bytes), blocks, seed, plan, plan_time, (trained, quiet, draws) = bpr.pairwise_fit(
+        'LightFM', ops, matrix, [('rank', rank, ops.warp_max_rank()), ('max_sampled', D, MAX_SAMPLED)], begin, num_epochs, seed, blocks,
+        default_blocks, reshuffle_items, lambda counts: counts[1] / matrix.nnz if matrix.nnz else float('nan'), history, iter_time, comm)
     if plan is None:
         plan = ops.warp_plan(matrix, blocks, None, item_features)
     Q = ops.warp_representation(plan, E, L)
@@ -191,8 +167,8 @@ class LightFMWrapper(FactorQueriesMixin, RecommenderModel):
         self.data.subscribe(self.data.on_change_event, self._clean_metadata)
 
     def _clean_metadata(self):
+        super()._clean_metadata()
         self.item_features_labels = None
-        self._factors_dev = None
 
     def _check_settings(self):
         """what the solver does not do, refused before any work, each by name"""
@@ -258,12 +234,9 @@ class LightFMWrapper(FactorQueriesMixin, RecommenderModel):
         ops.synchronize()
         self._track(start)
         self.build_stats = stats
-        userid, itemid = self.data.fields.userid, self.data.fields.itemid
-        labels = ops.to_host(L) if L is not None else np.zeros((0, int(self.rank) + 1))
-        self.factors = {userid: ops.to_host(P), itemid: ops.to_host(Q), f'{itemid}_identity': ops.to_host(E),
-                        f'{itemid}_features': labels}
-        self._factors_dev = (self.factors[userid], P, L if L is not None else ops.to_device(labels))
-        self._set_item_serving_index(Q)
+        if L is None:
+            L = ops.to_device(np.zeros((0, int(self.rank) + 1)))
+        self._set_factors(P, Q, kept=(L,), identity=E, features=L)
 
     def _extra_factors_device(self):
         L = self.factors[f'{self.data.fields.itemid}_features']

@@ -8,6 +8,8 @@ import torch
 
 import bpr_reference as ref
 from polara_amd import bpr  # noqa: F401  (the module under test: without it nothing here can run)
+from sweep_helpers import (MANY_STRATA_BLOCKS, MANY_STRATA_SEED, device_csr, many_strata_matrix, padding_is_zero, same_bits, strided,
+                           trained_in_the_last_stratum)
 from test_bpr_host import (FORWARDING_SEED, GRID, LEARN, POINTS, check_model_against_the_restated_fit, check_model_refusals,
                            planted_model)
 
@@ -15,29 +17,6 @@ pytestmark = pytest.mark.gpu
 
 LR, REG = 0.05, 0.01
 PLAN_KEYS = ('perm', 'block_ptr', 'item_ptr', 'users', 'items', 'item_order', 'item_part')
-
-
-def device_csr(ops, dense):
-    users, items = np.nonzero(dense)
-    return ops.csr_from_coo(users.astype(np.int64), items.astype(np.int64), np.ones(len(users)), dense.shape)
-
-
-def strided(ops, a, pad, off):
-    block = torch.zeros(a.shape[0], a.shape[1] + pad, dtype=torch.float64, device=ops.device)
-    view = block[:, off:off + a.shape[1]]
-    view.copy_(ops.to_device(a))
-    return view
-
-
-def padding_is_zero(view):
-    base = view._base.clone()
-    off = view.storage_offset() % base.stride(0)
-    base[:, off:off + view.shape[1]] = 0
-    return not bool(base.any())
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
 
 
 @functools.lru_cache(maxsize=None)
@@ -48,6 +27,9 @@ def restated_epoch(case, blocks, rank):
         order = ref.item_order(seed, 0, dense.shape[1])
     elif case == 'corner':
         (dense, order), seed = ref.corner_matrix(), 5
+    elif case == 'many strata':
+        dense, seed = many_strata_matrix(), MANY_STRATA_SEED
+        order = ref.item_order(seed, 0, dense.shape[1])
     else:
         dense, seed = ref.random_matrix(), 100 * blocks + rank
         order = ref.item_order(seed, 0, dense.shape[1])
@@ -139,6 +121,15 @@ def test_the_forwarding_case_is_bit_equal(hip_ops):
 
 def test_the_skip_corners_are_bit_equal(hip_ops):
     assert run_epoch(hip_ops, 'corner', 2, 3)[:2] == (2, 13)
+
+
+def test_more_strata_than_the_counters_reduction_has_threads(hip_ops):
+    """B = 257: the reduction of the block counters strides the strata over 256 threads, so stratum 256 is its second trip.  By
+    the restatement alone a sample of that stratum is trained (a wrong trip would lose it) and some samples are skipped."""
+    plan, neg = restated_epoch('many strata', MANY_STRATA_BLOCKS, 1)[3:5]
+    assert trained_in_the_last_stratum(plan, neg >= 0) and (neg < 0).any()
+    trained, skipped, _ = run_epoch(hip_ops, 'many strata', MANY_STRATA_BLOCKS, 1)
+    assert trained > 0 and skipped > 0
 
 
 def test_a_second_epoch_continues_from_the_first(hip_ops):

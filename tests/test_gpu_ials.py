@@ -16,6 +16,7 @@ import torch
 import ials_reference as ref
 from polara_amd import ials
 from polara_amd.models import ScaledMatrixMixin
+from sweep_helpers import strided
 
 pytestmark = pytest.mark.gpu
 
@@ -25,13 +26,6 @@ DROPPED_MARGIN = 6e7
 
 def device_csr(ops, C):
     return ops.csr(C.indptr, C.indices, np.asarray(C.data, dtype=np.float64), C.shape)
-
-
-def strided(ops, a, pad=3, off=1):
-    block = torch.zeros(a.shape[0], a.shape[1] + pad, dtype=torch.float64, device=ops.device)
-    view = block[:, off:off + a.shape[1]]
-    view.copy_(ops.to_device(a))
-    return view
 
 
 @functools.lru_cache(maxsize=None)

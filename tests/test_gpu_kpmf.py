@@ -10,7 +10,8 @@ import torch
 
 import kpmf_reference as ref
 from conftest import load_golden
-from test_gpu_pmf import device_csr, padding_is_zero, strided, tiny_triplets
+from sweep_helpers import padding_is_zero, strided
+from test_gpu_pmf import device_csr, tiny_triplets
 from test_kpmf_host import FIXTURES, check_kpmf_model_against_fixture, half_identity_kernels, restated_solution
 
 pytestmark = pytest.mark.gpu

@@ -10,6 +10,7 @@ import lce_reference as ref
 from conftest import load_golden
 from i2i_reference import select, tie_aware_mismatches
 from recorded_calls import sweeps
+from sweep_helpers import padding_is_zero, strided
 from test_lce_host import FIXTURES, TOL, check_lce_model_against_fixture, close
 
 pytestmark = pytest.mark.gpu
@@ -17,26 +18,10 @@ pytestmark = pytest.mark.gpu
 TIE_TOL = 1e-12                     # as in test_gpu_coldstart.py: O(1) sums of <= 100 fp64 products
 
 
-def strided(ops, a, pad=3, off=1):
-    """`a` on the device inside a wider block: leading dimension a.shape[1] + pad, first column `off`"""
-    block = torch.zeros(a.shape[0], a.shape[1] + pad, dtype=torch.float64, device=ops.device)
-    view = block[:, off:off + a.shape[1]]
-    view.copy_(ops.to_device(a))
-    return view
-
-
 def launches(rec):
     """names of the recorded library calls that enqueue work (first argument: the stream), as tools/bench_coldstart.py counts
     them; planning queries (work sizes, the fused bound) are host functions"""
     return [n for n, f, a in rec.calls if a and hasattr(a[0], 'value')]
-
-
-def padding_is_zero(view):
-    """nothing was written around a view made by `strided`"""
-    base = view._base.clone()
-    off = view.storage_offset() % base.stride(0)
-    base[:, off:off + view.shape[1]] = 0
-    return not bool(base.any())
 
 
 def update_case(rng, m, k, with_c):

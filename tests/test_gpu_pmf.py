@@ -10,6 +10,7 @@ import torch
 import pmf_reference as ref
 from conftest import load_golden
 from polara_amd import pmf
+from sweep_helpers import padding_is_zero, strided
 from test_pmf_host import FIXTURES, check_pmf_model_against_fixture, interactions, restated_solution
 
 pytestmark = pytest.mark.gpu
@@ -31,20 +32,6 @@ def tiny_triplets():
 
 def device_csr(ops, u, i, v, n_users, n_items):
     return ops.csr_from_coo(u, i, np.asarray(v, dtype=np.float64), (n_users, n_items))
-
-
-def strided(ops, a, pad=3, off=1):
-    block = torch.zeros(a.shape[0], a.shape[1] + pad, dtype=torch.float64, device=ops.device)
-    view = block[:, off:off + a.shape[1]]
-    view.copy_(ops.to_device(a))
-    return view
-
-
-def padding_is_zero(view):
-    base = view._base.clone()
-    off = view.storage_offset() % base.stride(0)
-    base[:, off:off + view.shape[1]] = 0
-    return not bool(base.any())
 
 
 @functools.lru_cache(maxsize=None)

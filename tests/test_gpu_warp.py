@@ -10,33 +10,16 @@ from scipy.sparse import csr_matrix
 
 import lightfm_reference as ref
 from polara_amd import warp  # noqa: F401  (the module under test: without it nothing here can run)
+from sweep_helpers import (MANY_STRATA_BLOCKS, MANY_STRATA_SEED, device_csr, many_strata_matrix, padding_is_zero, same_bits, strided,
+                           trained_in_the_last_stratum)
 from test_warp_host import (CORNER_D, CORNER_RANK, LEARN, check_cold_start_against_the_restated_fit,
-                            check_model_against_the_restated_fit, check_model_refusals, corner_case, planted_model, same_bits)
+                            check_model_against_the_restated_fit, check_model_refusals, corner_case, planted_model)
 
 pytestmark = pytest.mark.gpu
 
 LR = 0.05
 PLAN_KEYS = ('perm', 'block_ptr', 'item_ptr', 'users', 'items', 'item_order', 'item_part')
 FEATURE_KEYS = ('a', 'row_ptr', 'row_idx', 'row_val', 'col_ptr', 'col_idx', 'col_val')
-
-
-def device_csr(ops, dense):
-    users, items = np.nonzero(dense)
-    return ops.csr_from_coo(users.astype(np.int64), items.astype(np.int64), np.ones(len(users)), dense.shape)
-
-
-def strided(ops, a, pad, off):
-    block = torch.zeros(a.shape[0], a.shape[1] + pad, dtype=torch.float64, device=ops.device)
-    view = block[:, off:off + a.shape[1]]
-    view.copy_(ops.to_device(a))
-    return view
-
-
-def padding_is_zero(view):
-    base = view._base.clone()
-    off = view.storage_offset() % base.stride(0)
-    base[:, off:off + view.shape[1]] = 0
-    return not bool(base.any())
 
 
 def scaled_embeddings(n_users, n_items, n_labels, rank, seed):
@@ -56,8 +39,12 @@ def restated_epoch(case, blocks, rank, max_sampled, featured):
         dense, hot, order, plan, cand, init = corner_case()
         seed = None
     else:
-        dense, hot = ref.random_matrix(), ref.random_features()
-        seed = 1000 * blocks + 10 * rank + max_sampled
+        if case == 'many strata':
+            dense, seed = many_strata_matrix(), MANY_STRATA_SEED
+            hot = np.zeros((dense.shape[1], 0), dtype=np.int8)
+        else:
+            dense, hot = ref.random_matrix(), ref.random_features()
+            seed = 1000 * blocks + 10 * rank + max_sampled
         order = ref.item_order(seed, 0, dense.shape[1])
         plan = ref.make_plan(dense, blocks, order)
         cand = ref.draw_candidates(plan, seed, 0, max_sampled)
@@ -66,10 +53,13 @@ def restated_epoch(case, blocks, rank, max_sampled, featured):
     table = ref.loss_table(dense.shape[1], max_sampled)
     new = [x.copy() for x in init]
     state = [np.ones_like(x) for x in init]
+    trace = []
     counts = ref.epoch(plan, cand, table, new[0], new[1], state[0], state[1], LR, feat, new[2] if featured else None,
-                       state[2] if featured else None)
+                       state[2] if featured else None, trace=trace)
+    trained = np.zeros(plan['nnz'], dtype=bool)                           # per position of the schedule
+    trained[[p for p, hit in trace if hit >= 0]] = True
     out = dict(dense=dense, hot=hot, order=order, seed=seed, plan=plan, cand=cand, table=table, init=init, new=tuple(new),
-               state=tuple(state), counts=counts, feat=feat)
+               state=tuple(state), counts=counts, feat=feat, trained=trained)
     for a in (dense, hot, order, cand, table) + tuple(init) + tuple(new) + tuple(state) + tuple(plan[k] for k in PLAN_KEYS):
         a.setflags(write=False)
     return out
@@ -146,6 +136,15 @@ def test_one_epoch_with_features_is_bit_equal_to_the_restatement(hip_ops, blocks
     counts = run_epoch(hip_ops, 'random', blocks, rank, 5, True)
     assert counts[0] > 0 and counts[1] > 0
     assert not np.array_equal(r['new'][2], r['init'][2]) and (r['state'][2] > 1).any()
+
+
+def test_more_strata_than_the_counters_reduction_has_threads(hip_ops):
+    """B = 257: the reduction of the block counters strides the strata over 256 threads, so stratum 256 is its second trip.  By
+    the restatement alone a sample of that stratum is trained (a wrong trip would lose it) and some samples stay quiet."""
+    r = restated_epoch('many strata', MANY_STRATA_BLOCKS, 1, 3, False)
+    assert trained_in_the_last_stratum(r['plan'], r['trained']) and not r['trained'].all()
+    trained, quiet, _ = run_epoch(hip_ops, 'many strata', MANY_STRATA_BLOCKS, 1, 3, False)
+    assert trained > 0 and quiet > 0
 
 
 def test_the_corner_case_is_bit_equal(hip_ops):

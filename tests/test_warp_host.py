@@ -10,6 +10,7 @@ import pytest
 import bpr_reference as bref
 import lightfm_reference as ref
 from polara_amd import bpr, warp
+from sweep_helpers import same_bits
 
 # the learning test: planted_cold_start() (60 users, 40 warm + 8 cold items, 552 training positives, 8 labels), the restatement
 LEARN = dict(rank=4, learning_rate=0.05, max_sampled=10, num_epochs=30, seed=7, blocks=3)
@@ -240,10 +241,6 @@ def planted_model(ops, featured=True, cold=False, **settings):
     for key, value in settings.items():
         setattr(m, key, value)
     return m
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
 
 
 def check_model_against_the_restated_fit(m, featured=True):
