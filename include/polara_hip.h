@@ -1038,6 +1038,71 @@ int pk_warp_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, i
                       void *work_dev, int64_t *counts_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Factorisation model with side features (csrc/fm.hip; polara_amd/fm.py): rating regression with a global mean mu, user and
+ * item biases, linear weights of the side features and factorised interactions, fp64.  Rank k, C = k + 2 columns:
+ *     P  [n_users   x C]  user identity rows:  factors | bias          | 1  (never written)
+ *     LU [n_ulabels x C]  user label rows:     factors | linear weight | 0  (never written)
+ *     E  [n_items   x C]  item identity rows:  factors | 1  (never written) | bias
+ *     LI [n_ilabels x C]  item label rows:     factors | 0  (never written) | linear weight
+ * Features of a side: weights a [n_rows] and F [n_rows x n_labels] as CSR (row_*: labels ascending within a row) and CSC
+ * (col_*: rows ascending within a label), any values.  Representations and prediction:
+ *     pt_u = aU[u] * P[u] + SU[u],   SU[u] = (+0.0 + FU[u,l1] * LU[l1]) + FU[u,l2] * LU[l2] + ...   (storage order)
+ *     qt_i = aI[i] * E[i] + SI[i],   SI likewise;   a side without features (a*_dev == NULL) has pt_u = P[u] (qt_i = E[i]): no
+ *     multiplication, no S, no G, no label launches.
+ *     yhat(u, i) = mu + sum_c pt_u[c] * qt_i[c]
+ * Interactions inside one side (identity x own labels, label x label) are not modelled.
+ * The interactions, the schedule and the lane groups are PMF's above (w = the smallest of 16, 32, 64 that is >= C).
+ * Step rule (x the parameter, g its gradient, s its state; state blocks have the shapes of their parameters, start at 0 and are
+ * NOT cleared between epochs):   x <- x - step * adj(g, s)   with adj the adjusters of PMF above (NONE: adj = g).
+ * lam(c) = regularization for c < k, linear_regularization for the bias / linear-weight column.
+ *   One epoch (pk_fm_epoch_f64), per stratum in stream order:
+ *     1. per side with features (one launch each): S = F L as above and G [n_rows x (C + 1)] is cleared
+ *     2. the sweep (one launch).  Per sample (u, i, r) in IEEE fp64 without contraction, tree = PMF's halving tree over C columns:
+ *          pt, qt from the LIVE identity rows and the S of step 1
+ *          err = (mu + tree(pt * qt)) - r
+ *          eq = err * qt;   ep = err * pt                               (per column, both from the rows before the update)
+ *          gp = aU[u] * eq + lam(c) * P[u][c]    (without user features: eq + lam(c) * P[u][c])     for c <= k
+ *          gq = aI[i] * ep + lam(c) * E[i][c]    (without item features: ep + lam(c) * E[i][c])     for c < k and c = k + 1
+ *          the step rule on P[u] with gp (state SP[u]) and on E[i] with gq (state SE[i]), those columns only
+ *          with user features:  GU[u][c] <- GU[u][c] + eq  (c < C);  GU[u][C] <- GU[u][C] + 1
+ *          with item features:  GI[i][c] <- GI[i][c] + ep  (c < C);  GI[i][C] <- GI[i][C] + 1
+ *          the block's squared error += err * err   (reduced as PMF's into sse_dev[0])
+ *        A row (with its state row, its row of G and its count) stays in registers while consecutive samples share it.
+ *     3. per side with features, the label step (one launch each; pk_fm_label_step_f64 is this step alone, followed by clearing
+ *        G).  Per label l and column c — c = k (user side) or k + 1 (item side), and c < k when label_factors != 0:
+ *          g = (+0.0 + F[r1,l] * G[r1][c]) + F[r2,l] * G[r2][c] + ...;   N = (+0.0 + G[r1][C]) + G[r2][C] + ...   (rows ascending)
+ *          N == 0 (no row of the label was sampled in the stratum): nothing is done
+ *          g <- g + (lam(c) * N) * L[l][c];   the step rule on L[l][c] with g (state SL[l][c])
+ *   After the last stratum G is cleared.  No atomics, no flags: the label rows are read-only while a stratum runs, the rows
+ *   of P, E, their states and G that a block writes are its own, and stream order separates the launches.  The label rows
+ *   therefore take `blocks` steps per epoch, each on one stratum's summed gradient.
+ * pk_fm_label_image_f64: S alone (step 1 without clearing G).  item_side: 0 for user labels, 1 for item labels.
+ * work_dev: pk_pmf_work_doubles(blocks) doubles.  The kernels trust the plan and the feature matrices (indices in range,
+ * pointers ascending). */
+int32_t pk_fm_max_rank(void);
+int pk_fm_label_image_f64(void *stream, int32_t rank, int64_t n_rows, int64_t n_labels, const int64_t *row_ptr_dev,
+                          const int32_t *row_idx_dev, const double *row_val_dev, const double *L_dev, int64_t ldl,
+                          double *S_dev, int64_t lds);
+int pk_fm_label_step_f64(void *stream, int32_t rank, int32_t item_side, int32_t label_factors, int64_t n_rows,
+                         int64_t n_labels, const int64_t *col_ptr_dev, const int32_t *col_idx_dev,
+                         const double *col_val_dev, double *G_dev, int64_t ldg, double *L_dev, int64_t ldl, double *SL_dev,
+                         int64_t ldsl, double step, double regularization, double linear_regularization, int32_t adjust,
+                         double gamma, double smoothing);
+int pk_fm_epoch_f64(void *stream, int32_t blocks, int32_t rank, int64_t nnz, int64_t n_users, int64_t n_items,
+                    const int64_t *block_ptr_dev, const int32_t *users_dev, const int32_t *items_dev, const double *vals_dev,
+                    double mean, double *P_dev, int64_t ldp, double *E_dev, int64_t lde, double step, double regularization,
+                    double linear_regularization, int32_t adjust, double *SP_dev, int64_t ldsp, double *SE_dev, int64_t ldse,
+                    double gamma, double smoothing, int32_t label_factors,
+                    int64_t n_ulabels, const double *au_dev, const int64_t *urow_ptr_dev, const int32_t *urow_idx_dev,
+                    const double *urow_val_dev, const int64_t *ucol_ptr_dev, const int32_t *ucol_idx_dev,
+                    const double *ucol_val_dev, double *LU_dev, int64_t ldlu, double *SLU_dev, int64_t ldslu, double *SU_dev,
+                    int64_t ldsu, double *GU_dev, int64_t ldgu,
+                    int64_t n_ilabels, const double *ai_dev, const int64_t *irow_ptr_dev, const int32_t *irow_idx_dev,
+                    const double *irow_val_dev, const int64_t *icol_ptr_dev, const int32_t *icol_idx_dev,
+                    const double *icol_val_dev, double *LI_dev, int64_t ldli, double *SLI_dev, int64_t ldsli, double *SI_dev,
+                    int64_t ldsi, double *GI_dev, int64_t ldgi, double *work_dev, double *sse_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Implicit ALS (csrc/ials.hip): the alternating least squares of Hu, Koren and Volinsky for a CSR of confidences C
  * [n_rows x n_cols] (fp64 values, int64 row pointers, int32 column ids).  One half-step fixes Y [n_cols x rank] and solves
  * for every row u

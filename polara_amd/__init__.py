@@ -102,6 +102,7 @@ _EXPORTS = {
     'ImplicitALS': 'ials',
     'ImplicitBPR': 'bpr',
     'LightFMWrapper': 'warp', 'LightFMItemColdStart': 'warp',
+    'TuriFactorizationRecommender': 'fm', 'TuriFactorizationItemColdStart': 'fm',
     'EASEModel': 'ease',
     'SLIMModel': 'slim',
     'SimilarityAggregation': 'simagg', 'SimilarityAggregationItemColdStart': 'simagg',

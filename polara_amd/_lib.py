@@ -198,6 +198,13 @@ PROTOTYPES = {
     'pk_warp_epoch_f64': (C.c_int, [_vp, _i32, _i32, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
                                     _vp, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                                     _vp, _vp]),
+    'pk_fm_max_rank': (_i32, []),
+    'pk_fm_label_image_f64': (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64]),
+    'pk_fm_label_step_f64': (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _f64,
+                                       _f64, _i32, _f64, _f64]),
+    'pk_fm_epoch_f64': (C.c_int, [_vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _i64, _vp, _i64, _f64, _f64, _f64,
+                                  _i32, _vp, _i64, _vp, _i64, _f64, _f64, _i32]
+                        + 2 * ([_i64] + 7 * [_vp] + [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]) + [_vp, _vp]),
     'pk_ials_max_rank': (_i32, []),
     'pk_ials_work_bytes': (_i64, [_i64, _i32]),
     'pk_ials_half_step_f64': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _i64, _vp, _vp]),

@@ -36,7 +36,7 @@ extern "C" int pk_set_option(const char *name, int32_t value, int32_t unset) {
     pk_set_error("pk_set_option: unknown option '%s'", name ? name : "(null)");
     return PK_E_INVALID;
 }
-extern "C" int pk_version(void) { return 102; }
+extern "C" int pk_version(void) { return 103; }
 
 // Results on their way out, in stream order behind the kernels that produced them: `dst_host` should be pinned memory (the copy
 // is then asynchronous; from pageable memory the runtime stages it).  An entry of its own so that a host layer that replays a
@@ -95,6 +95,7 @@ hipError_t pk_tu_load_evalmetrics();
 hipError_t pk_tu_load_hybrid();
 hipError_t pk_tu_load_i2i();
 hipError_t pk_tu_load_ials();
+hipError_t pk_tu_load_fm();
 hipError_t pk_tu_load_foldq();
 hipError_t pk_tu_load_ingest();
 hipError_t pk_tu_load_lce();
@@ -111,7 +112,7 @@ hipError_t pk_tu_load_ttm();
 hipError_t pk_tu_load_warp();
 
 extern "C" int pk_warm_up(void) {
-    hipError_t (*const loaders[])() = {pk_tu_load_bpr, pk_tu_load_dense, pk_tu_load_driver, pk_tu_load_eigh, pk_tu_load_eigh_top, pk_tu_load_evalmetrics, pk_tu_load_foldq, pk_tu_load_hybrid, pk_tu_load_i2i, pk_tu_load_ials, pk_tu_load_ingest, pk_tu_load_kpmf, pk_tu_load_lce, pk_tu_load_pmf, pk_tu_load_rescore, pk_tu_load_sampled, pk_tu_load_score, pk_tu_load_simagg, pk_tu_load_slim, pk_tu_load_spgemm, pk_tu_load_spmm, pk_tu_load_ttm, pk_tu_load_warp};
+    hipError_t (*const loaders[])() = {pk_tu_load_bpr, pk_tu_load_dense, pk_tu_load_driver, pk_tu_load_eigh, pk_tu_load_eigh_top, pk_tu_load_evalmetrics, pk_tu_load_fm, pk_tu_load_foldq, pk_tu_load_hybrid, pk_tu_load_i2i, pk_tu_load_ials, pk_tu_load_ingest, pk_tu_load_kpmf, pk_tu_load_lce, pk_tu_load_pmf, pk_tu_load_rescore, pk_tu_load_sampled, pk_tu_load_score, pk_tu_load_simagg, pk_tu_load_slim, pk_tu_load_spgemm, pk_tu_load_spmm, pk_tu_load_ttm, pk_tu_load_warp};
     for (auto f : loaders) {
         const hipError_t e = f();
         if (e != hipSuccess) {

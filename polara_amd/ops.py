@@ -2465,6 +2465,148 @@ class HipOps:
                                                    _ptr(f['col_val']), _ptr(G), G.stride(0), _ptr(L), L.stride(0), _ptr(AL),
                                                    AL.stride(0), float(learning_rate)), 'pk_warp_label_step_f64')
 
+    # ---- Factorisation model with side features (csrc/fm.hip) -----------------------------------------------------------
+    _FM_FEATURE_KEYS = ('a', 'row_ptr', 'row_idx', 'row_val', 'col_ptr', 'col_idx', 'col_val')
+
+    def fm_max_rank(self):
+        return int(self.lib.pk_fm_max_rank())
+
+    def fm_plan(self, A, blocks, user_features=None, item_features=None, normalize=False):
+        """pmf_plan(A, blocks) plus plan['features'] = {'user': .., 'item': ..}: per side None, or for a SciPy one-hot matrix
+        [n_rows x n_labels] a dict on the device in warp_plan's layout — a (fp64 [n_rows]), F = diag(a) one_hot as CSR (row_ptr
+        int64, row_idx int32, row_val fp64) and as CSC (col_ptr, col_idx: rows ascending, col_val), n_labels.  a = 1 unless
+        `normalize`, which gives LightFM's 1 / (1 + labels of the row) (fm.side_features)."""
+        from . import fm
+        plan = self.pmf_plan(A, blocks)
+        plan['features'] = {}
+        for side, features, n in (('user', user_features, plan['shape'][0]), ('item', item_features, plan['shape'][1])):
+            plan['features'][side] = None
+            if features is None:
+                continue
+            if int(features.shape[0]) != n:
+                raise ValueError('TCF: features for %d %ss, the training matrix has %d' % (features.shape[0], side, n))
+            a, F = fm.side_features(features, normalize)
+            Fc = F.tocsc()
+            Fc.sort_indices()
+            up = lambda x, dt: self.to_device(np.ascontiguousarray(x, dtype=dt))
+            plan['features'][side] = dict(n_labels=int(F.shape[1]), a=up(a, np.float64), row_ptr=up(F.indptr, np.int64),
+                                          row_idx=up(F.indices, np.int32), row_val=up(F.data, np.float64),
+                                          col_ptr=up(Fc.indptr, np.int64), col_idx=up(Fc.indices, np.int32),
+                                          col_val=up(Fc.data, np.float64))
+        return plan
+
+    def _fm_check_plan(self, plan):
+        """(B, user features, item features) of a plan of fm_plan"""
+        B = self._check_plan(plan, 'PMF', users=('row_nnz',), items=('col_nnz',), entries=('users', 'vals'))
+        sides = plan.get('features', None)
+        if not isinstance(sides, dict) or set(sides) != {'user', 'item'}:
+            raise ValueError('TCF: not a plan of fm_plan')
+        for f, n in zip((sides['user'], sides['item']), plan['shape']):
+            if f is not None and (f['a'].numel() != n or f['row_ptr'].numel() != n + 1 or f['col_ptr'].numel() != f['n_labels'] + 1
+                                  or f['row_idx'].numel() != f['row_val'].numel() or f['col_idx'].numel() != f['row_idx'].numel()
+                                  or f['col_val'].numel() != f['row_idx'].numel()):
+                raise ValueError('TCF: not a plan of fm_plan (features)')
+        return B, sides['user'], sides['item']
+
+    def _fm_side(self, plan, side):
+        _, fu, fi = self._fm_check_plan(plan)
+        if side not in ('user', 'item'):
+            raise ValueError('TCF: side %r (\'user\' or \'item\')' % (side,))
+        f = fu if side == 'user' else fi
+        if f is None:
+            raise ValueError('TCF: the plan has no %s features' % side)
+        return f, plan['shape'][0 if side == 'user' else 1]
+
+    def _fm_rank(self, X):
+        k = int(X.shape[1]) - 2
+        if k < 1 or k > self.fm_max_rank():
+            raise ValueError('TCF: rank %d outside 1..%d' % (k, self.fm_max_rank()))
+        return k
+
+    def fm_label_image(self, plan, side, L):
+        """S = F L [n_rows x (k + 2)] of one side ('user' / 'item') in the storage-order sum of the sweep (pk_fm_label_image_f64)"""
+        f, n = self._fm_side(plan, side)
+        k = self._fm_rank(L)
+        self._check_row_blocks('TCF', (L,), (f['n_labels'],), k + 2)
+        S = self.empty(n, k + 2)
+        _lib.check(self.lib.pk_fm_label_image_f64(self.stream(), k, n, f['n_labels'], _ptr(f['row_ptr']), _ptr(f['row_idx']),
+                                                  _ptr(f['row_val']), _ptr(L), L.stride(0), _ptr(S), S.stride(0)),
+                   'pk_fm_label_image_f64')
+        return S
+
+    def fm_representation(self, plan, side, X, L=None):
+        """a o X + F L of one side (a copy of X without features on it): every product and sum rounded on its own"""
+        _, fu, fi = self._fm_check_plan(plan)
+        f = fu if side == 'user' else fi
+        if f is None:
+            return X.clone()
+        return X * f['a'][:, None] + self.fm_label_image(plan, side, L)
+
+    def fm_label_step(self, plan, side, G, L, SL, step, reg, lin_reg, adjust=None, gamma=0.9, label_factors=True, smoothing=1e-6):
+        """The label step of one side alone (pk_fm_label_step_f64): every label's gradient and sample count summed from G
+        [n_rows x (k + 3)] over its rows in ascending order, one adjusted step on L with the state SL (None without adjuster),
+        and G cleared — all in place."""
+        f, n = self._fm_side(plan, side)
+        k = self._fm_rank(L)
+        if adjust not in self._PMF_ADJUST:
+            raise ValueError('TCF: unknown gradient adjustment %r' % (adjust,))
+        self._check_row_blocks('TCF', (G,), (n,), k + 3)
+        self._check_row_blocks('TCF', (L,) + ((SL,) if adjust else ()), (f['n_labels'],), k + 2)
+        _lib.check(self.lib.pk_fm_label_step_f64(self.stream(), k, int(side == 'item'), int(bool(label_factors)), n, f['n_labels'],
+                                                 _ptr(f['col_ptr']), _ptr(f['col_idx']), _ptr(f['col_val']), _ptr(G), G.stride(0),
+                                                 _ptr(L), L.stride(0), _ptr(SL) if adjust else None, SL.stride(0) if adjust else 0,
+                                                 float(step), float(reg), float(lin_reg), self._PMF_ADJUST[adjust], float(gamma),
+                                                 float(smoothing)), 'pk_fm_label_step_f64')
+
+    def fm_epoch(self, plan, mean, P, E, LU, LI, state, step, reg, lin_reg, adjust=None, gamma=0.9, work=None, label_factors=True,
+                 smoothing=1e-6):
+        """One sweep over the plan's ratings (pk_fm_epoch_f64: per stratum the sweep's launch and, per side with features, one
+        before it (the label image) and one after (the label step); then the squared error).  P [n_users x (k + 2)], E [n_items
+        x (k + 2)] and, per side with features, LU / LI [n_labels x (k + 2)] (None otherwise) are updated in place, and so is
+        state = (SP, SE, SLU, SLI), the adjuster's state of the four blocks (None without adjuster; None for a side without
+        features).  work = (SU, GU, SI, GI): the images [n x (k + 2)] and the gradient rows [n x (k + 3)] (allocated here when
+        None; G is zero when the epoch ends).  Returns a device tensor of one double: the epoch's squared error."""
+        n_users, n_items = plan['shape']
+        k = self._fm_rank(P)
+        B, fu, fi = self._fm_check_plan(plan)
+        if adjust not in self._PMF_ADJUST:
+            raise ValueError('TCF: unknown gradient adjustment %r' % (adjust,))
+        if adjust and (state is None or len(state) != 4):
+            raise ValueError('TCF: the gradient adjustment %r needs state = (SP, SE, SLU, SLI)' % (adjust,))
+        SP, SE, SLU, SLI = state if adjust else (None,) * 4
+        self._check_row_blocks('TCF', (P, E) + ((SP, SE) if adjust else ()), (n_users, n_items), k + 2)
+        if work is not None and len(work) != 4:
+            raise ValueError('TCF: work = (SU, GU, SI, GI)')
+        ld = lambda X: X.stride(0) if X is not None else 0
+        sides = []
+        for side, f, n, L, SL, buffers in (('user', fu, n_users, LU, SLU, None if work is None else work[:2]),
+                                           ('item', fi, n_items, LI, SLI, None if work is None else work[2:])):
+            if f is None:
+                if L is not None:
+                    raise ValueError('TCF: %s label embeddings without %s features in the plan' % (side, side))
+                sides += [0] + [None] * len(self._FM_FEATURE_KEYS) + [None, 0, None, 0, None, 0, None, 0]
+                continue
+            if L is None or (adjust and SL is None):
+                raise ValueError('TCF: %s features need the label embeddings and, with an adjuster, their state' % side)
+            self._check_row_blocks('TCF', (L,) + ((SL,) if adjust else ()), (f['n_labels'],), k + 2)
+            S, G = buffers if buffers is not None else (self.empty(n, k + 2), self.empty(n, k + 3))
+            self._check_row_blocks('TCF', (S,), (n,), k + 2)
+            self._check_row_blocks('TCF', (G,), (n,), k + 3)
+            if not adjust:
+                SL = None
+            sides += [f['n_labels']] + [_ptr(f[name]) for name in self._FM_FEATURE_KEYS]
+            sides += [_ptr(L), ld(L), _ptr(SL), ld(SL), _ptr(S), ld(S), _ptr(G), ld(G)]
+        nnz = int(plan['nnz'])
+        sse_work = self.empty(int(self.lib.pk_pmf_work_doubles(B)))      # the block sums of the squared error
+        out = self.empty(1)
+        with self._timed('fm_epoch', (nnz, k, B, 0 if fu is None else fu['n_labels'], 0 if fi is None else fi['n_labels'])):
+            _lib.check(self.lib.pk_fm_epoch_f64(
+                self.stream(), B, k, nnz, n_users, n_items, _ptr(plan['block_ptr']), _ptr(plan['users']), _ptr(plan['items']),
+                _ptr(plan['vals']), float(mean), _ptr(P), P.stride(0), _ptr(E), E.stride(0), float(step), float(reg), float(lin_reg),
+                self._PMF_ADJUST[adjust], _ptr(SP), ld(SP), _ptr(SE), ld(SE), float(gamma), float(smoothing),
+                int(bool(label_factors)), *sides, _ptr(sse_work), _ptr(out)), 'pk_fm_epoch_f64')
+        return out
+
     # ---- Implicit ALS (csrc/ials.hip) ----------------------------------------------------------------------------------
     def ials_max_rank(self):
         return int(self.lib.pk_ials_max_rank())
