@@ -163,6 +163,29 @@ int pk_csr_rows_by_length(void *stream, int64_t n_rows, int64_t nnz, const int64
                           int32_t *indices_out_dev, void *values_out_dev, void *work_dev);
 /* counts[k] = number of keys equal to k (item popularity: the internal item order of the device path) */
 int pk_count_i32(void *stream, int64_t n, const int32_t *keys_dev, int64_t n_bins, int32_t *counts_dev);
+/* Splitting raw interactions into training / testset / holdout (csrc/split.hip; `RecommenderData.prepare()`,
+ * data.py:232-252, 388-458, 718-774).
+ * pk_split_keys: the selection key of n candidate rows, smaller = taken first.  mode is a sum of
+ *   PK_SPLIT_ASCENDING (1): key_hi ascends with the order value (else it descends: the largest values first);
+ *   PK_SPLIT_RANDOM_LO (2): key_lo = mix64(mix64(seed) + pos) (else ~pos: among equal values the LAST row first, the
+ *                           `keep='last'` of nlargest / nsmallest, data.py:741-746);
+ *   PK_SPLIT_NO_ORDER (4):  key_hi = 0 (order_vals_dev may be NULL);
+ *   PK_SPLIT_POS_ASCENDING (8): without RANDOM_LO, key_lo = pos (the first row first).
+ * Order values are finite fp64 compared as numbers (-0.0 = +0.0); pos >= 0.
+ * pk_segment_select: flags[q] = 1 for the min(k, len) entries of every segment [seg_ptr[s], seg_ptr[s + 1]) with the
+ * smallest (key_hi, key_lo) (lexicographic, unsigned), every other of the n flags 0.  Keys must be distinct inside a
+ * segment; the result is then unique and reproducible bit for bit.  1 <= k < 2^31, n < 2^32 - 1, empty segments allowed,
+ * a segment may be as long as n; seg_ptr ascends within [0, n] (a segment that does not is skipped).
+ * work >= pk_segment_select_work_bytes(n_seg, n). */
+#define PK_SPLIT_ASCENDING 1
+#define PK_SPLIT_RANDOM_LO 2
+#define PK_SPLIT_NO_ORDER 4
+#define PK_SPLIT_POS_ASCENDING 8
+int pk_split_keys(void *stream, int64_t n, const double *order_vals_dev, const int64_t *pos_dev, int32_t mode, uint64_t seed,
+                  uint64_t *key_hi_dev, uint64_t *key_lo_dev);
+int64_t pk_segment_select_work_bytes(int64_t n_seg, int64_t n);
+int pk_segment_select(void *stream, int64_t n_seg, int64_t n, const int64_t *seg_ptr_dev, const uint64_t *key_hi_dev,
+                      const uint64_t *key_lo_dev, int64_t k, uint8_t *flags_dev, void *work_dev);
 /* vals_out[p] = (row_scale[row of p] * vals[p]) * col_scale[indices[p]] (fp64): the diagonal rescaling A' = D_r A D_c of
  * ScaledMatrixMixin (models.py:864-895, preprocessing/matrices.py:71-93) applied to the device CSR. */
 int pk_csr_scale_f64(void *stream, int64_t n_rows, const int64_t *indptr_dev, const int32_t *indices_dev, const void *vals_dev,

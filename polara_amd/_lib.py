@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get('POLARA_HIP_LIB') or os.path.join(_HERE, 'libpolarahip
 PK_VAL_F32, PK_VAL_F64 = 0, 1
 PK_PMF_MAX_BLOCKS = 4096      # include/polara_hip.h
 PK_WARP_MAX_SAMPLED = 64      # include/polara_hip.h
+PK_SPLIT_ASCENDING, PK_SPLIT_RANDOM_LO, PK_SPLIT_NO_ORDER, PK_SPLIT_POS_ASCENDING = 1, 2, 4, 8     # include/polara_hip.h
 
 _vp, _i32, _i64, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 
@@ -48,6 +49,9 @@ PROTOTYPES = {
     'pk_csr_rows_by_length_work_bytes': (_i64, [_i64]),
     'pk_csr_rows_by_length': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'pk_count_i32': (C.c_int, [_vp, _i64, _vp, _i64, _vp]),
+    'pk_split_keys': (C.c_int, [_vp, _i64, _vp, _vp, _i32, C.c_uint64, _vp, _vp]),
+    'pk_segment_select_work_bytes': (_i64, [_i64, _i64]),
+    'pk_segment_select': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     'pk_csr_scale_f64': (C.c_int, [_vp, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     'pk_row_plan_work_bytes': (_i64, [_i64]),
     'pk_row_plan_count': (C.c_int, [_vp, _i64, _vp, _i32, _vp, _vp]),

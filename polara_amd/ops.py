@@ -667,6 +667,61 @@ class HipOps:
         _lib.check(self.lib.pk_count_i32(self.stream(), k32.numel(), _ptr(k32), int(n_bins), _ptr(counts)), 'pk_count_i32')
         return counts.to(torch.int64)
 
+    # ---- splitting raw interactions (csrc/split.hip; polara_amd/prepare.py) ------------------------------------------
+    def group_rows(self, codes, n_groups):
+        """(perm int64 [n], seg_ptr int64 [n_groups + 1]) of a device int64 tensor of group codes in [0, n_groups): the row
+        positions ordered by code, original order inside a group (own stable radix sort of (code, position) pairs), and
+        where every group starts (pk_count_i32 + scan)."""
+        n = int(codes.numel())
+        assert n < 2 ** 31 and n_groups < 2 ** 31, 'group_rows: 32-bit codes and positions'
+        seg_ptr = torch.zeros(int(n_groups) + 1, dtype=torch.int64, device=self.device)
+        if n == 0 or n_groups == 0:
+            return torch.zeros(0, dtype=torch.int64, device=self.device), seg_ptr
+        keys = codes.to(torch.int32).contiguous()
+        pos = torch.arange(n, dtype=torch.int32, device=self.device)
+        keys_tmp, pos_tmp = torch.empty_like(keys), torch.empty_like(pos)
+        bits = max(1, int(n_groups - 1).bit_length())
+        in_tmp = C.c_int32(0)
+        work = self._work(self.lib.pk_radix_work_bytes(n))
+        _lib.check(self.lib.pk_radix_sort_pairs(self.stream(), n, 4, _ptr(keys), _ptr(pos), _ptr(keys_tmp), _ptr(pos_tmp),
+                                                bits, _ptr(work), C.byref(in_tmp)), 'pk_radix_sort_pairs')
+        skeys, order = (keys_tmp, pos_tmp) if in_tmp.value else (keys, pos)
+        counts = torch.empty(int(n_groups), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.pk_count_i32(self.stream(), n, _ptr(skeys), int(n_groups), _ptr(counts)), 'pk_count_i32')
+        swork = self._work(self.lib.pk_scan_work_bytes(n_groups))
+        _lib.check(self.lib.pk_exclusive_scan_i32(self.stream(), int(n_groups), _ptr(counts), _ptr(seg_ptr), _ptr(swork)),
+                   'pk_exclusive_scan_i32')
+        return order.to(torch.int64), seg_ptr
+
+    def split_keys(self, order_vals, pos, mode, seed):
+        """(key_hi, key_lo): the two-word selection keys of pk_split_keys as int64 tensors holding the u64 bit patterns.
+        order_vals: device fp64 [n] or None (mode must then carry PK_SPLIT_NO_ORDER); pos: device int64 [n]."""
+        n = int(pos.numel())
+        pos = pos.contiguous()
+        if order_vals is not None:
+            order_vals = order_vals.contiguous()
+            assert order_vals.dtype == torch.float64 and order_vals.numel() == n
+        assert pos.dtype == torch.int64
+        key_hi = torch.empty(n, dtype=torch.int64, device=self.device)
+        key_lo = torch.empty(n, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.pk_split_keys(self.stream(), n, _ptr(order_vals), _ptr(pos), int(mode), int(seed) & (2 ** 64 - 1),
+                                          _ptr(key_hi), _ptr(key_lo)), 'pk_split_keys')
+        return key_hi, key_lo
+
+    def segment_select(self, seg_ptr, key_hi, key_lo, k):
+        """uint8 [n] (device): 1 for the min(k, len) entries of every segment with the smallest (key_hi, key_lo) —
+        pk_segment_select.  seg_ptr: device int64 [n_seg + 1], ascending within [0, n]."""
+        n = int(key_hi.numel())
+        n_seg = int(seg_ptr.numel()) - 1
+        assert seg_ptr.dtype == torch.int64 and key_hi.dtype == torch.int64 and key_lo.dtype == torch.int64
+        assert n_seg >= 0 and key_lo.numel() == n
+        seg_ptr, key_hi, key_lo = seg_ptr.contiguous(), key_hi.contiguous(), key_lo.contiguous()
+        flags = torch.empty(n, dtype=torch.uint8, device=self.device)
+        work = self._work(self.lib.pk_segment_select_work_bytes(n_seg, n))
+        _lib.check(self.lib.pk_segment_select(self.stream(), n_seg, n, _ptr(seg_ptr), _ptr(key_hi), _ptr(key_lo), int(k),
+                                              _ptr(flags), _ptr(work)), 'pk_segment_select')
+        return flags
+
     def csr_transpose(self, A, rows_per_block=0):
         """CSR of A^T on the device (pk_csr_transpose).  rows_per_block > 0: the (block, column)-ordered image — a
         DeviceCSR with n_blocks * n_cols rows whose row b * n_cols + c holds column c restricted to the rows of block b."""
