@@ -95,7 +95,10 @@ int pk_spmm_csr_x(void *stream,
  * to out.  Used for the transposed product of the build, Z = A^T Y (models.py:844's rmatvec), cut into user
  * blocks: the CSC of every block is one slice of a (block, item)-ordered plan (pk_csr_transpose with
  * rows_per_block > 0), block b adds its share to Z in launch order (deterministic), and the rows of Y that one
- * launch gathers stay cache-resident instead of spanning the whole user range. */
+ * launch gathers stay cache-resident instead of spanning the whole user range.
+ * EVERY row of X must be finite, rows that no entry references included: a task is processed in steps of several
+ * entries, and the padded steps of its last chunk multiply row 0 of X by a zero weight instead of branching
+ * (0 * inf = NaN would reach the sum).  X must therefore have at least one row whenever there are tasks. */
 int pk_spmm_csr_ex(void *stream,
                    int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
                    const int64_t *task_end_dev, const int32_t *task_slot_dev,
@@ -1158,7 +1161,9 @@ int pk_ials_loss_nz_f64(void *stream, int64_t n_rows, int64_t n_cols, int32_t ra
  * (lib/tensor.py:7-19):  res[i0, j, k] += val * u[i1, j] * v[i2, k].
  * nnz are pre-sorted by the output mode by the host layer; tasks as in pk_spmm_csr_f64, with
  * idx1/idx2 the two contracted-mode indices of every nnz and `vals` optional (NULL = ones,
- * data.py:805).  res is [n0 x (ra*rb)] row-major.
+ * data.py:805).  res is [n0 x (ra*rb)] row-major, ra * rb <= 1024.
+ * EVERY row of u and of v must be finite, rows that no entry references included: the padded steps of a task's
+ * last chunk multiply u[0, :] and v[0, :] by the value 0 instead of branching.
  * ------------------------------------------------------------------------------------------ */
 int pk_ttm_f64(void *stream,
                int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,

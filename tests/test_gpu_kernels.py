@@ -1,7 +1,7 @@
 """-m gpu: every HIP kernel, called through the C ABI (polara_amd.ops.HipOps -> libpolarahip.so),
 against NumPy/SciPy on the same seeded inputs.  Integer/index results must be bit-exact; fp64
 kernels are held to 1e-12 relative (summation order differs from BLAS), the fp32 MFMA candidate
-pass to the certified error bound it reports itself."""
+pass to the certified error bound it reports itself.  (Every instance of the row-task kernels: test_gpu_row_task_instances.py.)"""
 import numpy as np
 import pytest
 import scipy.sparse as sps
