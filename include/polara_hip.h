@@ -747,6 +747,31 @@ int pk_candidates_topk_f64(void *stream, int64_t n_users, int64_t n_items, int32
 int pk_sample_unseen(void *stream, int64_t n_users, int64_t n_items, const int64_t *t_indptr_dev, const int32_t *t_indices_dev,
                      const int64_t *h_indptr_dev, const int32_t *h_indices_dev, int32_t n, int64_t min_eligible,
                      const uint32_t *seeds_dev, int32_t *out_dev, int32_t *err_dev);
+/* ---- contextual post-filtering (csrc/context.hip; contextual/models.py:5-32) ----------------------------------------------
+ * Limits (host functions): the keys one workgroup sorts at a time, the largest number of contexts. */
+int32_t pk_context_window(void);
+int32_t pk_context_max(void);
+/* The class-lexicographic tier on top of the lists of the scoring pass.  Every user's list is ordered by
+ *   class descending, score descending, item ascending,   class = sum_j 2^j [item in the list of the user's value of context j]
+ * over the items that are not seen (all items when seen_indptr_dev is NULL); scores are E_u . V_i in fp64 with the summation
+ * order of the re-scoring and exact-row kernels (same bits).  The class-0 part comes from base_idx_dev, the lists of the
+ * plain pass [n_users x topk] (-1 pads allowed, at the end): out row = the min(topk, emitted) context items of the user,
+ * then the base entries that are not among them (in some list of the user and not seen), in their order, up to topk; pads
+ * stay at the end.  A seen item is never up-voted: the seen tail of a user with fewer than topk unseen items follows in the
+ * base order.
+ * V fp64 [n_items x K] rows in serving order (ldv), E fp64 [n_users x K] (lde); seen_*: CSR of the seen items, sorted rows.
+ * user_value_dev / value_ptr_dev / value_items_dev: HOST arrays of n_ctx DEVICE pointers; context j: user_value int32
+ * [n_users] (-1: no value), value_ptr int64 [n_values + 1], value_items int32 serving positions, ascending and distinct
+ * within a value, NOT range-checked on the device.  max_list: the longest list of any value (bounds the rounds of a
+ * workgroup).  out_class_dev int32 [n_users x topk] or NULL: the class of every slot, 0 for base entries and pads.
+ * order_dev int32 [n_users] or NULL: workgroup b serves row order_dev[b] (a permutation; users of one value next to each other
+ * walk the same list).  out_idx_dev must not alias base_idx_dev.
+ * 1 <= n_ctx <= pk_context_max(), 1 <= topk <= 1024, 1 <= K <= 1024, n_items < 2^28. */
+int pk_context_merge_f64(void *stream, int64_t n_users, int64_t n_items, int32_t K, const double *V_dev, int64_t ldv,
+                         const double *E_dev, int64_t lde, const int64_t *seen_indptr_dev, const int32_t *seen_indices_dev,
+                         int32_t n_ctx, const int32_t *const *user_value_dev, const int64_t *const *value_ptr_dev,
+                         const int32_t *const *value_items_dev, int64_t max_list, const int64_t *base_idx_dev, int32_t topk,
+                         int64_t *out_idx_dev, int32_t *out_class_dev, const int32_t *order_dev);
 /* The global order of the catalogue for PopularityModel: order_dev[p] = the item at position p by (score descending,
  * item ascending) — one stable device radix sort.  work >= pk_popular_order_work_bytes(n_items). */
 int64_t pk_popular_order_work_bytes(int64_t n_items);

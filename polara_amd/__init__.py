@@ -14,6 +14,7 @@
     from polara_amd import SVDModelSampled, RandomSampleArrayData   # sampled-negatives evaluation (1 holdout + n unseen items)
     from polara_amd import ArrayData, ShardedArrayData              # NumPy / on-disk data providers
     from polara_amd import RecommenderArrayData                     # raw interactions -> folds, holdout, indices on the device
+    from polara_amd import ItemPostFilteringMixin, ItemPostFilteringArrayData   # contextual post-filtering: context items first
 
 Resolved on first use, so that importing the package (or its build / binding modules) does not pull in torch."""
 import os as _os
@@ -113,6 +114,7 @@ _EXPORTS = {
     'ArrayData': 'data', 'ShardedArrayData': 'data',
     'RandomSampleEvaluationMixin': 'data', 'RandomSampleArrayData': 'data',
     'RecommenderArrayData': 'prepare', 'PrepareNumpyOps': 'prepare',
+    'ItemPostFilteringMixin': 'contextual', 'ItemPostFilteringArrayData': 'data',
     'RandomSampleEvaluationSVDMixin': 'sampled', 'SVDModelSampled': 'sampled', 'ScaledSVDSampled': 'sampled',
     'SparseProduct': 'operator', 'find_optimal_svd_rank': 'pipelines', 'find_optimal_tucker_ranks': 'pipelines',
     'find_optimal_config': 'pipelines',

@@ -153,6 +153,10 @@ PROTOTYPES = {
     'pk_sample_round_limit': (_i64, [_i64, _i32, _i64]),
     'pk_sample_max_rounds': (_i32, []),
     'pk_sample_unseen': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp]),
+    'pk_context_window': (_i32, []),
+    'pk_context_max': (_i32, []),
+    'pk_context_merge_f64': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32,
+                                       _vp, _vp, _vp]),
     'pk_popular_order_work_bytes': (_i64, [_i64]),
     'pk_popular_order': (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     'pk_popular_topk': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _vp]),

@@ -341,6 +341,115 @@ class SimilarityArrayData(ArrayData):
         self._relations[entity] = rel
 
 
+class ItemPostFilteringArrayData(ArrayData):
+    """ArrayData with item contexts: the counterpart of Polara's `ItemPostFilteringData` (contextual/data.py:4-64) for
+    `ItemPostFilteringMixin` — every test user comes with one value per context (the value of its held-out interaction: a
+    genre, a daypart), every value with a list of items, and the model ranks those items first.
+
+    item_context_mapping: {context: (item_ids, context_values)} — the many-to-many pairs of the reference's mapping frame, in
+    the data's item ids; items outside 0..n_items-1 are dropped, repeated pairs count once.  holdout_context: {context: values
+    aligned with the holdout rows as given}.  Like the reference (contextual/data.py:42-49) the holdout must have exactly one
+    row per user (ValueError otherwise).  A holdout value without items in the mapping gives an empty list (the reference's
+    `reindex(..., fill_value=[])`).  The mapped state is recomputed by `set_test_data` (pass the new holdout's
+    `holdout_context`) and dropped by a data-change event; it is rebuilt on the next access."""
+
+    def __init__(self, *args, item_context_mapping, holdout_context, **kwargs):
+        self._context_mapping = {c: (np.asarray(i, dtype=np.int64), np.asarray(v)) for c, (i, v) in dict(item_context_mapping).items()}
+        for c, (i, v) in self._context_mapping.items():
+            if i.ndim != 1 or i.shape != v.shape:
+                raise ValueError('context %r: %s item ids for %s values' % (c, i.shape, v.shape))
+        self._holdout_context_given = dict(holdout_context)
+        self._holdout_context = None
+        self._context = None
+        super().__init__(*args, **kwargs)
+        self.subscribe(self.on_change_event, self._clean_context)
+
+    @property
+    def contexts(self):
+        """the contexts in mapping order: position j is bit j of an item's class"""
+        return tuple(self._context_mapping)
+
+    def _clean_context(self):
+        self._context = None
+
+    def set_test_data(self, testset=None, holdout=None, notify=True, holdout_context=None):
+        if holdout_context is not None:
+            self._holdout_context_given = dict(holdout_context)
+        self._context = self._holdout_context = None
+        if holdout is not None:
+            u = np.asarray(holdout[0])
+            missing = [c for c in self._context_mapping if c not in self._holdout_context_given]
+            if missing:
+                raise ValueError('no holdout values for context %r' % (missing[0],))
+            cols = {c: np.asarray(self._holdout_context_given[c]) for c in self._context_mapping}
+            for c, v in cols.items():
+                if v.shape != u.shape:
+                    raise ValueError('context %r: %d values for %d holdout rows' % (c, len(v), len(u)))
+            if len(u) > 1 and not bool((u[1:] >= u[:-1]).all()):
+                order = np.argsort(u, kind='stable')          # the rows are stored sorted by user: the values move with them
+                cols = {c: v[order] for c, v in cols.items()}
+            self._holdout_context = cols
+        super().set_test_data(testset, holdout, notify=False)
+        self.update_contextual_data()
+        if notify:
+            self._notify(self.on_update_event)
+
+    def update_contextual_data(self):
+        """contextual/data.py:42-49 with map_context_data (:15-40): per context the sorted distinct values that have items,
+        the CSR of their sorted distinct items, and the position of every test user's value among them (-1: no items)."""
+        self._context = None
+        hold = self._test.holdout
+        if hold is None:
+            return
+        u = hold.userid
+        if len(u) > 1 and bool((u[1:] == u[:-1]).any()):
+            raise ValueError('contextual post-filtering needs exactly one holdout row per user: %d rows for %d users'
+                             % (len(u), int(np.count_nonzero(u[1:] != u[:-1])) + 1))
+        mapped = {}
+        for c, (items, values) in self._context_mapping.items():
+            keep = (items >= 0) & (items < self.n_items)
+            vals, inv = np.unique(values[keep], return_inverse=True)
+            pairs = np.unique(inv.astype(np.int64).ravel() * self.n_items + items[keep])      # sorted by (value, item), distinct
+            value_ptr = np.zeros(len(vals) + 1, dtype=np.int64)
+            np.cumsum(np.bincount(pairs // self.n_items, minlength=len(vals)), out=value_ptr[1:])
+            hv = self._holdout_context[c]
+            user_value = np.full(len(u), -1, dtype=np.int32)
+            if len(vals) and len(hv):
+                try:
+                    pos = np.minimum(np.searchsorted(vals, hv), len(vals) - 1)
+                    hit = vals[pos] == hv
+                except TypeError:                                    # values of another kind than the mapping's: none matches
+                    pos, hit = np.zeros(len(hv), dtype=np.int64), np.zeros(len(hv), dtype=bool)
+                user_value[hit] = pos[hit]
+            mapped[c] = (vals, value_ptr, (pairs % self.n_items).astype(np.int64), user_value)
+        self._context = mapped
+
+    def _mapped(self, context):
+        if self._context is None:
+            self.update_contextual_data()
+        if self._context is None:
+            raise ValueError('no holdout: the contexts have nothing to map')
+        return self._context[context]
+
+    @property
+    def context_data(self):
+        """{context: (values, value_ptr, value_items, user_value)} in mapping order: the mapped state as one object, replaced
+        whenever it is recomputed (what a model keys its device images by)"""
+        if self._context is None:
+            self.update_contextual_data()
+        return self._context
+
+    def context_values(self, context):
+        """(sorted distinct values, value_ptr int64 [n_values + 1], value_items int64 in the data's item ids, sorted and
+        distinct per value)"""
+        return self._mapped(context)[:3]
+
+    def user_context(self, context):
+        """int32 per test user (the distinct holdout users, sorted): the position of its value in `context_values`, -1 when
+        the value has no items"""
+        return self._mapped(context)[3]
+
+
 def one_hot_csr(features, n_rows=None, n_labels=None):
     """A SciPy CSR feature matrix [n_rows x n_labels] from a SciPy matrix or from one list of label ids per row (the
     layout `stack_features(..., normalize=False)` gives the reference, lib/similarity.py:327-348): canonical (sorted

@@ -86,8 +86,11 @@ class FactorQueriesMixin:
         if n_users == 0:
             return np.empty((0, self.topk), dtype=np.int64)
         stats = {}
+        queries, finish = self._list_tier(T, self._test_queries(test_users), lambda: test_users)
         recs_dev = scoring.recommend(ops, self._item_factors_device(), T, self.topk, self.filter_seen,
-                                     stats=stats if self.collect_recommend_stats else None, queries=self._test_queries(test_users))
+                                     stats=stats if self.collect_recommend_stats else None, queries=queries)
+        if finish is not None:
+            recs_dev = finish(recs_dev, stats)
         self.recommend_stats = stats
         recs = self._external_ids(recs_dev, self._item_inv)
         self._recs_dev = (recs, recs_dev)

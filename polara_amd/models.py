@@ -427,6 +427,13 @@ class RecommenderModel:
         compared by identity."""
         return (self._item_rank,)
 
+    def _list_tier(self, T, queries, row_users):
+        """The one hook of the recommend pipeline between the scoring pass and the renaming of its lists:
+        (queries of the pass, finish) — `finish(recs_dev, stats)` returns the device lists to hand on, None: as they are.
+        T: the device test CSR of the pass; queries: the ready-made query rows or None (a fold-in pass); row_users(): the
+        data-level user of every row of T.  The default adds nothing to a pass (contextual.ItemPostFilteringMixin does)."""
+        return queries, None
+
     def get_recommendations(self):
         if self.verify_integrity:
             self.verify_data_integrity()
@@ -448,8 +455,12 @@ class RecommenderModel:
         stats = {}
         recs_dev = None
         if hi > lo:
+            queries, finish = self._list_tier(T, None, lambda: (np.arange(n_users) if resident is not None
+                                                                else np.asarray(self._get_test_data()[2]))[lo:hi])
             recs_dev = scoring.recommend(ops, self._item_factors_device(), T, self.topk, self.filter_seen,
-                                         stats=stats if self.collect_recommend_stats else None)
+                                         stats=stats if self.collect_recommend_stats else None, queries=queries)
+            if finish is not None:
+                recs_dev = finish(recs_dev, stats)
             recs = self._external_ids(recs_dev, self._item_inv)     # internal positions -> external item ids
         else:
             recs = np.empty((0, self.topk), dtype=np.int64)

@@ -1816,6 +1816,46 @@ class HipOps:
                                                        _ptr(scores)), 'pk_candidates_topk_f64')
         return out, (scores if want_scores else None)
 
+    # ---- contextual post-filtering (csrc/context.hip) --------------------------------------------------------------
+    def context_lists(self, user_value, value_ptr, value_items, n_users, n_items):
+        """The device image of ONE context for `context_merge`, from host arrays, range-checked here (the kernel does not):
+        user_value [n_users] (-1: no value), value_ptr [n_values + 1], value_items: serving positions, ascending and
+        distinct within a value."""
+        from . import contextual
+        uv, ptr, items, max_list = contextual.check_context_lists(user_value, value_ptr, value_items, n_users, n_items)
+        return contextual.ContextLists(self.to_device(uv), self.to_device(ptr), self.to_device(items), max_list)
+
+    def context_merge(self, V, E, seen, contexts, base_idx, want_class=False, order=None):
+        """int64 [n_users x topk] (and the int32 classes or None): the lists `base_idx` of the plain pass with the context
+        items of every user on top, ordered by (class descending, score descending, position ascending) — pk_context_merge_f64.
+        V: fp64 device item rows in serving order; E: fp64 device query rows (unit column stride); seen: (indptr, indices) of
+        the seen CSR or None (filter_seen off); contexts: 1..pk_context_max() images of `context_lists`, in mapping order;
+        order: int32 device permutation of the rows (workgroup b serves row order[b]) or None."""
+        n_users, topk = (int(x) for x in base_idx.shape)
+        n_items, K = (int(x) for x in V.shape)
+        n_ctx = len(contexts)
+        if not 1 <= n_ctx <= self.lib.pk_context_max():
+            raise ValueError('context_merge: %d contexts, 1..%d are supported' % (n_ctx, self.lib.pk_context_max()))
+        if tuple(E.shape) != (n_users, K) or E.dtype != torch.float64 or V.dtype != torch.float64 or E.stride(1) != 1 or V.stride(1) != 1:
+            raise ValueError('context_merge: fp64 rows E [%d x %d] and V [n_items x %d] with unit column stride expected' % (n_users, K, K))
+        if base_idx.dtype != torch.int64 or not base_idx.is_contiguous():
+            raise ValueError('context_merge: the base lists are a contiguous int64 [n_users x topk] block')
+        for c in contexts:
+            if c.user_value.numel() != n_users:
+                raise ValueError('context_merge: context values for %d users, %d rows to merge' % (c.user_value.numel(), n_users))
+        if order is not None and (order.dtype != torch.int32 or order.numel() != n_users):
+            raise ValueError('context_merge: `order` is an int32 permutation of the %d rows' % n_users)
+        out = torch.empty_like(base_idx)
+        cls = torch.empty(n_users, topk, dtype=torch.int32, device=self.device) if want_class else None
+        ptrs = [(C.c_void_p * n_ctx)(*[getattr(c, f).data_ptr() for c in contexts]) for f in ('user_value', 'value_ptr', 'value_items')]
+        sp, si = seen if seen is not None else (None, None)
+        with self._timed('context_merge', (n_users, n_items, K, topk, n_ctx)):
+            _lib.check(self.lib.pk_context_merge_f64(self.stream(), n_users, n_items, K, _ptr(V), V.stride(0), _ptr(E), max(E.stride(0), K),
+                                                     _ptr(sp), _ptr(si), n_ctx, ptrs[0], ptrs[1], ptrs[2],
+                                                     max(c.max_list for c in contexts), _ptr(base_idx), topk, _ptr(out), _ptr(cls),
+                                                     _ptr(order)), 'pk_context_merge_f64')
+        return out, cls
+
     def sample_unseen(self, T, H, n, seeds):
         """int32 device [n_users x n]: n distinct items per user drawn uniformly from the items outside the user's row of
         the device CSR T (sorted columns) and of the device CSR H (None: no second exclusion), in draw order, from one
