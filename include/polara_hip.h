@@ -881,6 +881,40 @@ int pk_slim_csr_fill(void *stream, int64_t nc, int64_t n, const double *Wt_block
                      int64_t nnz, int32_t *indices_dev, double *values_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Neighbourhood and random-walk item models (ItemKNN, P3alpha / RP3beta; csrc/knn.hip): one pass over the dense Gram image
+ * G [n x ldg] (pk_i2i_build_f64 + pk_ease_diag_f64) that normalises every entry, keeps the K best of every row and writes
+ * them as n x K slots — the image is read once, nothing of its size is written.  The arithmetic is fixed
+ * (tests/knn_reference.py restates it in NumPy and the device's bits are compared with that): everything is fp64, every
+ * product, sum, difference and quotient is rounded on its own (no contraction) and the quotient is the correctly rounded
+ * one.  For row i and column j < n, with g = G[i * ldg + j]:
+ *     PK_KNN_SCALE:     w = (g * row[i]) * col[j]
+ *     PK_KNN_COSINE:    w = g / (row[i] * col[j] + shrink)
+ *     PK_KNN_TANIMOTO:  w = g / (((row[i] + col[j]) - g) + shrink)
+ *   candidate:  j != i, g != 0, w finite and w != 0
+ *   kept:       the min(K, candidates) best by w descending, then j ascending (the total order of pk_topk_rows_f64 and
+ *               pk_i2i_topk)
+ *   output:     the kept entries in ASCENDING j in the first count[i] slots of row i of idx / val; the other slots are
+ *               idx = -1, val = 0
+ *   normalize != 0:  s = ((+0.0 + |w_0|) + |w_1|) + ... over the kept entries in ascending j; when s is finite and != 0
+ *               every kept w becomes w / s
+ * row and col hold n doubles each; every kind reads both.
+ * One workgroup per row streams it in windows of pk_i2i_window() columns, sorts a window's keys in LDS and merges its best
+ * into the row's running list (the keys, sort and merge of pk_i2i_topk); windows without a candidate that beats the list's
+ * last entry are skipped.  No atomics and no cross-workgroup traffic: equal inputs give equal bits.
+ * ------------------------------------------------------------------------------------------ */
+#define PK_KNN_SCALE 0
+#define PK_KNN_COSINE 1
+#define PK_KNN_TANIMOTO 2
+/* The largest K of pk_knn_prune_f64 (host function): pk_i2i_max_topk() = 1024. */
+int32_t pk_knn_max_neighbours(void);
+/* count [n] int32; idx [n x K] int32 and val [n x K] fp64, row-major.  1 <= n < 2^30, ldg >= n, 1 <= K <=
+ * pk_knn_max_neighbours(), shrink finite and >= 0, no pointer NULL: checked before any device work.  Rows of G are loaded
+ * 16 bytes at a time when ldg % 8 == 0 and G and col are 16-byte aligned, one double at a time otherwise: the same bits. */
+int pk_knn_prune_f64(void *stream, int64_t n, const double *G_dev, int64_t ldg, int32_t kind, const double *row_dev,
+                     const double *col_dev, double shrink, int32_t K, int32_t normalize, int32_t *count_dev, int32_t *idx_dev,
+                     double *val_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Local Collective Embeddings (csrc/lce.hip).  Replace the NumPy element-wise updates and traces of
  * `local_collective_embeddings` (lib/optimize.py:347-379).  The factors are tall row-major fp64 blocks, the H factors
  * transposed ([labels x k], [users x k]), so the three multiplicative updates are one form:

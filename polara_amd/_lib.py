@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('POLARA_HIP_LIB') or os.path.join(_HERE, 'libpolarahip.so')
 
 PK_VAL_F32, PK_VAL_F64 = 0, 1
+PK_KNN_SCALE, PK_KNN_COSINE, PK_KNN_TANIMOTO = 0, 1, 2      # include/polara_hip.h
 PK_PMF_MAX_BLOCKS = 4096      # include/polara_hip.h
 PK_WARP_MAX_SAMPLED = 64      # include/polara_hip.h
 PK_SPLIT_ASCENDING, PK_SPLIT_RANDOM_LO, PK_SPLIT_NO_ORDER, PK_SPLIT_POS_ASCENDING = 1, 2, 4, 8     # include/polara_hip.h
@@ -178,6 +179,8 @@ PROTOTYPES = {
     'pk_slim_solve_f64': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _f64, _f64, _f64, _i32, _i32, _vp, _i64, _vp, _vp]),
     'pk_slim_csr_count': (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     'pk_slim_csr_fill': (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    'pk_knn_max_neighbours': (_i32, []),
+    'pk_knn_prune_f64': (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _f64, _i32, _i32, _vp, _vp, _vp]),
     'pk_lce_fused_max_rank': (_i32, []),
     'pk_lce_update_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _vp, _i64, _f64, _f64, _f64, _vp]),
     'pk_lce_update_ew_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _f64, _vp]),

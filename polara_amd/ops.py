@@ -2085,6 +2085,72 @@ class HipOps:
                                                  _ptr(indices), _ptr(values)), 'pk_slim_csr_fill')
         return indptr, indices, values
 
+    # ---- ItemKNN / RP3beta: top-K pruning of the normalised Gram image (csrc/knn.hip) ---------------------------------
+    def knn_gram(self, A):
+        """The Gram image [n_items x i2i.leading_dim(n_items)] of G = A^T A WITH its true diagonal for the device CSR A
+        (`_gram_image` with 0 added to the diagonal); the pad columns are 0.  Raises MemoryError before allocating when
+        the image would take more than half of the free device memory (i2i.check_build_memory)."""
+        from . import i2i
+        n_items = int(A.shape[1])
+        i2i.check_build_memory(n_items, self.free_bytes())
+        return self._gram_image('knn_gram', A, n_items, i2i.leading_dim(n_items), diag=0.0)
+
+    def csr_row_scaled_power(self, A, row_scale, alpha):
+        """The DeviceCSR (fp64, pattern and plans of A) with the values row_scale[u] * a^alpha for the host fp64 vector
+        `row_scale` [n_rows].  a^alpha is exact NumPy: with alpha != 1 and values other than 1 the DISTINCT stored values
+        are powered on the host (np.power; a stored 0 stays 0, also at alpha = 0) and gathered, so every stored value is one
+        IEEE product of two known doubles."""
+        alpha = float(alpha)
+        vals = A.values.to(torch.float64)
+        if alpha != 1.0 and vals.numel() and not bool((vals == 1.0).all().item()):
+            distinct, where = torch.unique(vals, return_inverse=True)
+            table = self.to_host(distinct)
+            table = np.where(table == 0, 0.0, np.power(table, alpha))      # a stored 0 stays 0 (no walk), also at alpha = 0
+            vals = self.to_device(table)[where]
+        rows = torch.repeat_interleave(torch.arange(A.shape[0], device=self.device), A.indptr[1:] - A.indptr[:-1])
+        scale = self.to_device(np.ascontiguousarray(row_scale, dtype=np.float64))
+        new = A.with_columns(A.indices, scale[rows] * vals)
+        new.val_kind = _lib.PK_VAL_F64
+        return new
+
+    def knn_prune_slots(self, G, n, kind, row, col, shrink, K, normalize):
+        """(count int32 [n], idx int32 [n x K], val fp64 [n x K]), all on the device: the K best normalised entries of
+        every row of the fp64 image G [>= n rows, row stride >= n], in ascending column order, pads idx -1 / val 0
+        (pk_knn_prune_f64: the contract of include/polara_hip.h).  `kind`: knn.KINDS; row, col: n doubles each, host arrays
+        or device tensors."""
+        from . import knn
+        n, K = int(n), knn.check_neighbours(K)
+        if (G.dtype != torch.float64 or G.dim() != 2 or G.stride(1) != 1 or G.shape[0] < n or G.shape[1] < n
+                or G.device.type != self.device.type
+                or (self.device.index is not None and G.device.index != self.device.index)):
+            raise ValueError('knn_prune: the image does not hold %d rows of %d fp64 columns on %s' % (n, n, self.device))
+        vec = []
+        for name, v in (('row', row), ('col', col)):
+            v = v if torch.is_tensor(v) else self.to_device(np.asarray(v, dtype=np.float64))
+            v = v.to(device=self.device, dtype=torch.float64).contiguous()
+            if v.numel() != n:
+                raise ValueError('knn_prune: `%s` holds %d numbers for %d items' % (name, v.numel(), n))
+            vec.append(v)
+        count = torch.empty(n, dtype=torch.int32, device=self.device)
+        idx = torch.empty(n, K, dtype=torch.int32, device=self.device)
+        val = torch.empty(n, K, dtype=torch.float64, device=self.device)
+        with self._timed('knn_prune', (n, K)):
+            _lib.check(self.lib.pk_knn_prune_f64(self.stream(), n, _ptr(G), G.stride(0), int(kind), _ptr(vec[0]), _ptr(vec[1]),
+                                                 float(shrink), K, 1 if normalize else 0, _ptr(count), _ptr(idx), _ptr(val)),
+                       'pk_knn_prune_f64')
+        return count, idx, val
+
+    def knn_prune(self, G, n, kind, row, col, shrink, K, normalize):
+        """The canonical DeviceCSR [n x n] (fp64) of `knn_prune_slots`: indptr is the cumulative sum of the counts,
+        indices and values the non-pad slots in row-major order."""
+        n = int(n)
+        count, idx, val = self.knn_prune_slots(G, n, kind, row, col, shrink, K, normalize)
+        indptr = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        torch.cumsum(count, 0, out=indptr[1:])
+        stored = idx >= 0
+        W = DeviceCSR.from_device(self, indptr, idx[stored], val[stored], (n, n))
+        return W
+
     # ---- item cold start -----------------------------------------------------------------------------------------
     def coldstart_queries(self, F, W, G):
         """E = (F W) G for the cold items of a DeviceCSR over the training labels, fp64: the SpMM and the tall-skinny product
