@@ -70,35 +70,20 @@ int pk_warm_up(void);
  * split threshold are cut into several tasks whose partial sums go to `partial[task_slot[t]]`
  * (task_slot >= 0) and are added in slot order by a fix-up pass (deterministic, no atomics).
  * ------------------------------------------------------------------------------------------ */
-int pk_spmm_csr_f64(void *stream,
-                    int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
-                    const int64_t *task_end_dev, const int32_t *task_slot_dev,
-                    int64_t n_long, const int32_t *long_row_dev, const int32_t *long_slot_begin_dev,
-                    const int32_t *long_slot_end_dev,
-                    const int32_t *indices_dev, const void *vals_dev, int val_kind,
-                    const double *X_dev, int64_t ldx, int32_t nc,
-                    double *out_dev, int64_t ldo, double *partial_dev /* [n_slots x nc] or NULL */);
-/* Same product with the dense block X given in fp32 (x_kind = PK_VAL_F32; needs nc % 4 == 0, ldx % 4 == 0,
- * 16-byte aligned X) or fp64 (PK_VAL_F64 = pk_spmm_csr_f64).  Accumulation and output are fp64.  Used for the
- * approximate fold-in of the scoring pass: E' = A_test fl32(V) moves half the gather bytes of models.py:860's
- * left factor; the re-scoring kernel certifies the result against the rounding of V (pk_rescore_f64). */
-int pk_spmm_csr_x(void *stream,
-                  int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
-                  const int64_t *task_end_dev, const int32_t *task_slot_dev,
-                  int64_t n_long, const int32_t *long_row_dev, const int32_t *long_slot_begin_dev,
-                  const int32_t *long_slot_end_dev,
-                  const int32_t *indices_dev, const void *vals_dev, int val_kind,
-                  const void *X_dev, int x_kind, int64_t ldx, int32_t nc,
-                  double *out_dev, int64_t ldo, double *partial_dev);
-/* The general form behind both: task rows are numbered from `row_base` (task t writes output row task_row[t] -
- * row_base — a row block of a larger plan runs as its own launch), and with accumulate != 0 the result is ADDED
- * to out.  Used for the transposed product of the build, Z = A^T Y (models.py:844's rmatvec), cut into user
- * blocks: the CSC of every block is one slice of a (block, item)-ordered plan (pk_csr_transpose with
- * rows_per_block > 0), block b adds its share to Z in launch order (deterministic), and the rows of Y that one
- * launch gathers stay cache-resident instead of spanning the whole user range.
+/* The plain product, one entry.  The dense block X is fp64 (x_kind = PK_VAL_F64) or fp32 (PK_VAL_F32; needs nc % 4 == 0,
+ * ldx % 4 == 0 and a 16-byte aligned X, else PK_E_UNSUPPORTED); accumulation and output are fp64.  The fp32 block serves
+ * the approximate fold-in of the scoring pass: E' = A_test fl32(V) moves half the gather bytes of models.py:860's left
+ * factor; the re-scoring kernel certifies the result against the rounding of V (pk_rescore_f64).
+ * Task rows are numbered from `row_base` (task t writes output row task_row[t] - row_base — a row block of a larger plan
+ * runs as its own launch; a row base needs accumulate), and with accumulate != 0 the result is ADDED to out; the whole
+ * product of a matrix is row_base = 0, accumulate = 0.  Used for the transposed product of the build, Z = A^T Y
+ * (models.py:844's rmatvec), cut into user blocks: the CSC of every block is one slice of a (block, item)-ordered plan
+ * (pk_csr_transpose with rows_per_block > 0), block b adds its share to Z in launch order (deterministic), and the rows
+ * of Y that one launch gathers stay cache-resident instead of spanning the whole user range.
  * EVERY row of X must be finite, rows that no entry references included: a task is processed in steps of several
  * entries, and the padded steps of its last chunk multiply row 0 of X by a zero weight instead of branching
- * (0 * inf = NaN would reach the sum).  X must therefore have at least one row whenever there are tasks. */
+ * (0 * inf = NaN would reach the sum).  X must therefore have at least one row whenever there are tasks.
+ * Every argument rule is checked before anything is launched, for n_tasks = 0 too. */
 int pk_spmm_csr_ex(void *stream,
                    int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
                    const int64_t *task_end_dev, const int32_t *task_slot_dev,
@@ -106,7 +91,8 @@ int pk_spmm_csr_ex(void *stream,
                    const int32_t *long_slot_end_dev,
                    const int32_t *indices_dev, const void *vals_dev, int val_kind,
                    const void *X_dev, int x_kind, int64_t ldx, int32_t nc,
-                   double *out_dev, int64_t ldo, double *partial_dev, int64_t row_base, int32_t accumulate,
+                   double *out_dev, int64_t ldo, double *partial_dev /* [n_slots x nc] or NULL */,
+                   int64_t row_base, int32_t accumulate,
                    int64_t x_rows /* rows of X (= columns of the sparse matrix), or 0 if unknown: with fewer than 2^24 rows
                    and X below 4 GiB the kernels address X with 32-bit offsets (a quarter of the address arithmetic) */);
 
@@ -1218,7 +1204,7 @@ int pk_ials_loss_nz_f64(void *stream, int64_t n_rows, int64_t n_cols, int32_t ra
  * K5.  Sparse tensor-times-matrix (CoFFee / HOOI).
  * Replaces numba `dttm_seq` / `dttm_par` (lib/sparse.py:203-234) called from `ttm3d_seq`
  * (lib/tensor.py:7-19):  res[i0, j, k] += val * u[i1, j] * v[i2, k].
- * nnz are pre-sorted by the output mode by the host layer; tasks as in pk_spmm_csr_f64, with
+ * nnz are pre-sorted by the output mode by the host layer; tasks as in pk_spmm_csr_ex, with
  * idx1/idx2 the two contracted-mode indices of every nnz and `vals` optional (NULL = ones,
  * data.py:805).  res is [n0 x (ra*rb)] row-major, ra * rb <= 1024.
  * EVERY row of u and of v must be finite, rows that no entry references included: the padded steps of a task's

@@ -31,10 +31,6 @@ PROTOTYPES = {
     'pk_version': (C.c_int, []),
     'pk_warm_up': (C.c_int, []),
     'pk_device_info': (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(_i64)]),
-    'pk_spmm_csr_f64': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int,
-                                  _vp, _i64, _i32, _vp, _i64, _vp]),
-    'pk_spmm_csr_x': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int,
-                                _vp, C.c_int, _i64, _i32, _vp, _i64, _vp]),
     'pk_spmm_csr_ex': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int,
                                  _vp, C.c_int, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _i64]),
     'pk_scan_work_bytes': (_i64, [_i64]),

@@ -1,5 +1,5 @@
 """Host-side sparse containers: canonical CSR/CSC construction and the per-row task plans the
-SpMM / TTM kernels consume (include/polara_hip.h, pk_spmm_csr_f64).
+SpMM / TTM kernels consume (include/polara_hip.h, pk_spmm_csr_ex).
 
 The COO->CSR step restates `RecommenderModel.get_training_matrix` (models.py:160-177:
 `coo_matrix(...).tocsr()`, duplicates summed, indices sorted) in NumPy; it is index bookkeeping, not

@@ -384,83 +384,62 @@ __global__ __launch_bounds__(256) void spmm_fixup_kernel(
     }
 }
 
-template <typename VT>
-static int launch_spmm(hipStream_t st, int64_t n_tasks, const int32_t *task_row, const int64_t *task_begin,
-                       const int64_t *task_end, const int32_t *task_slot, const int32_t *indices,
-                       const void *vals, const void *Xv, int x_kind, int64_t ldx, int nc, double *out, int64_t ldo,
-                       double *partial, int64_t row_base, int accumulate, int64_t x_rows) {
-    dim3 grid((unsigned)pk_ceil_div(n_tasks, 4)), block(256);
-    const VT *v = static_cast<const VT *>(vals);
-    if (x_kind == PK_VAL_F32) {
-        // fp32 dense block: groups mapping only (one 16-byte load = 4 columns)
-        const float *X = static_cast<const float *>(Xv);
-        if (!((nc % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)X) % 16 == 0))) {
-            pk_set_error("pk_spmm_csr_x: an fp32 dense block needs nc %% 4 == 0, ldx %% 4 == 0 and 16-byte alignment");
-            return PK_E_UNSUPPORTED;
-        }
-        // 32-bit offsets: the caller told us how many rows X has, they number fewer than 2^24, a row is a whole number of
-        // 16-byte units and the last byte of X lies below 4 GiB
-        const bool off32 = x_rows > 0 && x_rows < (1 << 24) && ldx * 4 < (1 << 24) &&
-                           x_rows * ldx * 4 < ((int64_t)1 << 32);
-#define PK_SPMM_LAUNCH_F(G, A, O)                                                                                   \
-    hipLaunchKernelGGL((spmm_csr_groups_kernel<VT, G, float, A, O>), grid, block, 0, st, n_tasks, task_row,         \
-                       task_begin, task_end, task_slot, indices, v, X, ldx, nc, out, ldo, partial, row_base)
-#define PK_SPMM_GROUPS_F(G)                                                                                          \
-    do {                                                                                                             \
-        if (accumulate) { if (off32) PK_SPMM_LAUNCH_F(G, true, true); else PK_SPMM_LAUNCH_F(G, true, false); }       \
-        else { if (off32) PK_SPMM_LAUNCH_F(G, false, true); else PK_SPMM_LAUNCH_F(G, false, false); }                \
-    } while (0)
-        if (nc <= 16) PK_SPMM_GROUPS_F(16);
-        else if (nc <= 32) PK_SPMM_GROUPS_F(8);
-        else if (nc <= 64) PK_SPMM_GROUPS_F(4);
-        else if (nc <= 128) PK_SPMM_GROUPS_F(2);
-        else PK_SPMM_GROUPS_F(1);
-#undef PK_SPMM_GROUPS_F
-#undef PK_SPMM_LAUNCH_F
-        return PK_OK;
-    }
-    const double *X = static_cast<const double *>(Xv);
-    const bool paired = (nc % 2 == 0) && (ldx % 2 == 0) && (((uintptr_t)X) % 16 == 0);
-    if (paired) {
-        const bool off32 = x_rows > 0 && x_rows < (1 << 24) && ldx * 8 < (1 << 24) &&
-                           x_rows * ldx * 8 < ((int64_t)1 << 32);
-#define PK_SPMM_LAUNCH_D(G, A, O)                                                                                   \
-    hipLaunchKernelGGL((spmm_csr_groups_kernel<VT, G, double, A, O>), grid, block, 0, st, n_tasks, task_row,        \
-                       task_begin, task_end, task_slot, indices, v, X, ldx, nc, out, ldo, partial, row_base)
-#define PK_SPMM_GROUPS(G)                                                                                             \
-    do {                                                                                                              \
-        if (accumulate) { if (off32) PK_SPMM_LAUNCH_D(G, true, true); else PK_SPMM_LAUNCH_D(G, true, false); }        \
-        else { if (off32) PK_SPMM_LAUNCH_D(G, false, true); else PK_SPMM_LAUNCH_D(G, false, false); }                 \
-    } while (0)
-        if (nc <= 16) PK_SPMM_GROUPS(16);
-        else if (nc <= 32) PK_SPMM_GROUPS(8);
-        else if (nc <= 64) PK_SPMM_GROUPS(4);
-        else if (nc <= 128) PK_SPMM_GROUPS(2);
-        else PK_SPMM_GROUPS(1);
-#undef PK_SPMM_GROUPS
-#undef PK_SPMM_LAUNCH_D
-        return PK_OK;
-    }
-    const int cpl = (nc + 63) / 64;
-#define PK_SPMM_CASE(C)                                                                                            \
-    case C:                                                                                                        \
-        if (accumulate)                                                                                            \
-            hipLaunchKernelGGL((spmm_csr_kernel<VT, C, true>), grid, block, 0, st, n_tasks, task_row, task_begin,  \
-                               task_end, task_slot, indices, v, X, ldx, nc, out, ldo, partial, row_base);          \
-        else                                                                                                       \
-            hipLaunchKernelGGL((spmm_csr_kernel<VT, C, false>), grid, block, 0, st, n_tasks, task_row, task_begin, \
-                               task_end, task_slot, indices, v, X, ldx, nc, out, ldo, partial, row_base);          \
-        break;
-    switch (cpl) {
-        PK_SPMM_CASE(1)
-        PK_SPMM_CASE(2)
-        PK_SPMM_CASE(3)
-        PK_SPMM_CASE(4)
-        default:
-            pk_set_error("pk_spmm_csr_f64: nc=%d unsupported (max 256)", nc);
-            return PK_E_UNSUPPORTED;
-    }
-#undef PK_SPMM_CASE
+// ---- host side: one dispatcher for the instances, one validator, one fix-up launch; one C entry per kernel ------------------
+// a run-time choice between two instances as a compile-time constant: f(std::true_type()) or f(std::false_type())
+template <typename F>
+static void spmm_if(bool b, F &&f) {
+    if (b) f(std::true_type()); else f(std::false_type());
+}
+
+// GROUPS of the groups mapping for nc columns, as std::integral_constant<int, GROUPS>: the most groups whose lanes (four
+// columns each) still cover a row of the dense block
+template <typename F>
+static void spmm_groups(int nc, F &&f) {
+    if (nc <= 16) f(std::integral_constant<int, 16>());
+    else if (nc <= 32) f(std::integral_constant<int, 8>());
+    else if (nc <= 64) f(std::integral_constant<int, 4>());
+    else if (nc <= 128) f(std::integral_constant<int, 2>());
+    else f(std::integral_constant<int, 1>());
+}
+
+// 32-bit offsets into X: the caller told us how many rows X has, they number fewer than 2^24, so does the row stride in
+// bytes, and the last byte of X lies below 4 GiB
+static bool spmm_off32(int64_t x_rows, int64_t ldx, int elem_bytes) {
+    return x_rows > 0 && x_rows < (1 << 24) && ldx * elem_bytes < (1 << 24) && x_rows * ldx * elem_bytes < ((int64_t)1 << 32);
+}
+
+// the instance of a groups kernel (plain, flagged or listed) for this value type, width and addressing:
+// launch(VT(), std::integral_constant<int, GROUPS>(), std::bool_constant<OFF32>())
+template <typename F>
+static void spmm_groups_instance(int val_kind, int nc, bool off32, F &&launch) {
+    spmm_if(val_kind == PK_VAL_F32, [&](auto v32) {
+        using VT = std::conditional_t<decltype(v32)::value, float, double>;
+        spmm_if(off32, [&](auto o) { spmm_groups(nc, [&](auto g) { launch(VT(), g, o); }); });
+    });
+}
+
+// out[row, :] (+)= the partial sums of the split rows, for the rows whose tasks ran (row_flags = nullptr: all of them)
+static int launch_spmm_fixup(hipStream_t st, int64_t n_long, const int32_t *long_row, const int32_t *slot_begin,
+                             const int32_t *slot_end, const double *partial, int nc, double *out, int64_t ldo, int64_t row_base,
+                             int accumulate, const int32_t *row_flags, int flag_mask) {
+    if (n_long <= 0) return PK_OK;
+    hipLaunchKernelGGL(spmm_fixup_kernel, dim3((unsigned)n_long), dim3(256), 0, st, n_long, long_row, slot_begin, slot_end, partial,
+                       nc, out, ldo, row_base, accumulate, row_flags, flag_mask);
+    PK_CHECK_LAUNCH("spmm_fixup_kernel");
+    return PK_OK;
+}
+
+// The rules the three entries share, under the entry's name; an entry checks what is its own BEFORE these, and the value kind
+// comes last.  `counts`: the entry's word on its task / list count.  f64_only: the flagged and the listed product, which have
+// the groups mapping of an fp64 X only (two columns per 16-byte load).
+static int spmm_check(const char *entry, bool counts, bool f64_only, int nc, const void *X, int64_t ldx, int64_t ldo,
+                      int64_t n_long, const double *partial, int val_kind) {
+    PK_REQUIRE(counts && nc >= 1 && nc <= 256 && !(f64_only && nc % 2), "%s: bad sizes (nc=%d: %s256)", entry, nc,
+               f64_only ? "even, 2.." : "1..");
+    PK_REQUIRE(ldo >= nc && ldx >= nc, "%s: ldo/ldx < nc", entry);
+    PK_REQUIRE(!f64_only || (ldx % 2 == 0 && ((uintptr_t)X) % 16 == 0), "%s: ldx even, X 16-byte aligned", entry);
+    PK_REQUIRE(n_long == 0 || partial != nullptr, "%s: partial buffer required", entry);
+    PK_REQUIRE(val_kind == PK_VAL_F32 || val_kind == PK_VAL_F64, "%s: bad val_kind %d", entry, val_kind);
     return PK_OK;
 }
 
@@ -471,108 +450,73 @@ extern "C" int pk_spmm_csr_ex(void *stream, int64_t n_tasks, const int32_t *task
                               const int32_t *indices_dev, const void *vals_dev, int val_kind,
                               const void *X_dev, int x_kind, int64_t ldx, int32_t nc, double *out_dev, int64_t ldo,
                               double *partial_dev, int64_t row_base, int32_t accumulate, int64_t x_rows) {
-    PK_REQUIRE(n_tasks >= 0 && nc >= 1 && nc <= 256, "pk_spmm_csr: bad sizes n_tasks=%lld nc=%d",
-               (long long)n_tasks, nc);
-    PK_REQUIRE(ldo >= nc && ldx >= nc, "pk_spmm_csr: ldo/ldx < nc");
-    PK_REQUIRE(x_kind == PK_VAL_F32 || x_kind == PK_VAL_F64, "pk_spmm_csr_x: bad x_kind %d", x_kind);
-    PK_REQUIRE(n_long == 0 || partial_dev != nullptr, "pk_spmm_csr: partial buffer required");
+    PK_REQUIRE(x_kind == PK_VAL_F32 || x_kind == PK_VAL_F64, "pk_spmm_csr_ex: bad x_kind %d", x_kind);
     PK_REQUIRE(row_base >= 0 && (accumulate || row_base == 0), "pk_spmm_csr_ex: a row base needs accumulate (block 0 has base 0)");
+    const bool x32 = x_kind == PK_VAL_F32, x16 = ((uintptr_t)X_dev) % 16 == 0;
+    if (x32 && !(nc % 4 == 0 && ldx % 4 == 0 && x16)) {       // groups mapping only: one 16-byte load = 4 columns
+        pk_set_error("pk_spmm_csr_ex: an fp32 dense block needs nc %% 4 == 0, ldx %% 4 == 0 and 16-byte alignment");
+        return PK_E_UNSUPPORTED;
+    }
+    if (int rc = spmm_check("pk_spmm_csr_ex", n_tasks >= 0, false, nc, X_dev, ldx, ldo, n_long, partial_dev, val_kind)) return rc;
     if (n_tasks == 0) return PK_OK;
     hipStream_t st = pk_stream(stream);
-    int rc;
-    if (val_kind == PK_VAL_F32)
-        rc = launch_spmm<float>(st, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev,
-                                indices_dev, vals_dev, X_dev, x_kind, ldx, nc, out_dev, ldo, partial_dev, row_base, accumulate, x_rows);
-    else if (val_kind == PK_VAL_F64)
-        rc = launch_spmm<double>(st, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev,
-                                 indices_dev, vals_dev, X_dev, x_kind, ldx, nc, out_dev, ldo, partial_dev, row_base, accumulate, x_rows);
-    else {
-        pk_set_error("pk_spmm_csr: bad val_kind %d", val_kind);
-        return PK_E_INVALID;
+    const dim3 grid((unsigned)pk_ceil_div(n_tasks, 4)), block(256);
+    if (x32 || (nc % 2 == 0 && ldx % 2 == 0 && x16)) {
+        spmm_if(x32, [&](auto xf) {
+            using XT = std::conditional_t<decltype(xf)::value, float, double>;
+            spmm_groups_instance(val_kind, nc, spmm_off32(x_rows, ldx, sizeof(XT)), [&](auto vt, auto g, auto o) {
+                spmm_if(accumulate != 0, [&](auto acc) {
+                    hipLaunchKernelGGL((spmm_csr_groups_kernel<decltype(vt), decltype(g)::value, XT, decltype(acc)::value, decltype(o)::value>),
+                                       grid, block, 0, st, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev,
+                                       static_cast<const decltype(vt) *>(vals_dev), static_cast<const XT *>(X_dev), ldx, nc, out_dev, ldo,
+                                       partial_dev, row_base);
+                });
+            });
+        });
+    } else {
+        // an fp64 block that is odd, odd-strided or not 16-byte aligned: a column per lane, CPL = ceil(nc / 64) of them
+        spmm_if(val_kind == PK_VAL_F32, [&](auto v32) {
+            using VT = std::conditional_t<decltype(v32)::value, float, double>;
+            spmm_if(accumulate != 0, [&](auto acc) {
+                auto launch = [&](auto cpl) {
+                    hipLaunchKernelGGL((spmm_csr_kernel<VT, decltype(cpl)::value, decltype(acc)::value>), grid, block, 0, st, n_tasks,
+                                       task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev,
+                                       static_cast<const VT *>(vals_dev), static_cast<const double *>(X_dev), ldx, nc, out_dev, ldo,
+                                       partial_dev, row_base);
+                };
+                if (nc <= 64) launch(std::integral_constant<int, 1>());
+                else if (nc <= 128) launch(std::integral_constant<int, 2>());
+                else if (nc <= 192) launch(std::integral_constant<int, 3>());
+                else launch(std::integral_constant<int, 4>());
+            });
+        });
     }
-    if (rc != PK_OK) return rc;
     PK_CHECK_LAUNCH("spmm_csr_kernel");
-    if (n_long > 0) {
-        hipLaunchKernelGGL(spmm_fixup_kernel, dim3((unsigned)n_long), dim3(256), 0, st, n_long, long_row_dev,
-                           long_slot_begin_dev, long_slot_end_dev, partial_dev, nc, out_dev, ldo, row_base, accumulate);
-        PK_CHECK_LAUNCH("spmm_fixup_kernel");
-    }
-    return PK_OK;
-}
-
-extern "C" int pk_spmm_csr_x(void *stream, int64_t n_tasks, const int32_t *task_row_dev,
-                             const int64_t *task_begin_dev, const int64_t *task_end_dev,
-                             const int32_t *task_slot_dev, int64_t n_long, const int32_t *long_row_dev,
-                             const int32_t *long_slot_begin_dev, const int32_t *long_slot_end_dev,
-                             const int32_t *indices_dev, const void *vals_dev, int val_kind,
-                             const void *X_dev, int x_kind, int64_t ldx, int32_t nc, double *out_dev, int64_t ldo,
-                             double *partial_dev) {
-    return pk_spmm_csr_ex(stream, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, n_long,
-                          long_row_dev, long_slot_begin_dev, long_slot_end_dev, indices_dev, vals_dev, val_kind, X_dev,
-                          x_kind, ldx, nc, out_dev, ldo, partial_dev, 0, 0, 0);
-}
-
-extern "C" int pk_spmm_csr_f64(void *stream, int64_t n_tasks, const int32_t *task_row_dev,
-                               const int64_t *task_begin_dev, const int64_t *task_end_dev,
-                               const int32_t *task_slot_dev, int64_t n_long, const int32_t *long_row_dev,
-                               const int32_t *long_slot_begin_dev, const int32_t *long_slot_end_dev,
-                               const int32_t *indices_dev, const void *vals_dev, int val_kind,
-                               const double *X_dev, int64_t ldx, int32_t nc, double *out_dev, int64_t ldo,
-                               double *partial_dev) {
-    return pk_spmm_csr_ex(stream, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, n_long,
-                          long_row_dev, long_slot_begin_dev, long_slot_end_dev, indices_dev, vals_dev, val_kind, X_dev,
-                          PK_VAL_F64, ldx, nc, out_dev, ldo, partial_dev, 0, 0, 0);
+    return launch_spmm_fixup(st, n_long, long_row_dev, long_slot_begin_dev, long_slot_end_dev, partial_dev, nc, out_dev, ldo, row_base,
+                             accumulate, nullptr, 0);
 }
 
 // ---- the product restricted to flagged rows (fp64 dense block) ---------------------------------------------------------
-template <typename VT>
-static int launch_spmm_flagged(hipStream_t st, int64_t n_tasks, const int32_t *task_row, const int64_t *task_begin,
-                               const int64_t *task_end, const int32_t *task_slot, const int32_t *indices, const void *vals,
-                               const double *X, int64_t ldx, int nc, double *out, int64_t ldo, double *partial, int64_t x_rows,
-                               const int32_t *row_flags, int flag_mask) {
-    dim3 grid((unsigned)pk_ceil_div(n_tasks, 4)), block(256);
-    const VT *v = static_cast<const VT *>(vals);
-    const bool off32 = x_rows > 0 && x_rows < (1 << 24) && ldx * 8 < (1 << 24) && x_rows * ldx * 8 < ((int64_t)1 << 32);
-#define PK_SPMM_LAUNCH_P(G, O)                                                                                          \
-    hipLaunchKernelGGL((spmm_csr_groups_kernel<VT, G, double, false, O, true>), grid, block, 0, st, n_tasks, task_row,  \
-                       task_begin, task_end, task_slot, indices, v, X, ldx, nc, out, ldo, partial, (int64_t)0, row_flags, flag_mask)
-#define PK_SPMM_GROUPS_P(G) do { if (off32) PK_SPMM_LAUNCH_P(G, true); else PK_SPMM_LAUNCH_P(G, false); } while (0)
-    if (nc <= 16) PK_SPMM_GROUPS_P(16);
-    else if (nc <= 32) PK_SPMM_GROUPS_P(8);
-    else if (nc <= 64) PK_SPMM_GROUPS_P(4);
-    else if (nc <= 128) PK_SPMM_GROUPS_P(2);
-    else PK_SPMM_GROUPS_P(1);
-#undef PK_SPMM_GROUPS_P
-#undef PK_SPMM_LAUNCH_P
-    return PK_OK;
-}
-
 extern "C" int pk_spmm_csr_flagged_f64(void *stream, int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
                                        const int64_t *task_end_dev, const int32_t *task_slot_dev, int64_t n_long,
                                        const int32_t *long_row_dev, const int32_t *long_slot_begin_dev,
                                        const int32_t *long_slot_end_dev, const int32_t *indices_dev, const void *vals_dev,
                                        int val_kind, const double *X_dev, int64_t ldx, int32_t nc, double *out_dev, int64_t ldo,
                                        double *partial_dev, int64_t x_rows, const int32_t *row_flags_dev, int32_t flag_mask) {
-    PK_REQUIRE(n_tasks >= 0 && nc >= 2 && nc <= 256 && nc % 2 == 0, "pk_spmm_csr_flagged_f64: nc=%d (even, 2..256)", nc);
-    PK_REQUIRE(ldo >= nc && ldx >= nc && ldx % 2 == 0 && (((uintptr_t)X_dev) % 16) == 0, "pk_spmm_csr_flagged_f64: ldx even, X 16-byte aligned");
     PK_REQUIRE(row_flags_dev != nullptr, "pk_spmm_csr_flagged_f64: row flags required");
-    PK_REQUIRE(n_long == 0 || partial_dev != nullptr, "pk_spmm_csr_flagged_f64: partial buffer required");
-    PK_REQUIRE(val_kind == PK_VAL_F32 || val_kind == PK_VAL_F64, "pk_spmm_csr_flagged_f64: bad val_kind %d", val_kind);
+    if (int rc = spmm_check("pk_spmm_csr_flagged_f64", n_tasks >= 0, true, nc, X_dev, ldx, ldo, n_long, partial_dev, val_kind)) return rc;
     if (n_tasks == 0) return PK_OK;
     hipStream_t st = pk_stream(stream);
-    if (val_kind == PK_VAL_F32)
-        launch_spmm_flagged<float>(st, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev, vals_dev, X_dev,
-                                   ldx, nc, out_dev, ldo, partial_dev, x_rows, row_flags_dev, flag_mask);
-    else
-        launch_spmm_flagged<double>(st, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev, vals_dev, X_dev,
-                                    ldx, nc, out_dev, ldo, partial_dev, x_rows, row_flags_dev, flag_mask);
+    const dim3 grid((unsigned)pk_ceil_div(n_tasks, 4)), block(256);
+    spmm_groups_instance(val_kind, nc, spmm_off32(x_rows, ldx, 8), [&](auto vt, auto g, auto o) {
+        hipLaunchKernelGGL((spmm_csr_groups_kernel<decltype(vt), decltype(g)::value, double, false, decltype(o)::value, true>), grid, block,
+                           0, st, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev,
+                           static_cast<const decltype(vt) *>(vals_dev), X_dev, ldx, nc, out_dev, ldo, partial_dev, (int64_t)0,
+                           row_flags_dev, flag_mask);
+    });
     PK_CHECK_LAUNCH("spmm_csr_groups_kernel (flagged rows)");
-    if (n_long > 0) {
-        hipLaunchKernelGGL(spmm_fixup_kernel, dim3((unsigned)n_long), dim3(256), 0, st, n_long, long_row_dev, long_slot_begin_dev,
-                           long_slot_end_dev, partial_dev, nc, out_dev, ldo, (int64_t)0, 0, row_flags_dev, flag_mask);
-        PK_CHECK_LAUNCH("spmm_fixup_kernel (flagged rows)");
-    }
-    return PK_OK;
+    return launch_spmm_fixup(st, n_long, long_row_dev, long_slot_begin_dev, long_slot_end_dev, partial_dev, nc, out_dev, ldo, 0, 0,
+                             row_flags_dev, flag_mask);
 }
 
 // eager load of this translation unit's code object (pk_warm_up, api.cpp): the runtime loads a code object at the first
@@ -590,38 +534,19 @@ extern "C" int pk_spmm_csr_rows_list_f64(void *stream, int64_t cap, const int32_
                                          const int32_t *indices_dev, const void *vals_dev, int val_kind, const double *X_dev, int64_t ldx,
                                          int32_t nc, double *out_dev, int64_t ldo, double *partial_dev, int64_t x_rows,
                                          const int32_t *row_flags_dev, int32_t flag_mask) {
-    PK_REQUIRE(cap >= 1 && nc >= 2 && nc <= 256 && nc % 2 == 0, "pk_spmm_csr_rows_list_f64: nc=%d (even, 2..256)", nc);
-    PK_REQUIRE(ldo >= nc && ldx >= nc && ldx % 2 == 0 && (((uintptr_t)X_dev) % 16) == 0, "pk_spmm_csr_rows_list_f64: ldx even, X 16-byte aligned");
     PK_REQUIRE(list_dev && count_dev && row_first_task_dev && task_row_dev, "pk_spmm_csr_rows_list_f64: bad pointers");
-    PK_REQUIRE(n_long == 0 || (partial_dev != nullptr && row_flags_dev != nullptr), "pk_spmm_csr_rows_list_f64: split rows need the partial buffer and the row flags");
-    PK_REQUIRE(val_kind == PK_VAL_F32 || val_kind == PK_VAL_F64, "pk_spmm_csr_rows_list_f64: bad val_kind %d", val_kind);
+    PK_REQUIRE(n_long == 0 || row_flags_dev != nullptr, "pk_spmm_csr_rows_list_f64: split rows need the row flags");
+    if (int rc = spmm_check("pk_spmm_csr_rows_list_f64", cap >= 1, true, nc, X_dev, ldx, ldo, n_long, partial_dev, val_kind)) return rc;
     hipStream_t st = pk_stream(stream);
-    int64_t wgs = cap;                 // one workgroup per listed row, at most 4 096 of them in flight (the rest in turn)
-    if (wgs > 4096) wgs = 4096;
-    const dim3 grid((unsigned)wgs), block(64 * PK_LIST_WAVES);
-    const bool off32 = x_rows > 0 && x_rows < (1 << 24) && ldx * 8 < (1 << 24) && x_rows * ldx * 8 < ((int64_t)1 << 32);
-#define PK_LIST_LAUNCH(VT, G, O)                                                                                             \
-    hipLaunchKernelGGL((spmm_csr_rows_list_kernel<VT, G, O>), grid, block, 0, st, cap, list_dev, count_dev, row_offset,      \
-                       row_first_task_dev, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev,           \
-                       static_cast<const VT *>(vals_dev), X_dev, ldx, nc, out_dev, ldo, partial_dev)
-#define PK_LIST_GROUPS(VT, G) do { if (off32) PK_LIST_LAUNCH(VT, G, true); else PK_LIST_LAUNCH(VT, G, false); } while (0)
-#define PK_LIST_NC(VT)                                                                                                       \
-    do {                                                                                                                     \
-        if (nc <= 16) PK_LIST_GROUPS(VT, 16);                                                                                \
-        else if (nc <= 32) PK_LIST_GROUPS(VT, 8);                                                                            \
-        else if (nc <= 64) PK_LIST_GROUPS(VT, 4);                                                                            \
-        else if (nc <= 128) PK_LIST_GROUPS(VT, 2);                                                                           \
-        else PK_LIST_GROUPS(VT, 1);                                                                                          \
-    } while (0)
-    if (val_kind == PK_VAL_F32) PK_LIST_NC(float); else PK_LIST_NC(double);
-#undef PK_LIST_NC
-#undef PK_LIST_GROUPS
-#undef PK_LIST_LAUNCH
+    // one workgroup per listed row, at most 4 096 of them in flight (the rest in turn)
+    const dim3 grid((unsigned)std::min<int64_t>(cap, 4096)), block(64 * PK_LIST_WAVES);
+    spmm_groups_instance(val_kind, nc, spmm_off32(x_rows, ldx, 8), [&](auto vt, auto g, auto o) {
+        hipLaunchKernelGGL((spmm_csr_rows_list_kernel<decltype(vt), decltype(g)::value, decltype(o)::value>), grid, block, 0, st, cap,
+                           list_dev, count_dev, row_offset, row_first_task_dev, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev,
+                           indices_dev, static_cast<const decltype(vt) *>(vals_dev), X_dev, ldx, nc, out_dev, ldo, partial_dev);
+    });
     PK_CHECK_LAUNCH("spmm_csr_rows_list_kernel");
-    if (n_long > 0) {
-        hipLaunchKernelGGL(spmm_fixup_kernel, dim3((unsigned)n_long), dim3(256), 0, st, n_long, long_row_dev, long_slot_begin_dev,
-                           long_slot_end_dev, partial_dev, nc, out_dev, ldo, (int64_t)0, 0, row_flags_dev, flag_mask);
-        PK_CHECK_LAUNCH("spmm_fixup_kernel (listed rows)");
-    }
-    return PK_OK;
+    return launch_spmm_fixup(st, n_long, long_row_dev, long_slot_begin_dev, long_slot_end_dev, partial_dev, nc, out_dev, ldo, 0, 0,
+                             row_flags_dev, flag_mask);
 }
+

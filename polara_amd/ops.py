@@ -897,22 +897,26 @@ class HipOps:
         rng = (0, A.n_tasks, 0, A.n_long) if rows is None else A.task_range(int(rows[0]), int(rows[1]))
         return self._spmm_launch(A, X, out, rng)
 
+    @staticmethod
+    def _plan_side(A, rng):
+        """the eight plan arguments of a row-task entry for the plan slice `rng` = (first task, tasks, first long row, long
+        rows): the four task arrays from the first task on, the long-row count, the three long-row arrays from the first long row on"""
+        p = A.plan
+        t0, _, l0, n_long = rng
+        return (_ptr(p['task_row'], t0), _ptr(p['task_begin'], t0), _ptr(p['task_end'], t0), _ptr(p['task_slot'], t0), n_long,
+                _ptr(p['long_row'], l0), _ptr(p['long_slot_begin'], l0), _ptr(p['long_slot_end'], l0))
+
     def _spmm_launch(self, A, X, out, rng, row_base=0, accumulate=False, meta_shape=None):
         """one launch of the row-task kernel over the plan slice `rng` = (first task, tasks, first long row, long rows)"""
         nc = X.shape[1]
         x_kind = _lib.PK_VAL_F64 if X.dtype == torch.float64 else _lib.PK_VAL_F32
-        p = A.plan
-        t0, n_tasks, l0, n_long = rng
-        tr, tb, te, ts = p['task_row'], p['task_begin'], p['task_end'], p['task_slot']
-        lr, lb, le = p['long_row'], p['long_slot_begin'], p['long_slot_end']
         meta = None
         if self.timers is not None:   # (output rows, source rows, nnz, nc, value bytes, dense element bytes) of this launch
             shp = meta_shape or (A.shape[0], A.shape[1], A.nnz)
             meta = (shp[0], shp[1], shp[2], nc, A.values.element_size(), X.element_size())
         with self._timed('spmm', meta):
             _lib.check(self.lib.pk_spmm_csr_ex(
-                self.stream(), n_tasks, _ptr(tr, t0), _ptr(tb, t0), _ptr(te, t0), _ptr(ts, t0), n_long,
-                _ptr(lr, l0), _ptr(lb, l0), _ptr(le, l0), _ptr(A.indices), _ptr(A.values), A.val_kind,
+                self.stream(), rng[1], *self._plan_side(A, rng), _ptr(A.indices), _ptr(A.values), A.val_kind,
                 _ptr(X), x_kind, X.stride(0), nc, _ptr(out), out.stride(0), _ptr(A.partial(nc)), int(row_base),
                 1 if accumulate else 0, int(X.shape[0])), 'pk_spmm_csr_ex')
         return out
@@ -923,14 +927,11 @@ class HipOps:
         assert X.dtype == torch.float64 and X.stride(1) == 1 and X.shape[0] == A.shape[1] and out.stride(1) == 1
         assert row_flags.dtype == torch.int32 and row_flags.is_contiguous() and row_flags.numel() == A.shape[0]
         nc = X.shape[1]
-        t0, n_tasks, l0, n_long = (0, A.n_tasks, 0, A.n_long) if rows is None else A.task_range(int(rows[0]), int(rows[1]))
-        p = A.plan
+        rng = (0, A.n_tasks, 0, A.n_long) if rows is None else A.task_range(int(rows[0]), int(rows[1]))
         with self._timed('spmm_flagged', (A.shape[0], nc)):
             _lib.check(self.lib.pk_spmm_csr_flagged_f64(
-                self.stream(), n_tasks, _ptr(p['task_row'], t0), _ptr(p['task_begin'], t0), _ptr(p['task_end'], t0),
-                _ptr(p['task_slot'], t0), n_long, _ptr(p['long_row'], l0), _ptr(p['long_slot_begin'], l0),
-                _ptr(p['long_slot_end'], l0), _ptr(A.indices), _ptr(A.values), A.val_kind, _ptr(X), X.stride(0), nc,
-                _ptr(out), out.stride(0), _ptr(A.partial(nc)), int(X.shape[0]), _ptr(row_flags), int(mask)),
+                self.stream(), rng[1], *self._plan_side(A, rng), _ptr(A.indices), _ptr(A.values), A.val_kind, _ptr(X),
+                X.stride(0), nc, _ptr(out), out.stride(0), _ptr(A.partial(nc)), int(X.shape[0]), _ptr(row_flags), int(mask)),
                 'pk_spmm_csr_flagged_f64')
         return out
 
@@ -942,16 +943,14 @@ class HipOps:
         assert lst.dtype == torch.int32 and cnt.dtype == torch.int32 and row_flags.dtype == torch.int32 and row_flags.numel() == A.shape[0]
         nc = X.shape[1]
         lo = 0 if rows is None else int(rows[0])
+        # (the task arrays of the WHOLE plan — the kernel finds a listed row's tasks itself —, the long rows of the row range)
         _, _, l0, n_long = (0, A.n_tasks, 0, A.n_long) if rows is None else A.task_range(int(rows[0]), int(rows[1]))
-        p = A.plan
         rft = A._ensure_plan()['row_first_task']
         with self._timed('spmm_rows_list', (int(lst.numel()), nc)):
             _lib.check(self.lib.pk_spmm_csr_rows_list_f64(
-                self.stream(), int(lst.numel()), _ptr(lst), _ptr(cnt), lo, _ptr(rft), _ptr(p['task_row']), _ptr(p['task_begin']),
-                _ptr(p['task_end']), _ptr(p['task_slot']), n_long, _ptr(p['long_row'], l0), _ptr(p['long_slot_begin'], l0),
-                _ptr(p['long_slot_end'], l0), _ptr(A.indices), _ptr(A.values), A.val_kind, _ptr(X), X.stride(0), nc,
-                _ptr(out), out.stride(0), _ptr(A.partial(nc)), int(X.shape[0]), _ptr(row_flags), int(mask)),
-                'pk_spmm_csr_rows_list_f64')
+                self.stream(), int(lst.numel()), _ptr(lst), _ptr(cnt), lo, _ptr(rft), *self._plan_side(A, (0, A.n_tasks, l0, n_long)),
+                _ptr(A.indices), _ptr(A.values), A.val_kind, _ptr(X), X.stride(0), nc, _ptr(out), out.stride(0),
+                _ptr(A.partial(nc)), int(X.shape[0]), _ptr(row_flags), int(mask)), 'pk_spmm_csr_rows_list_f64')
         return out
 
     def spmm_flagged_ok(self, X):

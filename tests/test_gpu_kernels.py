@@ -63,7 +63,7 @@ def test_spmm_matches_scipy(hip_ops, nc, vdtype):
 
 @pytest.mark.parametrize('nc', [4, 52, 64, 104, 204])
 def test_spmm_fp32_dense_block(hip_ops, nc):
-    """pk_spmm_csr_x with an fp32 dense block (the approximate fold-in): fp64 accumulation of fl32(X)."""
+    """pk_spmm_csr_ex with an fp32 dense block (the approximate fold-in): fp64 accumulation of fl32(X)."""
     import torch
     rng = np.random.RandomState(nc)
     n_rows, n_cols = 700, 900

@@ -3,19 +3,19 @@ pipelines, against NumPy on data whose result does not depend on the summation o
 
 The launchers pick an instance by the value type of A, the type of the dense block, the mapping (GROUPS 16 / 8 / 4 / 2 / 1 for
 an even, even-strided, 16-byte aligned block, else column-per-lane with CPL 1..4), ACC, OFF32 and PRED (plus the list-driven
-kernel); the test ids spell the instance out, so that the branches of launch_spmm, launch_spmm_flagged, PK_LIST_NC and
-PK_TTM_LAUNCH can be ticked off from `pytest --collect-only`:
+kernel); the test ids spell the instance out, so that the branches of spmm_groups / spmm_groups_instance, of the three
+entries that call them and of PK_TTM_LAUNCH can be ticked off from `pytest --collect-only`:
 
   test                                     id                                             branch
-  test_spmm_exact                          x64_groups{16,8,4,2,1}_nc*_vals{32,64}_acc0_off32  PK_SPMM_GROUPS, both edges of every class
-                                           x32_groups*_nc*_vals*_acc0_off32                   PK_SPMM_GROUPS_F
-                                           x64_cpl{1,2,3,4}_nc*_vals*_acc0                    PK_SPMM_CASE; ..._oddld / ..._misaligned:
+  test_spmm_exact                          x64_groups{16,8,4,2,1}_nc*_vals{32,64}_acc0_off32  spmm_groups under pk_spmm_csr_ex, XT = double, both edges of every class
+                                           x32_groups*_nc*_vals*_acc0_off32                   the same, XT = float
+                                           x64_cpl{1,2,3,4}_nc*_vals*_acc0                    its column-per-lane branch; ..._oddld / ..._misaligned:
                                                                                               even nc that must leave the paired kernel
   test_spmm_accumulate                     ..._acc1_off32                                     the ACC twins, `HipOps.spmm_acc`
   test_spmm_accumulate_row_block           ..._acc1_off32_rows150to209                        ACC with row_base
   test_spmm_offsets                        ..._acc{0,1}_off64                                 OFF32 = false (x_rows = 0), bits of off32
-  test_spmm_stride_at_the_24_bit_edge      x*_groups16_nc8_stride*_off{32,64}                 the largest stride of OFF32, the next one
-  test_spmm_flagged / test_spmm_rows_list  flagged_/listed_x64_groups*_nc*_vals*_off{32,64}   PK_SPMM_GROUPS_P / PK_LIST_NC
+  test_spmm_stride_at_the_24_bit_edge      x*_groups16_nc8_stride*_off{32,64}                 spmm_off32: the largest stride of OFF32, the next one
+  test_spmm_flagged / test_spmm_rows_list  flagged_/listed_x64_groups*_nc*_vals*_off{32,64}   spmm_groups_instance under pk_spmm_csr_flagged_f64 / pk_spmm_csr_rows_list_f64
   test_spmm_rounded                        rounded_x*_{groups*,cpl*}_nc*_vals*                the precision of every mapping's sums
   test_spmm_plan_with_many_slots           x64_groups4_nc64_vals32_acc0_off32_split64         rows of 2..24 slots
   test_ttm_exact / test_ttm_rounded        ttm_epl{1,2,4,8,16}_ra*_rb*_vals{1,0}              PK_TTM_LAUNCH, both edges of every class
