@@ -530,7 +530,13 @@ int pk_spmm_csr_rows_list_f64(void *stream, int64_t cap, const int32_t *list_dev
  * tab_dev (96 doubles), info_dev (int32: 0 = ok, else the factors are outside the format's range: use the fp32 image);
  * work_dev: 768 bytes.  pk_q20_decode_f64: the rows exactly as the fold-in reads them, [n x (K + 1)], column K = D_j
  * (tests, diagnostics).  pk_fold_q20: the row-task plan of pk_spmm_csr_ex; non-negative values only (w_u is a bound
- * for a_uj >= 0); the partial buffer holds Kx doubles per slot. */
+ * for a_uj >= 0); the partial buffer holds Kx doubles per slot.  Every row a launch touches is written in full: columns
+ * 0 .. K, columns K+1 .. Kx-1 as zero, a row without entries as Kx zeros (a row outside the launch's tasks keeps what it held);
+ * column K of a row is kappa * (its sum of weight windows), rounded once per task — a split row's is the sum of its
+ * tasks' in slot order.  The padded lanes of a task's last chunk (and a task without entries) gather image row 0 with
+ * weight 0: row 0 of the image must be allocated, and tab_dev must be finite (0 * tab[b] * window is then 0 whatever the
+ * bits of row 0).  Errors (rank above 202, Kx <= K, ldo < Kx, a val_kind other than PK_VAL_F32 / PK_VAL_F64, split rows
+ * without a partial buffer, n_items >= 2^24 or an image of 4 GiB) are returned before anything is launched. */
 int32_t pk_q20_lanes(int32_t K);
 double pk_q20_kappa(int32_t K);
 int64_t pk_q20_image_bytes(int64_t n, int32_t K);

@@ -77,6 +77,21 @@ def decode(img, tab, K):
     return out
 
 
+def pack(p, dig):
+    """p: int [n, L, 6] 20-bit fields, dig: int [n, L] 8-bit digits (two's complement, or already masked) -> img uint8
+    [n, L*16]: the four little-endian dwords of every lane piece, digit first"""
+    p = np.asarray(p).astype(np.int64) & 0xFFFFF
+    db = np.asarray(dig).astype(np.int64) & 0xFF
+    n, L = db.shape
+    assert p.shape == (n, L, 6)
+    d = np.zeros((n, L, 4), dtype=np.uint32)
+    d[..., 0] = ((db << 24) | (p[:, :, 0] << 4) | (p[:, :, 1] >> 16)).astype(np.uint32)
+    d[..., 1] = (((p[:, :, 1] & 0xFFFF) << 16) | (p[:, :, 2] >> 4)).astype(np.uint32)
+    d[..., 2] = (((p[:, :, 2] & 0xF) << 28) | (p[:, :, 3] << 8) | (p[:, :, 4] >> 12)).astype(np.uint32)
+    d[..., 3] = (((p[:, :, 4] & 0xFFF) << 20) | p[:, :, 5]).astype(np.uint32)
+    return d.reshape(n, L * 4).view(np.uint8).reshape(n, L * 16)
+
+
 def encode(V):
     """(img uint8 [n, L*16], tab fp64 [96]) by the algorithm of q20_encode_kernel"""
     V = np.asarray(V, dtype=np.float64)
@@ -131,10 +146,4 @@ def encode(V):
     dw = np.where((s > 0) & (dw <= 127.0) & (f32(np.clip(dw, -128, 127) * 16777216.0 + GL) < Y), dw + 1.0, dw)
     assert dw.max() <= 127.0, 'kappa too small'
     dig[:, L - 1] = np.maximum(dw, -128.0)
-    db = dig.astype(np.int64) & 0xFF
-    d = np.zeros((n, L, 4), dtype=np.uint32)
-    d[..., 0] = ((db << 24) | (p[:, :, 0] << 4) | (p[:, :, 1] >> 16)).astype(np.uint32)
-    d[..., 1] = (((p[:, :, 1] & 0xFFFF) << 16) | (p[:, :, 2] >> 4)).astype(np.uint32)
-    d[..., 2] = (((p[:, :, 2] & 0xF) << 28) | (p[:, :, 3] << 8) | (p[:, :, 4] >> 12)).astype(np.uint32)
-    d[..., 3] = (((p[:, :, 4] & 0xFFF) << 20) | p[:, :, 5]).astype(np.uint32)
-    return d.reshape(n, L * 4).view(np.uint8).reshape(n, L * 16), tab
+    return pack(p, dig), tab
