@@ -1207,6 +1207,30 @@ int pk_ials_loss_nz_f64(void *stream, int64_t n_rows, int64_t n_cols, int32_t ra
                         int64_t ldy, double *out_dev, void *work_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * iALS++ (csrc/ialspp.hip): the block-subspace solver of Rendle, Krichene, Zhang and Koren for the objective of implicit ALS,
+ * ranks 1 .. pk_ialspp_max_rank() (2048).  E [nnz] caches e = x_u . y_i for the stored entries of C in storage order.
+ * pk_ialspp_predict_f64: E from X [n_rows x rank] and Y [n_cols x rank]; one wave per row, a fixed order of summation.
+ * pk_ialspp_block_step_f64: with pi = [p0, min(p0 + block_size, rank)), block_size 16, 32 or 64, for every row u
+ *     g = r_u + lambda_u x_pi + sum_i ((c_i - 1) e_i - c_i) y_{i,pi},    H = G[pi,pi] + lambda_u I + sum_i (c_i - 1) y_{i,pi} y_{i,pi}^T
+ *     delta = H^-1 g (Cholesky, fp64);    x_pi -= delta;    e_i -= y_{i,pi} . delta          — in place on X and E
+ * with R [n_rows x |pi|] = X G[:,pi] formed by the caller from the X the step starts from, G = Y^T Y [rank x rank], lambda_u =
+ * lambda_rows_dev[u] when that pointer is not null, else lambda.  Rows are taken in row_order_dev (int32 permutation; null:
+ * 0, 1, ..); the order of every summation depends on the row alone: equal inputs give equal bits, whatever the row order.  No
+ * atomics.  An empty row gets x_pi = 0 exactly.  info_dev: two int32 — the number of rows with a pivot that is not > 0 (NaN
+ * included) and the first such row (-1: none); x_pi and e of those rows are left as they were.  work_dev:
+ * pk_ialspp_work_bytes(n_rows, block_size) bytes.  Column ids outside 0 .. n_cols - 1 contribute nothing (predict: e = 0). */
+int32_t pk_ialspp_max_rank(void);
+int64_t pk_ialspp_work_bytes(int64_t n_rows, int32_t block_size);
+int pk_ialspp_block_step_f64(void *stream, int64_t n_rows, int64_t n_cols, int32_t rank, int32_t p0, int32_t block_size,
+                             const int64_t *indptr_dev, const int32_t *indices_dev, const double *conf_dev,
+                             const int32_t *row_order_dev, const double *Y_dev, int64_t ldy, const double *G_dev, int64_t ldg,
+                             double lambda, const double *lambda_rows_dev, const double *R_dev, int64_t ldr, double *X_dev,
+                             int64_t ldx, double *E_dev, int32_t *info_dev, void *work_dev);
+int pk_ialspp_predict_f64(void *stream, int64_t n_rows, int64_t n_cols, int32_t rank, const int64_t *indptr_dev,
+                          const int32_t *indices_dev, const double *X_dev, int64_t ldx, const double *Y_dev, int64_t ldy,
+                          double *E_dev);
+
+/* ------------------------------------------------------------------------------------------
  * K5.  Sparse tensor-times-matrix (CoFFee / HOOI).
  * Replaces numba `dttm_seq` / `dttm_par` (lib/sparse.py:203-234) called from `ttm3d_seq`
  * (lib/tensor.py:7-19):  res[i0, j, k] += val * u[i1, j] * v[i2, k].

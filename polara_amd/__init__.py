@@ -7,6 +7,7 @@
     from polara_amd import LCEModel, LCEModelItemColdStart          # Local Collective Embeddings, standard and item cold start
     from polara_amd import ProbabilisticMF                          # PMF trained by a blocked SGD sweep
     from polara_amd import ImplicitALS                              # iALS / WRMF: alternating least squares, exact per-row solves
+    from polara_amd import ImplicitALSPP                            # iALS++: block-subspace steps of the same objective, ranks to 2048
     from polara_amd import ImplicitBPR                              # BPR-MF: pairwise ranking by a blocked triplet sweep
     from polara_amd import LightFMWrapper, LightFMItemColdStart     # LightFM (WARP, item features), standard and item cold start
     from polara_amd import EASEModel                                # EASE: closed-form item weights on a device SPD inverse
@@ -103,6 +104,7 @@ _EXPORTS = {
     'LCEModel': 'lce', 'LCEModelItemColdStart': 'lce',
     'ProbabilisticMF': 'pmf',
     'ImplicitALS': 'ials',
+    'ImplicitALSPP': 'ialspp',
     'ImplicitBPR': 'bpr',
     'LightFMWrapper': 'warp', 'LightFMItemColdStart': 'warp',
     'TuriFactorizationRecommender': 'fm', 'TuriFactorizationItemColdStart': 'fm',

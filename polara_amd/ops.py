@@ -2875,6 +2875,124 @@ class HipOps:
         gx, gy = self.to_host(GX), self.to_host(GY)
         return float((gx * gy).sum() + float(out[0].item()) + float(regularization) * (np.trace(gx) + np.trace(gy)))
 
+    # ---- iALS++ (csrc/ialspp.hip) ---------------------------------------------------------------------------------------
+    def ialspp_max_rank(self):
+        return int(self.lib.pk_ialspp_max_rank())
+
+    def ialspp_block_sizes(self):
+        return (16, 32, 64)
+
+    def _ialspp_check(self, Cm, X, Y, what, E=None):
+        k = int(Y.shape[1])
+        if k < 1 or k > self.ialspp_max_rank():
+            raise ValueError('iALS++: rank %d outside 1..%d' % (k, self.ialspp_max_rank()))
+        for M, n in ((X, Cm.shape[0]), (Y, Cm.shape[1])):
+            if M is not None and (M.dtype != torch.float64 or M.dim() != 2 or tuple(M.shape) != (n, k) or M.stride(1) != 1
+                                  or M.stride(0) < k):
+                raise ValueError('iALS++ %s: a block of shape %s, strides %s for [%d x %d] fp64 rows'
+                                 % (what, tuple(M.shape), M.stride(), n, k))
+        nnz = int(Cm.indices.numel())
+        if E is not None and (E.dtype != torch.float64 or tuple(E.shape) != (nnz,) or not E.is_contiguous()):
+            raise ValueError('iALS++ %s: predictions of shape %s for %d stored entries (contiguous fp64)' % (what, tuple(E.shape), nnz))
+        return k
+
+    def ialspp_predict(self, Cm, X, Y, out=None):
+        """E [nnz] fp64 in the storage order of the DeviceCSR `Cm`: e = x_u . y_i for every stored entry (u, i)
+        (pk_ialspp_predict_f64).  X [n_rows x k], Y [n_cols x k]; views with a leading dimension are fine."""
+        n_rows, n_cols = Cm.shape
+        E = self.empty(int(Cm.indices.numel())) if out is None else out
+        k = self._ialspp_check(Cm, X, Y, 'predict', E)
+        with self._timed('ialspp_predict', (n_rows, n_cols, int(Cm.indices.numel()), k)):
+            _lib.check(self.lib.pk_ialspp_predict_f64(self.stream(), n_rows, n_cols, k, _ptr(Cm.indptr), _ptr(Cm.indices), _ptr(X),
+                                                      X.stride(0), _ptr(Y), Y.stride(0), _ptr(E)), 'pk_ialspp_predict_f64')
+        return E
+
+    def _ialspp_regularization(self, regularization, n_rows):
+        """(scalar, device vector or None) of a float or a device fp64 vector [n_rows]"""
+        if isinstance(regularization, torch.Tensor):
+            if regularization.dtype != torch.float64 or tuple(regularization.shape) != (n_rows,) or not regularization.is_contiguous():
+                raise ValueError('iALS++: per-row regularization of shape %s for %d rows (contiguous fp64)'
+                                 % (tuple(regularization.shape), n_rows))
+            return 0.0, regularization
+        return float(regularization), None
+
+    def ialspp_block_step(self, Cm, Y, X, E, G, p0, block_size, regularization, R=None, row_order=None):
+        """One block step of iALS++ (pk_ialspp_block_step_f64), IN PLACE on X [n_rows x k] and on the cached predictions E
+        [nnz]: for every row u of the DeviceCSR of confidences `Cm`, with pi = [p0, min(p0 + block_size, k)),
+            g = G[pi,:] x_u + lambda_u x_pi + sum_i ((c_i - 1) e_i - c_i) y_{i,pi},   H = G[pi,pi] + lambda_u I + sum_i (c_i - 1) y_{i,pi} y_{i,pi}^T
+            delta = H^-1 g,   x_pi -= delta,   e_i -= y_{i,pi} . delta
+        against the fixed block Y [n_cols x k], G = Y^T Y.  regularization: a float, or a device fp64 vector of one value per
+        row.  R [n_rows x |pi|] = X G[:,pi] (formed here by `tsmm` when None; it must belong to the X the step starts from).
+        A row whose H is not positive definite raises a ValueError naming how many there are and the first; x_pi and e of
+        those rows are left as they were.  row_order as in `ials_half_step`: never a bit of the result."""
+        n_rows, n_cols = Cm.shape
+        k = self._ialspp_check(Cm, X, Y, 'block step', E)
+        p0, block_size = int(p0), int(block_size)
+        if block_size not in self.ialspp_block_sizes():
+            raise ValueError('iALS++ block step: block size %d is not one of %s' % (block_size, self.ialspp_block_sizes()))
+        if p0 < 0 or p0 >= k:
+            raise ValueError('iALS++ block step: block start %d outside the rank %d' % (p0, k))
+        p1 = min(p0 + block_size, k)
+        if G.dtype != torch.float64 or tuple(G.shape) != (k, k) or G.stride(1) != 1:
+            raise ValueError('iALS++ block step: G of shape %s for rank %d' % (tuple(G.shape), k))
+        lam, lam_rows = self._ialspp_regularization(regularization, n_rows)
+        if R is None:
+            R = self.tsmm(X, G[:, p0:p1]) if n_rows else self.empty(0, p1 - p0)
+        if R.dtype != torch.float64 or tuple(R.shape) != (n_rows, p1 - p0) or R.stride(1) != 1 or (n_rows and R.stride(0) < p1 - p0):
+            raise ValueError('iALS++ block step: R of shape %s, strides %s for [%d x %d] fp64 rows'
+                             % (tuple(R.shape), R.stride(), n_rows, p1 - p0))
+        conf = Cm.values if Cm.values.dtype == torch.float64 else Cm.values.to(torch.float64)
+        order = self._ials_row_order(Cm) if row_order is None else row_order
+        if order.dtype != torch.int32 or order.numel() != n_rows or not order.is_contiguous():
+            raise ValueError('iALS++ block step: row_order must be a contiguous int32 permutation of the %d rows' % n_rows)
+        info = torch.empty(2, dtype=torch.int32, device=self.device)
+        work = self._work(self.lib.pk_ialspp_work_bytes(n_rows, block_size))
+        with self._timed('ialspp_block_step', (n_rows, n_cols, int(Cm.indices.numel()), k, block_size)):
+            _lib.check(self.lib.pk_ialspp_block_step_f64(self.stream(), n_rows, n_cols, k, p0, block_size, _ptr(Cm.indptr),
+                                                         _ptr(Cm.indices), _ptr(conf), _ptr(order), _ptr(Y), Y.stride(0), _ptr(G),
+                                                         G.stride(0), lam, _ptr(lam_rows), _ptr(R), max(R.stride(0), p1 - p0),
+                                                         _ptr(X), X.stride(0), _ptr(E), _ptr(info), _ptr(work)),
+                       'pk_ialspp_block_step_f64')
+        bad, first = (int(v) for v in info.tolist())
+        if bad:
+            raise ValueError('iALS++ block step: %d row(s) whose block system is not positive definite, the first is row %d '
+                             '(their factors are left unchanged)' % (bad, first))
+        return X
+
+    def ialspp_half_sweep(self, Cm, Y, X, G, regularization, block_size, E=None):
+        """One half-sweep of iALS++ in place on X: the predictions of X and Y (into `E` when given), then the block steps
+        over [0, d), [d, 2 d), .. in ascending order.  Returns (X, E)."""
+        E = self.ialspp_predict(Cm, X, Y, out=E)
+        for p0 in range(0, int(Y.shape[1]), int(block_size)):
+            self.ialspp_block_step(Cm, Y, X, E, G, p0, block_size, regularization)
+        return X, E
+
+    def ialspp_loss(self, Cm, X, Y, reg_rows, reg_cols, GX=None, GY=None):
+        """The objective of iALS++ as a float:  sum over ALL pairs of w (p - x_u . y_i)^2 + sum_u reg_rows[u] |x_u|^2 +
+        sum_i reg_cols[i] |y_i|^2  (reg_rows / reg_cols: floats or device fp64 vectors) =  tr(X^T X Y^T Y) + the sparse term
+        + the regularisation.  The sparse term is pk_ials_loss_nz_f64's up to its rank; above it, it is summed from the
+        predictions (pk_ialspp_predict_f64) and the confidences."""
+        n_rows, n_cols = Cm.shape
+        k = self._ialspp_check(Cm, X, Y, 'loss')
+        GX = self.gram(X) if GX is None else GX
+        GY = self.gram(Y) if GY is None else GY
+        conf = Cm.values if Cm.values.dtype == torch.float64 else Cm.values.to(torch.float64)
+        if k <= self.ials_max_rank():
+            out = self.empty(1)
+            work = self._work(self.lib.pk_ials_work_bytes(n_rows, k))
+            _lib.check(self.lib.pk_ials_loss_nz_f64(self.stream(), n_rows, n_cols, k, _ptr(Cm.indptr), _ptr(Cm.indices), _ptr(conf),
+                                                    _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), _ptr(out), _ptr(work)),
+                       'pk_ials_loss_nz_f64')
+            sparse = float(out[0].item())
+        else:
+            s = self.ialspp_predict(Cm, X, Y)
+            sparse = float((conf * (1.0 - s) ** 2 - s * s).sum().item())
+        reg = 0.0
+        for lam, M, Gm, n in ((reg_rows, X, GX, n_rows), (reg_cols, Y, GY, n_cols)):
+            lam, lam_rows = self._ialspp_regularization(lam, n)
+            reg += float(lam * torch.trace(Gm).item()) if lam_rows is None else float((lam_rows * (M * M).sum(dim=1)).sum().item())
+        return float((self.to_host(GX) * self.to_host(GY)).sum() + sparse + reg)
+
     def dense_scores(self, V, E):
         n_rows, K = E.shape
         n_items = V.shape[0]
