@@ -671,6 +671,15 @@ int pk_spsp_topk(void *stream, int64_t n_rows, int64_t n_inner, int64_t n_cols, 
                  const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind, const int64_t *b_indptr_dev,
                  const int32_t *b_indices_dev, const double *b_values_dev, int32_t topk, int32_t filter_seen, int32_t sparse,
                  int64_t *out_idx_dev, double *out_scores_dev, void *work_dev);
+/* pk_spsp_topk with the seen set handed over: row r of the pattern CSR (seen_indptr_dev int64 [n_rows + 1], seen_indices_dev
+ * int32, columns < n_cols ascending per row) holds the seen columns of row r under filter_seen, so n_inner != n_cols is
+ * allowed.  Classes, order, pads, score bits and work size are those of pk_spsp_topk; with the pattern of L as the seen set
+ * and n_inner == n_cols the two entries return the same bits. */
+int pk_spsp_topk_seen(void *stream, int64_t n_rows, int64_t n_inner, int64_t n_cols, const int64_t *l_indptr_dev,
+                      const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind, const int64_t *b_indptr_dev,
+                      const int32_t *b_indices_dev, const double *b_values_dev, const int64_t *seen_indptr_dev,
+                      const int32_t *seen_indices_dev, int32_t topk, int32_t filter_seen, int32_t sparse, int64_t *out_idx_dev,
+                      double *out_scores_dev, void *work_dev);
 /* The same sums of rows [row0, row0 + n_rows) of L as a dense fp64 block: out_dev[(r - row0) * ld + c] for c < n_cols
  * (ld >= n_cols; the columns beyond n_cols are not written). */
 int pk_spsp_rows_f64(void *stream, int64_t row0, int64_t n_rows, int64_t n_inner, int64_t n_cols, const int64_t *l_indptr_dev,
@@ -905,6 +914,29 @@ int32_t pk_knn_max_neighbours(void);
 int pk_knn_prune_f64(void *stream, int64_t n, const double *G_dev, int64_t ldg, int32_t kind, const double *row_dev,
                      const double *col_dev, double shrink, int32_t K, int32_t normalize, int32_t *count_dev, int32_t *idx_dev,
                      double *val_dev);
+
+/* ---- the neighbour pass without an image (csrc/uknn.hip): UserKNN, and ItemKNN / RP3beta with gram = 'sparse' ----------
+ * The pruning pass above over a row of L . B formed from the sparse operands of pk_spsp_topk (L: CSR [n_rows x n_inner],
+ * int64 indptr, int32 indices, values of kind l_val_kind; B: canonical fp64 CSR [n_inner x n_cols]) instead of a row of
+ * an image.  For row r and column c < n_cols:
+ *   g           the sum of pk_spsp_topk: the products added in ascending position of the left row from +0.0, each a
+ *               separately rounded multiply and add, -0 stored as +0 (an inner index outside [0, n_inner) is skipped)
+ *   w           from g, row[r], col[c] and shrink by the three formulas and rounding rules above (no contraction, the
+ *               correctly rounded quotient)
+ *   candidate   c != exclude[r] (when exclude_dev is given and exclude[r] >= 0), g != 0, w finite and w != 0
+ *   kept, output order (ascending c, pads idx -1 / val 0) and normalize: exactly as pk_knn_prune_f64
+ * row_dev [n_rows] and col_dev [n_cols] fp64; exclude_dev int32 [n_rows] or NULL; count_dev int32 [n_rows], idx_dev int32
+ * [n_rows x K], val_dev fp64 [n_rows x K].  1 <= K <= the largest K of the pruning pass, n_cols < 2^30, shrink finite and
+ * >= 0, no other pointer NULL: checked before any device work.  work >= the bytes the work-size function returns.
+ * A (row, window) grid accumulates in LDS, forms the keys in place and sorts a touched window; the merge of pk_i2i_topk
+ * joins a row's windows and a finishing kernel orders, normalises and writes the slots.  Rows are chunked under the
+ * candidate budget of pk_i2i_topk.  No atomics on results, no cross-workgroup ordering: equal inputs give equal bits. */
+int64_t pk_spsp_knn_work_bytes(int64_t n_rows, int64_t n_cols, int32_t K);
+int pk_spsp_knn_f64(void *stream, int64_t n_rows, int64_t n_inner, int64_t n_cols, const int64_t *l_indptr_dev,
+                    const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind, const int64_t *b_indptr_dev,
+                    const int32_t *b_indices_dev, const double *b_values_dev, int32_t kind, const double *row_dev,
+                    const double *col_dev, double shrink, const int32_t *exclude_dev, int32_t K, int32_t normalize,
+                    int32_t *count_dev, int32_t *idx_dev, double *val_dev, void *work_dev);
 
 /* ------------------------------------------------------------------------------------------
  * Local Collective Embeddings (csrc/lce.hip).  Replace the NumPy element-wise updates and traces of

@@ -13,6 +13,7 @@
     from polara_amd import EASEModel                                # EASE: closed-form item weights on a device SPD inverse
     from polara_amd import SLIMModel                                # SLIM: sparse item weights by device coordinate descent
     from polara_amd import ItemKNNModel, RP3BetaModel, P3AlphaModel # neighbourhood and random-walk item weights, K per item
+    from polara_amd import UserKNNModel                             # user neighbourhoods from a sparse neighbour pass, no image
     from polara_amd import SVDModelSampled, RandomSampleArrayData   # sampled-negatives evaluation (1 holdout + n unseen items)
     from polara_amd import ArrayData, ShardedArrayData              # NumPy / on-disk data providers
     from polara_amd import RecommenderArrayData                     # raw interactions -> folds, holdout, indices on the device
@@ -110,7 +111,7 @@ _EXPORTS = {
     'TuriFactorizationRecommender': 'fm', 'TuriFactorizationItemColdStart': 'fm',
     'EASEModel': 'ease',
     'SLIMModel': 'slim',
-    'ItemKNNModel': 'knn', 'RP3BetaModel': 'knn', 'P3AlphaModel': 'knn',
+    'ItemKNNModel': 'knn', 'RP3BetaModel': 'knn', 'P3AlphaModel': 'knn', 'UserKNNModel': 'knn',
     'SimilarityAggregation': 'simagg', 'SimilarityAggregationItemColdStart': 'simagg',
     'cosine_similarity': 'similarity', 'cosine_tfidf_similarity': 'similarity', 'jaccard_similarity': 'similarity',
     'jaccard_similarity_weighted': 'similarity', 'cross_similarity': 'similarity', 'combine_similarity': 'similarity',

@@ -138,6 +138,8 @@ PROTOTYPES = {
     'pk_i2i_topk': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     'pk_spsp_topk_work_bytes': (_i64, [_i64, _i64, _i32]),
     'pk_spsp_topk': (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'pk_spsp_topk_seen': (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp,
+                                    _vp]),
     'pk_spsp_rows_f64': (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _i64]),
     'pk_spgemm_work_bytes': (_i64, [_i64, _i64]),
     'pk_spgemm_count': (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
@@ -177,6 +179,9 @@ PROTOTYPES = {
     'pk_slim_csr_fill': (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     'pk_knn_max_neighbours': (_i32, []),
     'pk_knn_prune_f64': (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _f64, _i32, _i32, _vp, _vp, _vp]),
+    'pk_spsp_knn_work_bytes': (_i64, [_i64, _i64, _i32]),
+    'pk_spsp_knn_f64': (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _vp, _i32, _i32,
+                                  _vp, _vp, _vp, _vp]),
     'pk_lce_fused_max_rank': (_i32, []),
     'pk_lce_update_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _vp, _i64, _f64, _f64, _f64, _vp]),
     'pk_lce_update_ew_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _f64, _vp]),

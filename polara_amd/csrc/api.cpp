@@ -113,10 +113,11 @@ hipError_t pk_tu_load_spgemm();
 hipError_t pk_tu_load_split();
 hipError_t pk_tu_load_spmm();
 hipError_t pk_tu_load_ttm();
+hipError_t pk_tu_load_uknn();
 hipError_t pk_tu_load_warp();
 
 extern "C" int pk_warm_up(void) {
-    hipError_t (*const loaders[])() = {pk_tu_load_bpr, pk_tu_load_context, pk_tu_load_dense, pk_tu_load_driver, pk_tu_load_eigh, pk_tu_load_eigh_top, pk_tu_load_evalmetrics, pk_tu_load_fm, pk_tu_load_foldq, pk_tu_load_hybrid, pk_tu_load_i2i, pk_tu_load_ials, pk_tu_load_ialspp, pk_tu_load_ingest, pk_tu_load_knn, pk_tu_load_kpmf, pk_tu_load_lce, pk_tu_load_pmf, pk_tu_load_rescore, pk_tu_load_sampled, pk_tu_load_score, pk_tu_load_simagg, pk_tu_load_slim, pk_tu_load_spgemm, pk_tu_load_split, pk_tu_load_spmm, pk_tu_load_ttm, pk_tu_load_warp};
+    hipError_t (*const loaders[])() = {pk_tu_load_bpr, pk_tu_load_context, pk_tu_load_dense, pk_tu_load_driver, pk_tu_load_eigh, pk_tu_load_eigh_top, pk_tu_load_evalmetrics, pk_tu_load_fm, pk_tu_load_foldq, pk_tu_load_hybrid, pk_tu_load_i2i, pk_tu_load_ials, pk_tu_load_ialspp, pk_tu_load_ingest, pk_tu_load_knn, pk_tu_load_kpmf, pk_tu_load_lce, pk_tu_load_pmf, pk_tu_load_rescore, pk_tu_load_sampled, pk_tu_load_score, pk_tu_load_simagg, pk_tu_load_slim, pk_tu_load_spgemm, pk_tu_load_split, pk_tu_load_spmm, pk_tu_load_ttm, pk_tu_load_uknn, pk_tu_load_warp};
     for (auto f : loaders) {
         const hipError_t e = f();
         if (e != hipSuccess) {

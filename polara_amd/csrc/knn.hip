@@ -16,6 +16,7 @@
 //   * No contraction: every product, sum, difference and quotient is rounded on its own; fp64 division is the correctly
 //     rounded one (no fast-math flag in the build).
 #include "i2i_keys.h"
+#include "knn_weight.h"                    // knn_weight: shared with uknn.hip
 #include <float.h>
 
 #pragma clang fp contract(off)
@@ -30,12 +31,6 @@ __device__ __forceinline__ void knn_load8(const double *__restrict__ p, double *
         const double2 a = reinterpret_cast<const double2 *>(p)[k];
         c[2 * k] = a.x, c[2 * k + 1] = a.y;
     }
-}
-
-__device__ __forceinline__ double knn_weight(int kind, double g, double ri, double cj, double shrink) {
-    if (kind == PK_KNN_SCALE) return (g * ri) * cj;
-    if (kind == PK_KNN_COSINE) return g / (ri * cj + shrink);
-    return g / (((ri + cj) - g) + shrink);
 }
 
 // VEC: ldg % 8 == 0 and G, col 16-byte aligned — a lane whose 8 columns are all below n loads them as double2

@@ -26,17 +26,20 @@ extern "C" int64_t pk_spsp_topk_work_bytes(int64_t n_rows, int64_t n_cols, int32
     return pk_i2i_topk_work_bytes(n_rows, n_cols, topk);
 }
 
+// SEEN: the seen set of row r is row r of the pattern CSR (s_indptr, s_indices) over the columns (pk_spsp_topk_seen) instead
+// of the left row's own inner indices (pk_spsp_topk, where n_inner == n_cols)
+template <bool SEEN>
 __global__ __launch_bounds__(PK_I2I_THREADS) void spsp_window_kernel(
     int64_t r0, int64_t n_inner, int64_t n_cols, const int64_t *__restrict__ l_indptr, const int32_t *__restrict__ l_indices,
     const void *__restrict__ l_values, int l_kind, const int64_t *__restrict__ b_indptr, const int32_t *__restrict__ b_indices,
-    const double *__restrict__ b_values, int P, int filter_seen, int sparse, uint64_t *__restrict__ cand_s,
-    uint32_t *__restrict__ cand_m) {
+    const double *__restrict__ b_values, const int64_t *__restrict__ s_indptr, const int32_t *__restrict__ s_indices, int P,
+    int filter_seen, int sparse, uint64_t *__restrict__ cand_s, uint32_t *__restrict__ cand_m) {
     __shared__ uint64_t ks[PK_I2I_WIN];
     __shared__ uint32_t km[PK_I2I_WIN];
     __shared__ uint32_t seen[PK_I2I_WIN / 32];
     const int64_t w0 = (int64_t)blockIdx.y * PK_I2I_WIN;
     const bool touched = spsp_accumulate(r0 + blockIdx.x, w0, n_inner, l_indptr, l_indices, l_values, l_kind, b_indptr, b_indices,
-                                         b_values, filter_seen, ks, seen);
+                                         b_values, SEEN ? 0 : filter_seen, ks, seen);
     const int any = __syncthreads_or(touched);
     const int64_t base = ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * P;
     if (sparse && !any) {                    // no candidate in this window: pad keys, no sort
@@ -45,6 +48,16 @@ __global__ __launch_bounds__(PK_I2I_THREADS) void spsp_window_kernel(
             cand_m[base + k] = PK_I2I_ITEM_MASK;
         }
         return;
+    }
+    if (SEEN && filter_seen) {               // the bitmap is zero (spsp_accumulate): the row's seen columns of this window
+        const int64_t r = r0 + blockIdx.x, p1 = s_indptr[r + 1];
+        const int64_t lo = i2i_lower_bound(s_indices, s_indptr[r], p1, w0);
+        const int64_t hi = i2i_lower_bound(s_indices, lo, p1, w0 + PK_I2I_WIN);
+        for (int64_t k = lo + threadIdx.x; k < hi; k += PK_I2I_THREADS) {
+            const uint32_t d = (uint32_t)((int64_t)s_indices[k] - w0);
+            if (d < PK_I2I_WIN) atomicOr(&seen[d >> 5], 1u << (d & 31));
+        }
+        __syncthreads();
     }
     for (int slot = threadIdx.x; slot < PK_I2I_WIN; slot += PK_I2I_THREADS) {
         const int64_t col = w0 + slot;
@@ -98,6 +111,30 @@ static int spsp_check(const char *who, int64_t n_rows, int64_t n_inner, int64_t 
     return PK_OK;
 }
 
+static int spsp_topk_launch(void *stream, int64_t n_rows, int64_t n_inner, int64_t n_cols,
+                            const int64_t *l_indptr_dev, const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind,
+                            const int64_t *b_indptr_dev, const int32_t *b_indices_dev, const double *b_values_dev,
+                            const int64_t *s_indptr_dev, const int32_t *s_indices_dev, int32_t topk, int32_t filter_seen,
+                            int32_t sparse, int64_t *out_idx_dev, double *out_scores_dev, void *work_dev) {
+    const int64_t n_win = pk_ceil_div(n_cols, PK_I2I_WIN);
+    const int P = i2i_pow2(topk);
+    const int64_t chunk = pk_i2i_chunk_users(n_rows, n_cols, topk);
+    uint64_t *cand_s = static_cast<uint64_t *>(work_dev);
+    uint32_t *cand_m = reinterpret_cast<uint32_t *>(cand_s + chunk * n_win * P);
+    hipStream_t s = pk_stream(stream);
+    auto kernel = s_indptr_dev ? spsp_window_kernel<true> : spsp_window_kernel<false>;
+    for (int64_t r0 = 0; r0 < n_rows; r0 += chunk) {
+        const int64_t nr = n_rows - r0 < chunk ? n_rows - r0 : chunk;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nr, (unsigned)n_win), dim3(PK_I2I_THREADS), 0, s, r0, n_inner, n_cols,
+                           l_indptr_dev, l_indices_dev, l_values_dev, l_val_kind, b_indptr_dev, b_indices_dev, b_values_dev,
+                           s_indptr_dev, s_indices_dev, P, (int)filter_seen, (int)sparse, cand_s, cand_m);
+        PK_CHECK_LAUNCH("spsp_window_kernel");
+        i2i_launch_merge(s, nr, r0, (int)n_win, P, (int)topk, cand_s, cand_m, out_idx_dev, out_scores_dev);
+        PK_CHECK_LAUNCH("i2i_merge_kernel");
+    }
+    return PK_OK;
+}
+
 extern "C" int pk_spsp_topk(void *stream, int64_t n_rows, int64_t n_inner, int64_t n_cols, const int64_t *l_indptr_dev,
                             const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind, const int64_t *b_indptr_dev,
                             const int32_t *b_indices_dev, const double *b_values_dev, int32_t topk, int32_t filter_seen,
@@ -110,22 +147,25 @@ extern "C" int pk_spsp_topk(void *stream, int64_t n_rows, int64_t n_inner, int64
     if (rc != PK_OK) return rc;
     PK_REQUIRE(out_idx_dev && work_dev, "pk_spsp_topk: null pointer");
     if (n_rows == 0) return PK_OK;
-    const int64_t n_win = pk_ceil_div(n_cols, PK_I2I_WIN);
-    const int P = i2i_pow2(topk);
-    const int64_t chunk = pk_i2i_chunk_users(n_rows, n_cols, topk);
-    uint64_t *cand_s = static_cast<uint64_t *>(work_dev);
-    uint32_t *cand_m = reinterpret_cast<uint32_t *>(cand_s + chunk * n_win * P);
-    hipStream_t s = pk_stream(stream);
-    for (int64_t r0 = 0; r0 < n_rows; r0 += chunk) {
-        const int64_t nr = n_rows - r0 < chunk ? n_rows - r0 : chunk;
-        hipLaunchKernelGGL(spsp_window_kernel, dim3((unsigned)nr, (unsigned)n_win), dim3(PK_I2I_THREADS), 0, s, r0, n_inner, n_cols,
-                           l_indptr_dev, l_indices_dev, l_values_dev, l_val_kind, b_indptr_dev, b_indices_dev, b_values_dev, P,
-                           (int)filter_seen, (int)sparse, cand_s, cand_m);
-        PK_CHECK_LAUNCH("spsp_window_kernel");
-        i2i_launch_merge(s, nr, r0, (int)n_win, P, (int)topk, cand_s, cand_m, out_idx_dev, out_scores_dev);
-        PK_CHECK_LAUNCH("i2i_merge_kernel");
-    }
-    return PK_OK;
+    return spsp_topk_launch(stream, n_rows, n_inner, n_cols, l_indptr_dev, l_indices_dev, l_values_dev, l_val_kind,
+                            b_indptr_dev, b_indices_dev, b_values_dev, nullptr, nullptr, topk, filter_seen, sparse, out_idx_dev,
+                            out_scores_dev, work_dev);
+}
+
+extern "C" int pk_spsp_topk_seen(void *stream, int64_t n_rows, int64_t n_inner, int64_t n_cols, const int64_t *l_indptr_dev,
+                                 const int32_t *l_indices_dev, const void *l_values_dev, int l_val_kind,
+                                 const int64_t *b_indptr_dev, const int32_t *b_indices_dev, const double *b_values_dev,
+                                 const int64_t *seen_indptr_dev, const int32_t *seen_indices_dev, int32_t topk,
+                                 int32_t filter_seen, int32_t sparse, int64_t *out_idx_dev, double *out_scores_dev,
+                                 void *work_dev) {
+    PK_REQUIRE(topk >= 1 && topk <= PK_I2I_MAX_TOPK, "pk_spsp_topk_seen: topk %d outside 1..%d", (int)topk, PK_I2I_MAX_TOPK);
+    const int rc = spsp_check("pk_spsp_topk_seen", n_rows, n_inner, n_cols, l_indptr_dev, b_indptr_dev, l_val_kind);
+    if (rc != PK_OK) return rc;
+    PK_REQUIRE(out_idx_dev && work_dev && seen_indptr_dev, "pk_spsp_topk_seen: null pointer");
+    if (n_rows == 0) return PK_OK;
+    return spsp_topk_launch(stream, n_rows, n_inner, n_cols, l_indptr_dev, l_indices_dev, l_values_dev,
+                            l_val_kind, b_indptr_dev, b_indices_dev, b_values_dev, seen_indptr_dev, seen_indices_dev, topk,
+                            filter_seen, sparse, out_idx_dev, out_scores_dev, work_dev);
 }
 
 extern "C" int pk_spsp_rows_f64(void *stream, int64_t row0, int64_t n_rows, int64_t n_inner, int64_t n_cols,
@@ -148,5 +188,5 @@ extern "C" int pk_spsp_rows_f64(void *stream, int64_t row0, int64_t n_rows, int6
 // eager load of this translation unit's code object (pk_warm_up, api.cpp)
 hipError_t pk_tu_load_simagg() {
     hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&spsp_window_kernel));
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&spsp_window_kernel<false>));
 }

@@ -869,6 +869,22 @@ class HipOps:
         new._nnz = p1 - p0
         return new
 
+    def csr_gather_rows(self, A, rows):
+        """The DeviceCSR whose row k is row rows[k] of A (host or device int64 ids; plumbing in torch, no kernel)."""
+        rows = rows if torch.is_tensor(rows) else torch.as_tensor(np.ascontiguousarray(rows, dtype=np.int64))
+        rows = rows.to(device=self.device, dtype=torch.int64)
+        start = A.indptr[rows]
+        length = A.indptr[rows + 1] - start
+        indptr = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=self.device)
+        torch.cumsum(length, 0, out=indptr[1:])
+        nnz = int(indptr[-1].item())
+        pos = torch.repeat_interleave(start - indptr[:-1], length) + torch.arange(nnz, dtype=torch.int64, device=self.device)
+        new = DeviceCSR.from_device(self, indptr, A.indices[pos].contiguous(), A.values[pos].contiguous(),
+                                    (int(rows.numel()), A.shape[1]), A.split)
+        new.sorted_cols = A.sorted_cols
+        new._nnz = nnz
+        return new
+
     def randn(self, n, m, seed):
         # device-side Philox stream: identical on every rank for the same seed (the solver relies
         # on all ranks starting from the same block), and no 50 MB host round trip
@@ -2149,6 +2165,83 @@ class HipOps:
         stored = idx >= 0
         W = DeviceCSR.from_device(self, indptr, idx[stored], val[stored], (n, n))
         return W
+
+    # ---- the neighbour pass without an image (csrc/uknn.hip) and scoring with a separate seen set ------------------------
+    def _own_csr(self, A, what):
+        """`A` must be a DeviceCSR of this device (its addresses are handed to a kernel)."""
+        for t in (getattr(A, 'indptr', None), getattr(A, 'indices', None), getattr(A, 'values', None)):
+            if not torch.is_tensor(t) or t.device.type != self.device.type or (
+                    self.device.index is not None and t.device.index != self.device.index):
+                raise ValueError('%s is no device CSR on %s' % (what, self.device))
+        if A.indptr.dtype != torch.int64 or A.indices.dtype != torch.int32 or A.values.dtype not in (torch.float32, torch.float64):
+            raise ValueError('%s: int64 indptr, int32 indices and fp32 or fp64 values expected' % what)
+        return A
+
+    def spsp_knn_slots(self, L, B, kind, row, col, shrink, K, normalize, exclude=None):
+        """(count int32 [n_rows], idx int32 [n_rows x K], val fp64 [n_rows x K]), all on the device: the K best normalised
+        entries of every row of L B for the device CSR L [n_rows x n_inner] and the canonical device CSR B [n_inner x
+        n_cols], in ascending column order, pads idx -1 / val 0 (pk_spsp_knn_f64: the contract of include/polara_hip.h; no
+        image of the product exists).  `kind`: knn.KINDS; row: n_rows doubles, col: n_cols doubles, host arrays or device
+        tensors; exclude: None or n_rows int32 column ids (negative: nothing) a row may not keep."""
+        from . import knn, simagg
+        self._own_csr(L, 'spsp_knn: L')
+        self._own_csr(B, 'spsp_knn: B')
+        n_rows, n_inner, n_cols = simagg.check_shapes(L.shape, B.shape)
+        K = knn.check_neighbours(K)
+        vec = []
+        for name, v, n in (('row', row, n_rows), ('col', col, n_cols)):
+            v = v if torch.is_tensor(v) else self.to_device(np.asarray(v, dtype=np.float64))
+            v = v.to(device=self.device, dtype=torch.float64).contiguous()
+            if v.numel() != n:
+                raise ValueError('spsp_knn: `%s` holds %d numbers, %d expected' % (name, v.numel(), n))
+            vec.append(v)
+        if exclude is not None:
+            exclude = exclude if torch.is_tensor(exclude) else torch.as_tensor(np.asarray(exclude, dtype=np.int32))
+            exclude = exclude.to(device=self.device, dtype=torch.int32).contiguous()
+            if exclude.numel() != n_rows:
+                raise ValueError('spsp_knn: `exclude` holds %d ids for %d rows' % (exclude.numel(), n_rows))
+        count = torch.empty(n_rows, dtype=torch.int32, device=self.device)
+        idx = torch.empty(n_rows, K, dtype=torch.int32, device=self.device)
+        val = torch.empty(n_rows, K, dtype=torch.float64, device=self.device)
+        work = self._work(self.lib.pk_spsp_knn_work_bytes(n_rows, n_cols, K))
+        with self._timed('spsp_knn', (n_rows, n_cols, L.nnz, K)):
+            _lib.check(self.lib.pk_spsp_knn_f64(self.stream(), n_rows, n_inner, n_cols, _ptr(L.indptr), _ptr(L.indices),
+                                                _ptr(L.values), L.val_kind, _ptr(B.indptr), _ptr(B.indices),
+                                                _ptr(self._spsp_values(B)), int(kind), _ptr(vec[0]), _ptr(vec[1]), float(shrink),
+                                                _ptr(exclude), K, 1 if normalize else 0, _ptr(count), _ptr(idx), _ptr(val),
+                                                _ptr(work)), 'pk_spsp_knn_f64')
+        return count, idx, val
+
+    def spsp_knn(self, L, B, kind, row, col, shrink, K, normalize, exclude=None):
+        """The canonical DeviceCSR [n_rows x n_cols] (fp64) of `spsp_knn_slots`, built as `knn_prune` builds its own."""
+        count, idx, val = self.spsp_knn_slots(L, B, kind, row, col, shrink, K, normalize, exclude)
+        indptr = torch.zeros(count.numel() + 1, dtype=torch.int64, device=self.device)
+        torch.cumsum(count, 0, out=indptr[1:])
+        stored = idx >= 0
+        return DeviceCSR.from_device(self, indptr, idx[stored], val[stored], (int(L.shape[0]), int(B.shape[1])))
+
+    def spsp_topk_seen(self, L, B, seen, topk, filter_seen, sparse, want_scores=False):
+        """`spsp_topk` with the seen set of row r taken from row r of the device CSR `seen` [n_rows x n_cols] (its pattern;
+        sorted columns) instead of L's own row, so L's inner dimension need not be the catalogue (pk_spsp_topk_seen)."""
+        from . import simagg
+        self._own_csr(L, 'spsp_topk_seen: L')
+        self._own_csr(B, 'spsp_topk_seen: B')
+        self._own_csr(seen, 'spsp_topk_seen: seen')
+        n_rows, n_inner, n_cols = simagg.check_shapes(L.shape, B.shape)
+        if tuple(seen.shape) != (n_rows, n_cols) or not getattr(seen, 'sorted_cols', True):
+            raise ValueError('spsp_topk_seen: the seen set is %s (sorted columns: %s), the scores are %d x %d'
+                             % (tuple(seen.shape), getattr(seen, 'sorted_cols', True), n_rows, n_cols))
+        topk = int(topk)
+        out = torch.empty(n_rows, topk, dtype=torch.int64, device=self.device)
+        scores = torch.empty(n_rows, topk, dtype=torch.float64, device=self.device) if want_scores else None
+        work = self._work(self.lib.pk_spsp_topk_work_bytes(n_rows, n_cols, topk))
+        with self._timed('spsp_topk_seen', (n_rows, n_cols, L.nnz, topk)):
+            _lib.check(self.lib.pk_spsp_topk_seen(self.stream(), n_rows, n_inner, n_cols, _ptr(L.indptr), _ptr(L.indices),
+                                                  _ptr(L.values), L.val_kind, _ptr(B.indptr), _ptr(B.indices),
+                                                  _ptr(self._spsp_values(B)), _ptr(seen.indptr), _ptr(seen.indices), topk,
+                                                  1 if filter_seen else 0, 1 if sparse else 0, _ptr(out), _ptr(scores),
+                                                  _ptr(work)), 'pk_spsp_topk_seen')
+        return out, scores
 
     # ---- item cold start -----------------------------------------------------------------------------------------
     def coldstart_queries(self, F, W, G):
