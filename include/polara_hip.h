@@ -558,6 +558,18 @@ int pk_fold_q20_zero(void *stream, int64_t n_tasks, const int32_t *task_row_dev,
                      const int32_t *indices_dev, const void *vals_dev, int val_kind, const void *img_dev,
                      const double *tab_dev, int64_t n_items, int32_t K, int32_t Kx, double *out_dev, int64_t ldo,
                      double *partial_dev, int32_t *zero_dev, int32_t zero_n);
+/* pk_fold_q20_zero with `tasks_per_wave` adjacent row tasks sharing one wave: 1 (what the two entries above run), 2 or 4; any
+ * other value is refused, and the value is clamped to what the rank's lane class allows (4 up to K = 50, 2 up to K = 101, 1
+ * above).  A wave runs as long as the longest of its tasks, so more than one pays only where adjacent tasks are alike in
+ * length (a matrix whose rows are in activity order): the caller states that by asking for it.  Every value keeps the
+ * contract above (the same certified weight, the same rows written); the bits of columns 0 .. K-1 may differ between
+ * values — the order of the fp64 sums — and never between two launches of one value. */
+int pk_fold_q20_sliced(void *stream, int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
+                       const int64_t *task_end_dev, const int32_t *task_slot_dev, int64_t n_long,
+                       const int32_t *long_row_dev, const int32_t *long_slot_begin_dev, const int32_t *long_slot_end_dev,
+                       const int32_t *indices_dev, const void *vals_dev, int val_kind, const void *img_dev,
+                       const double *tab_dev, int64_t n_items, int32_t K, int32_t Kx, double *out_dev, int64_t ldo,
+                       double *partial_dev, int32_t *zero_dev, int32_t zero_n, int32_t tasks_per_wave);
 /* dst[perm_dev[r], :] = src_dev[r, :] for rows of `width` int64 (perm_dev == NULL: a plain copy): the lists of a pass whose
  * users were grouped by activity go back to the caller's user order.  `dst` is device memory or MAPPED PINNED HOST memory:
  * the host-side [n_users x topk] int64 array of get_recommendations (models.py:400-405) can be written by the kernel

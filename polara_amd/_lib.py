@@ -108,6 +108,8 @@ PROTOTYPES = {
                               _vp, _i64, _vp]),
     'pk_fold_q20_zero': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _i64, _i32, _i32,
                                    _vp, _i64, _vp, _vp, _i32]),
+    'pk_fold_q20_sliced': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _i64, _i32, _i32,
+                                     _vp, _i64, _vp, _vp, _i32, _i32]),
     'pk_rescore_f64': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32,
                                  _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     'pk_zero_i32': (C.c_int, [_vp, _vp, _i32]),

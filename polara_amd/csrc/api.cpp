@@ -36,7 +36,7 @@ extern "C" int pk_set_option(const char *name, int32_t value, int32_t unset) {
     pk_set_error("pk_set_option: unknown option '%s'", name ? name : "(null)");
     return PK_E_INVALID;
 }
-extern "C" int pk_version(void) { return 104; }
+extern "C" int pk_version(void) { return 105; }
 
 // Results on their way out, in stream order behind the kernels that produced them: `dst_host` should be pinned memory (the copy
 // is then asynchronous; from pageable memory the runtime stages it).  An entry of its own so that a host layer that replays a

@@ -25,7 +25,7 @@
 //
 // Mapping: one wave per row task (the plan of spmm.hip), the wave cut into 64 / L groups of L lanes, group g takes
 // entries g, g + GROUPS, ... of the task; one dwordx4 load per lane and entry; group sums added in a fixed order
-// (deterministic).
+// (deterministic).  Where the caller states that adjacent tasks are alike, 2 or 4 of them share a wave (the kernel's T).
 // Arithmetic: the first version converted every window to fp64 and accumulated with v_fma_f64 — and ran at the speed of
 // the fp32-image kernel (0.233 against 0.259 ms on the ML-20M-shaped fold-in): both are bound by their fp64 CONVERSIONS
 // (v_cvt_f64_*: a quarter of the VALU rate), not by the texture path.  Here a lane multiplies in fp32 — packed
@@ -201,6 +201,9 @@ static inline int q20_steps(int L) {
     // fact of encoder and kernel alike, because the rows' certified weights carry U + 2 roundings: VERDICT r5 weak #8)
     return L >= 8 ? 4 : (L == 4 ? 2 : 1);
 }
+// (T, the row tasks per wave, is no such fact: the weights do not depend on it.  The scoring pass asks for 4 on its
+// activity-ordered matrix, ops.FOLD_TASKS_PER_WAVE, where the launch is long enough — ML-20M-shaped rank 50: 0.176 / 0.160 /
+// 0.155 ms for T = 1 / 2 / 4, VALU instructions per launch 77.9 M -> 67.3 M; profiles/foldq_slices_ml20m.txt)
 // unit of the weight digit: the largest weight a row can need — every column half a step (2048 units) off plus its fp32
 // conversion (64), the fp32 arithmetic term on a row of full-scale windows, the extra columns counted at twice a main
 // one's magnitude — must fit 126 digit units
@@ -314,7 +317,15 @@ typedef float pk_f2 __attribute__((ext_vector_type(2)));
 
 // (Measured and not kept, round 5: the fp64 accumulators in LDS with the register allocation held to 6 or 8 waves per SIMD
 // — 0.245 ms against 0.232 with the accumulators in registers and 5 waves: occupancy is not what this kernel waits for.)
-template <typename VT, int L, int U>
+// T = tasks per wave (1, 2 or 4).  T = 1 is the mapping above.  For T > 1 the wave is cut into T SLICES of CH = 64 / T lanes:
+// slice s of wave w owns task T * w + s, its GS = GROUPS / T lane groups take entries g, g + GS, ... of that task, and a
+// chunk is CH pairs of EACH task (one coalesced 64-lane load per wave still).  The per-task prologue and epilogue — about
+// as many VALU instructions as the body of a median row — are then paid once per T tasks.  The loop's trip count, `have`,
+// `have_next` and the skipped steps follow the LONGEST task of the wave: a slice past its own end holds padded pairs
+// (0, 0.0) like the tail of a chunk, so the mapping pays where adjacent tasks are alike in length (rows in activity order)
+// and is the caller's choice (pk_fold_q20_sliced).  A slice whose task lies beyond n_tasks runs as a task of no entries
+// and stores nothing; a real empty task stores its zeros.  The shuffles' sources stay inside the slice.
+template <typename VT, int L, int U, int T>
 __global__ __launch_bounds__(256) void fold_q20_kernel(
     int64_t n_tasks, const int32_t *__restrict__ task_row, const int64_t *__restrict__ task_begin,
     const int64_t *__restrict__ task_end, const int32_t *__restrict__ task_slot,
@@ -322,17 +333,38 @@ __global__ __launch_bounds__(256) void fold_q20_kernel(
     const double *__restrict__ tab, double kappa, int K, int Kx, double *__restrict__ out, int64_t ldo,
     double *__restrict__ partial) {
     constexpr int GROUPS = 64 / L;
-    constexpr int SPC = L;                                   // wave steps per 64-pair chunk
+    constexpr int GS = GROUPS / T;                           // lane groups of a slice
+    constexpr int CH = 64 / T;                               // lanes of a slice = pairs of one task per chunk
+    constexpr int SPC = L;                                   // wave steps per chunk (CH / GS)
     constexpr int SETS = SPC / U;                            // register sets (U steps each, two in flight) per chunk
+    static_assert(T == 1 || T == 2 || T == 4, "1, 2 or 4 tasks per wave");
+    static_assert(GS >= 2 && GS * T == GROUPS, "a slice holds at least two lane groups");
     static_assert(SETS >= 1 && SETS * U == SPC, "a chunk is a whole number of register sets");
     constexpr int LOG_RB = L == 2 ? 5 : (L == 4 ? 6 : (L == 8 ? 7 : (L == 16 ? 8 : 9)));   // log2(row bytes)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t task = (int64_t)blockIdx.x * 4 + wave;
-    if (task >= n_tasks) return;
-    const int64_t p0 = task_begin[task];
-    const int n = (int)(task_end[task] - p0);
+    const int64_t wtask = ((int64_t)blockIdx.x * 4 + wave) * T;
+    if (wtask >= n_tasks) return;
+    const int sl = T == 1 ? 0 : lane / CH, ls = lane % CH;   // slice, lane of the slice
+    const int64_t task = wtask + sl;
+    const bool real = T == 1 || task < n_tasks;
+    int64_t p0 = 0;
+    int n = 0;                                               // per lane for T > 1: the entries of the slice's task
+    if (real) {
+        p0 = task_begin[task];
+        n = (int)(task_end[task] - p0);
+    }
+    int nmax = n;                                            // wave-uniform: the longest task of the wave
+    if constexpr (T > 1) {
+        nmax = __builtin_amdgcn_readlane(n, 0);
+#pragma unroll
+        for (int s = 1; s < T; ++s) {
+            const int ns = __builtin_amdgcn_readlane(n, s * CH);
+            nmax = ns > nmax ? ns : nmax;
+        }
+    }
     const int g = lane / L, l = lane % L;
+    const int src0 = T == 1 ? g : (lane & ~(CH - 1)) | (g % GS);                     // the slice's lane that holds the group's pair of step 0
     const int32_t *ip = indices + p0;
     const VT *vp = vals + p0;
     const char *Xb = reinterpret_cast<const char *>(img);
@@ -346,21 +378,21 @@ __global__ __launch_bounds__(256) void fold_q20_kernel(
     // the top of the iteration before it), the chunk after that in flight
     int jc = 0, jn = 0;
     VT araw = (VT)0, an = (VT)0;
-    if (lane < n) {
-        jc = ip[lane];
-        araw = vp[lane];
+    if (ls < n) {
+        jc = ip[ls];
+        araw = vp[ls];
     }
-    if (64 + lane < n) {
-        jn = ip[64 + lane];
-        an = vp[64 + lane];
+    if (CH + ls < n) {
+        jn = ip[CH + ls];
+        an = vp[CH + ls];
     }
     // (a step whose eight pairs all lie beyond the chunk's count is skipped — loads and products: rows are 20 .. 9 000
     // entries long and a short row's last register set is mostly padding)
     auto issue = [&](int jch, int st0, int cnt_ch, uint4(&x)[U]) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if (u > 0 && (st0 + u) * GROUPS >= cnt_ch) break;
-            const int jj = __shfl(jch, (st0 + u) * GROUPS + g, 64);
+            if (u > 0 && (st0 + u) * GS >= cnt_ch) break;
+            const int jj = __shfl(jch, (st0 + u) * GS + src0, 64);
             unsigned off;
             asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(off) : "v"(jj), "n"(LOG_RB), "v"(lo0));
             x[u] = *reinterpret_cast<const uint4 *>(Xb + off);
@@ -372,8 +404,8 @@ __global__ __launch_bounds__(256) void fold_q20_kernel(
         float s6 = 0.0f;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if (u > 0 && (st0 + u) * GROUPS >= cnt_ch) break;
-            const float a = __shfl(ach, (st0 + u) * GROUPS + g, 64);
+            if (u > 0 && (st0 + u) * GS >= cnt_ch) break;
+            const float a = __shfl(ach, (st0 + u) * GS + src0, 64);
             const pk_f2 aa = {a, a};
             const uint4 d = x[u];
             const pk_f2 x01 = {(float)(int)__builtin_amdgcn_alignbit(d.x, d.y, 24), (float)(int)__builtin_amdgcn_alignbit(d.x, d.y, 4)};
@@ -393,27 +425,27 @@ __global__ __launch_bounds__(256) void fold_q20_kernel(
         acc[6] += (double)s6;
     };
     uint4 x0[U], x1[U];
-    issue(jc, 0, n < 64 ? n : 64, x0);                       // the first gathers do not wait for the scale
+    issue(jc, 0, nmax < CH ? nmax : CH, x0);                 // the first gathers do not wait for the scale
     float ac = (float)((double)araw * tab[pk_q20_bracket((unsigned)jc)]);
-    // one 64-pair chunk whose first set sits in register file P (the sets alternate between the two files; with an odd
+    // one chunk (CH pairs per task; the counts are those of the wave's longest task) whose first set sits in register file P (the sets alternate between the two files; with an odd
     // number of sets per chunk the next chunk starts in the other one)
     auto chunk = [&](int p, auto P) {
         constexpr int P0 = decltype(P)::value;
-        const int cnt = (n - p) < 64 ? (n - p) : 64;         // pairs of this chunk; padded lanes hold (0, 0.0)
-        const bool more = p + 64 < n;
-        const int cnt_next = (n - p - 64) < 64 ? (n - p - 64) : 64;
+        const int cnt = (nmax - p) < CH ? (nmax - p) : CH;   // pairs of this chunk; padded lanes hold (0, 0.0)
+        const bool more = p + CH < nmax;
+        const int cnt_next = (nmax - p - CH) < CH ? (nmax - p - CH) : CH;
         int jf = 0;
         VT af = (VT)0;
-        if (p + 128 + lane < n) {                            // pairs two chunks ahead
-            jf = ip[p + 128 + lane];
-            af = vp[p + 128 + lane];
+        if (p + 2 * CH + ls < n) {                           // pairs two chunks ahead
+            jf = ip[p + 2 * CH + ls];
+            af = vp[p + 2 * CH + ls];
         }
         double sn = 0.0;
         if (more) sn = tab[pk_q20_bracket((unsigned)jn)];     // the next chunk's scales (its indices arrived a chunk ago)
 #pragma unroll
         for (int k = 0; k < SETS; ++k) {
-            const bool have = k * U * GROUPS < cnt;
-            const bool have_next = (k + 1 < SETS) ? ((k + 1) * U * GROUPS < cnt) : more;
+            const bool have = k * U * GS < cnt;
+            const bool have_next = (k + 1 < SETS) ? ((k + 1) * U * GS < cnt) : more;
             if (((k + P0) & 1) == 0) {
                 if (have_next) {
                     if (k + 1 < SETS) issue(jc, (k + 1) * U, cnt, x1);
@@ -434,26 +466,40 @@ __global__ __launch_bounds__(256) void fold_q20_kernel(
         an = af;
     };
     if constexpr ((SETS & 1) == 0) {
-        for (int p = 0; p < n; p += 64) chunk(p, std::integral_constant<int, 0>());
+        for (int p = 0; p < nmax; p += CH) chunk(p, std::integral_constant<int, 0>());
     } else {
         // an odd number of sets per chunk: two chunks bring the files back to where they started
-        for (int p = 0; p < n; p += 128) {
+        for (int p = 0; p < nmax; p += 2 * CH) {
             chunk(p, std::integral_constant<int, 0>());
-            if (p + 64 < n) chunk(p + 64, std::integral_constant<int, 1>());
+            if (p + CH < nmax) chunk(p + CH, std::integral_constant<int, 1>());
         }
     }
 
-    // ---- sum over the groups (fixed order: deterministic).  After the halving rounds a lane holds the totals of TWO column
-    // slots (four for L = 32): slot t0 = 4 * bit5(lane) + 2 * bit4(lane) and t0 + 1; slot 6 is the digit's sum.
-    double w[4];
-    w[0] = q20_swap_add32(acc[0], acc[4]);
-    w[1] = q20_swap_add32(acc[1], acc[5]);
-    w[2] = q20_swap_add32(acc[2], acc[6]);
-    w[3] = q20_swap_add32(acc[3], 0.0);
-    constexpr int NW = L <= 16 ? 2 : 4;
-    if constexpr (L <= 16) {
-        w[0] = q20_swap_add16(w[0], w[2]);
-        w[1] = q20_swap_add16(w[1], w[3]);
+    // ---- sum over the groups of the slice (fixed order: deterministic).
+    // T = 1: after the halving rounds a lane holds the totals of TWO column slots (four for L = 32): slot
+    //        t0 = 4 * bit5(lane) + 2 * bit4(lane) and t0 + 1; slot 6 is the digit's sum.
+    // T = 2: a slice is a half wave, so the 32-lane exchange drops out: v_permlane16_swap on (slot k, slot k + 4) leaves
+    //        FOUR slots per lane, t0 = 4 * bit4(lane); the 8 / 4 / 2-lane distances go through the DPP butterflies.
+    // T = 4: a slice is one 16-lane row: the DPP butterflies alone, on all seven sums; every lane holds every slot.
+    constexpr int NW = T == 4 ? 7 : ((T == 2 || L == 32) ? 4 : 2);
+    double w[NW];
+    if constexpr (T == 1) {
+        const double h0 = q20_swap_add32(acc[0], acc[4]), h1 = q20_swap_add32(acc[1], acc[5]);
+        const double h2 = q20_swap_add32(acc[2], acc[6]), h3 = q20_swap_add32(acc[3], 0.0);
+        if constexpr (L <= 16) {
+            w[0] = q20_swap_add16(h0, h2);
+            w[1] = q20_swap_add16(h1, h3);
+        } else {
+            w[0] = h0, w[1] = h1, w[2] = h2, w[3] = h3;
+        }
+    } else if constexpr (T == 2) {
+        w[0] = q20_swap_add16(acc[0], acc[4]);
+        w[1] = q20_swap_add16(acc[1], acc[5]);
+        w[2] = q20_swap_add16(acc[2], acc[6]);
+        w[3] = q20_swap_add16(acc[3], 0.0);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 7; ++i) w[i] = acc[i];
     }
 #pragma unroll
     for (int i = 0; i < NW; ++i) {
@@ -462,22 +508,30 @@ __global__ __launch_bounds__(256) void fold_q20_kernel(
         if constexpr (L <= 2) w[i] += pk_lane_xor<2>(w[i]);
     }
     const int b5 = (lane >> 5) & 1, b4 = (lane >> 4) & 1;
-    const int t0 = L <= 16 ? 4 * b5 + 2 * b4 : 4 * b5;          // first column slot this lane holds
-    // the digit's sum (slot 6) sits in w[0] of the lanes with t0 == 6 (L <= 16) or in w[2] of the upper half (L = 32);
+    // first column slot this lane holds
+    const int t0 = T == 4 ? 0 : (T == 2 ? 4 * b4 : (L <= 16 ? 4 * b5 + 2 * b4 : 4 * b5));
+    // the digit's sum (slot 6) sits in w[6 - t0] of the lanes that hold it: w[0] where t0 == 6 (T = 1, L <= 16), w[2] of the
+    // upper half wave (T = 1, L = 32) or of the upper rows (T = 2), w[6] everywhere (T = 4);
     // the three digit sums of an extra column meet in its top lane
-    const double dsum = L <= 16 ? w[0] : w[2];
+    constexpr int DW = T == 4 ? 6 : ((T == 2 || L == 32) ? 2 : 0);
+    const double dsum = w[DW];
     const double a1 = __shfl(dsum, lane + 1, 64), a2 = __shfl(dsum, lane + 2, 64);
-    const int slot = task_slot[task];
-    double *dst = slot < 0 ? out + (int64_t)task_row[task] * ldo : partial + (int64_t)slot * Kx;
-    // one lane per (row piece l, slot pair) stores: the lanes whose group bits below bit 4 are zero
-    const bool owner = L <= 16 ? (((lane & 15) / L) == 0) : true;
+    int slot = -1;
+    int64_t row = 0;
+    if (real) {
+        slot = task_slot[task];
+        row = task_row[task];
+    }
+    double *dst = slot < 0 ? out + row * ldo : partial + (int64_t)slot * Kx;
+    // one lane per (row piece l, slot set) stores: the lanes whose group bits below bit 4 are zero
+    const bool owner = real && (L <= 16 ? (((lane & 15) / L) == 0) : true);
     if (owner) {
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
             const int t = t0 + i;
             if (t < 6 && 6 * l + t < K) dst[6 * l + t] = w[i];
         }
-        const bool digit_lane = L <= 16 ? (t0 == 6) : (b5 == 1);
+        const bool digit_lane = T == 4 ? true : (T == 2 ? (b4 == 1) : (L <= 16 ? (t0 == 6) : (b5 == 1)));
         if (digit_lane) {
             const int e = l / 3;
             if (l % 3 == 0 && 3 * e + 2 <= L - 2 && 6 * L + e < K) dst[6 * L + e] = 2.0 * (dsum + a1 * 0.00390625 + a2 * 1.52587890625e-05);
@@ -510,53 +564,70 @@ __global__ __launch_bounds__(256) void fold_q20_fixup_kernel(int64_t n_long, con
 }
 
 template <typename VT>
-static void launch_fold_q20(hipStream_t st, int L, int64_t n_tasks, const int32_t *task_row, const int64_t *task_begin,
+static void launch_fold_q20(hipStream_t st, int L, int T, int64_t n_tasks, const int32_t *task_row, const int64_t *task_begin,
                             const int64_t *task_end, const int32_t *task_slot, const int32_t *indices, const void *vals,
                             const uint4 *img, const double *tab, double kappa, int K, int Kx, double *out, int64_t ldo, double *partial) {
-    const dim3 grid((unsigned)pk_ceil_div(n_tasks, 4)), block(256);
+    const dim3 grid((unsigned)pk_ceil_div(n_tasks, (int64_t)4 * T)), block(256);      // four waves of T tasks per workgroup
     const VT *v = static_cast<const VT *>(vals);
-#define PK_FOLDQ(LL, UU)                                                                                                      \
-    hipLaunchKernelGGL((fold_q20_kernel<VT, LL, UU>), grid, block, 0, st, n_tasks, task_row, task_begin, task_end, task_slot, \
+#define PK_FOLDQ(LL, UU, TT)                                                                                                      \
+    hipLaunchKernelGGL((fold_q20_kernel<VT, LL, UU, TT>), grid, block, 0, st, n_tasks, task_row, task_begin, task_end, task_slot, \
                        indices, v, img, tab, kappa, K, Kx, out, ldo, partial)
+#define PK_FOLDQ_T4(LL, UU)                      \
+    do {                                         \
+        if (T == 4) PK_FOLDQ(LL, UU, 4);         \
+        else if (T == 2) PK_FOLDQ(LL, UU, 2);    \
+        else PK_FOLDQ(LL, UU, 1);                \
+    } while (0)
     switch (L) {
-        case 2: PK_FOLDQ(2, 1); break;
-        case 4: PK_FOLDQ(4, 2); break;
+        case 2: PK_FOLDQ_T4(2, 1); break;
+        case 4: PK_FOLDQ_T4(4, 2); break;
         case 8:
-            if (q20_steps(8) == 2) PK_FOLDQ(8, 2);
-            else if (q20_steps(8) == 8) PK_FOLDQ(8, 8);
-            else PK_FOLDQ(8, 4);
+            if (q20_steps(8) == 2) PK_FOLDQ_T4(8, 2);
+            else if (q20_steps(8) == 8) PK_FOLDQ_T4(8, 8);
+            else PK_FOLDQ_T4(8, 4);
             break;
-        case 16: PK_FOLDQ(16, 4); break;
-        default: PK_FOLDQ(32, 4); break;
+        case 16:
+            if (T == 2) PK_FOLDQ(16, 4, 2);
+            else PK_FOLDQ(16, 4, 1);
+            break;
+        default: PK_FOLDQ(32, 4, 1); break;
     }
+#undef PK_FOLDQ_T4
 #undef PK_FOLDQ
 }
 
-// pk_fold_q20 that also zeroes zero_dev[0 .. zero_n) (int32 device counters; zero_n == 0: nothing) in its fix-up launch —
-// which then runs even without a split row, as one workgroup that only zeroes
-extern "C" int pk_fold_q20_zero(void *stream, int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
-                                const int64_t *task_end_dev, const int32_t *task_slot_dev, int64_t n_long,
-                                const int32_t *long_row_dev, const int32_t *long_slot_begin_dev, const int32_t *long_slot_end_dev,
-                                const int32_t *indices_dev, const void *vals_dev, int val_kind, const void *img_dev,
-                                const double *tab_dev, int64_t n_items, int32_t K, int32_t Kx, double *out_dev, int64_t ldo,
-                                double *partial_dev, int32_t *zero_dev, int32_t zero_n) {
+// The fold-in with `tasks_per_wave` = 1, 2 or 4 adjacent row tasks per wave (fold_q20_kernel's T; anything else is refused),
+// clamped to what the lane class allows: 4 for L <= 8, 2 for L = 16, 1 for L = 32.  More than one pays where adjacent tasks
+// are alike in length — the wave runs as long as its longest task — which only the caller knows (rows in activity order).
+// Every value returns the product within the same certified weight; the bits differ between values (the order of the
+// fp64 sums), never between launches of one value.  zero_dev / zero_n: as pk_fold_q20_zero.
+// Which value the scoring pass uses on its activity-ordered matrix is recorded at ops.FOLD_TASKS_PER_WAVE with its measurement.
+extern "C" int pk_fold_q20_sliced(void *stream, int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
+                                  const int64_t *task_end_dev, const int32_t *task_slot_dev, int64_t n_long,
+                                  const int32_t *long_row_dev, const int32_t *long_slot_begin_dev, const int32_t *long_slot_end_dev,
+                                  const int32_t *indices_dev, const void *vals_dev, int val_kind, const void *img_dev,
+                                  const double *tab_dev, int64_t n_items, int32_t K, int32_t Kx, double *out_dev, int64_t ldo,
+                                  double *partial_dev, int32_t *zero_dev, int32_t zero_n, int32_t tasks_per_wave) {
     const int L = q20_lanes(K);
     PK_REQUIRE(L != 0 && n_tasks >= 0 && Kx >= K + 1 && ldo >= Kx, "pk_fold_q20: bad sizes (K=%d, Kx=%d)", K, Kx);
     PK_REQUIRE(n_items >= 1 && n_items < (1 << 24) && n_items * L * 16 < ((int64_t)1 << 32), "pk_fold_q20: image beyond 32-bit offsets");
     PK_REQUIRE(n_long == 0 || partial_dev != nullptr, "pk_fold_q20: partial buffer required");
     PK_REQUIRE(val_kind == PK_VAL_F32 || val_kind == PK_VAL_F64, "pk_fold_q20: bad val_kind %d", val_kind);
     PK_REQUIRE(zero_n >= 0 && zero_n <= (1 << 20) && (zero_n == 0 || zero_dev != nullptr), "pk_fold_q20: bad counter range");
+    PK_REQUIRE(tasks_per_wave == 1 || tasks_per_wave == 2 || tasks_per_wave == 4, "pk_fold_q20_sliced: tasks_per_wave %d (1, 2 or 4)",
+               tasks_per_wave);
+    const int T = L == 32 ? 1 : (L == 16 && tasks_per_wave > 2 ? 2 : tasks_per_wave);
     hipStream_t st = pk_stream(stream);
     if (n_tasks == 0) n_long = 0;      // nothing to fold: only the counters are left to do
     if (n_tasks > 0) {
         const uint4 *img = static_cast<const uint4 *>(img_dev);
         const double kappa = q20_kappa(K);
         if (val_kind == PK_VAL_F32)
-            launch_fold_q20<float>(st, L, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev, vals_dev, img,
-                                   tab_dev, kappa, K, Kx, out_dev, ldo, partial_dev);
+            launch_fold_q20<float>(st, L, T, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev, vals_dev,
+                                   img, tab_dev, kappa, K, Kx, out_dev, ldo, partial_dev);
         else
-            launch_fold_q20<double>(st, L, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev, vals_dev, img,
-                                    tab_dev, kappa, K, Kx, out_dev, ldo, partial_dev);
+            launch_fold_q20<double>(st, L, T, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, indices_dev, vals_dev,
+                                    img, tab_dev, kappa, K, Kx, out_dev, ldo, partial_dev);
         PK_CHECK_LAUNCH("fold_q20_kernel");
     }
     if (n_long > 0 || zero_n > 0) {
@@ -567,15 +638,28 @@ extern "C" int pk_fold_q20_zero(void *stream, int64_t n_tasks, const int32_t *ta
     return PK_OK;
 }
 
+// pk_fold_q20 that also zeroes zero_dev[0 .. zero_n) (int32 device counters; zero_n == 0: nothing) in its fix-up launch —
+// which then runs even without a split row, as one workgroup that only zeroes.  One task per wave.
+extern "C" int pk_fold_q20_zero(void *stream, int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
+                                const int64_t *task_end_dev, const int32_t *task_slot_dev, int64_t n_long,
+                                const int32_t *long_row_dev, const int32_t *long_slot_begin_dev, const int32_t *long_slot_end_dev,
+                                const int32_t *indices_dev, const void *vals_dev, int val_kind, const void *img_dev,
+                                const double *tab_dev, int64_t n_items, int32_t K, int32_t Kx, double *out_dev, int64_t ldo,
+                                double *partial_dev, int32_t *zero_dev, int32_t zero_n) {
+    return pk_fold_q20_sliced(stream, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, n_long, long_row_dev,
+                              long_slot_begin_dev, long_slot_end_dev, indices_dev, vals_dev, val_kind, img_dev, tab_dev, n_items, K, Kx,
+                              out_dev, ldo, partial_dev, zero_dev, zero_n, 1);
+}
+
 extern "C" int pk_fold_q20(void *stream, int64_t n_tasks, const int32_t *task_row_dev, const int64_t *task_begin_dev,
                            const int64_t *task_end_dev, const int32_t *task_slot_dev, int64_t n_long,
                            const int32_t *long_row_dev, const int32_t *long_slot_begin_dev, const int32_t *long_slot_end_dev,
                            const int32_t *indices_dev, const void *vals_dev, int val_kind, const void *img_dev,
                            const double *tab_dev, int64_t n_items, int32_t K, int32_t Kx, double *out_dev, int64_t ldo,
                            double *partial_dev) {
-    return pk_fold_q20_zero(stream, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, n_long, long_row_dev,
-                            long_slot_begin_dev, long_slot_end_dev, indices_dev, vals_dev, val_kind, img_dev, tab_dev, n_items, K, Kx,
-                            out_dev, ldo, partial_dev, nullptr, 0);
+    return pk_fold_q20_sliced(stream, n_tasks, task_row_dev, task_begin_dev, task_end_dev, task_slot_dev, n_long, long_row_dev,
+                              long_slot_begin_dev, long_slot_end_dev, indices_dev, vals_dev, val_kind, img_dev, tab_dev, n_items, K, Kx,
+                              out_dev, ldo, partial_dev, nullptr, 0, 1);
 }
 
 // eager load of this translation unit's code object (pk_warm_up, api.cpp): the runtime loads a code object at the first

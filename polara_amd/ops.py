@@ -16,6 +16,13 @@ from . import _lib
 from .csr import SPLIT_NNZ
 
 
+# row tasks per wave of the packed fold-in on a matrix marked `adjacent_alike` (csrc/foldq.hip: fold_q20_kernel's T)
+FOLD_TASKS_PER_WAVE = 4
+# ... as long as the launch keeps this many waves per SIMD: five rounds of the kernel's residency (90 VGPRs: 5 waves).  T tasks
+# per wave are T times fewer waves that each run T times as long, and a launch of a few rounds ends on its longest waves:
+# ML-20M-shaped rows at rank 50, ms for T = 1 / 2 / 4 — 8 K tasks 0.017 / 0.029 / 0.052, 28 K 0.040 / 0.049 / 0.084, 56 K 0.076 /
+# 0.071 / 0.096, 140 K 0.176 / 0.160 / 0.155 (profiles/foldq_slices_ml20m.txt): T pays from ~27 waves per SIMD, not at ~14
+FOLD_SLICED_MIN_WAVES = 25
 _PTR_KEEP = None      # scoring.RecordedPass: the tensors whose addresses went into the recorded calls (kept alive with them)
 
 
@@ -188,7 +195,8 @@ class DeviceCSR:
 
     def by_activity(self):
         """(this matrix with its rows ordered by descending entry count, perm int64: row r of the result = row perm[r]
-        of this one) — a format image like the transpose, built once (pk_csr_rows_by_length) and cached."""
+        of this one) — a format image like the transpose, built once (pk_csr_rows_by_length) and cached.  The image is marked
+        `adjacent_alike`: adjacent row tasks are alike in length, which lets the packed fold-in share a wave among them."""
         if getattr(self, '_by_activity', None) is None:
             self._by_activity = self.ops.csr_rows_by_length(self)
         return self._by_activity
@@ -755,6 +763,7 @@ class HipOps:
         P._nnz = nnz
         P.sorted_cols = A.sorted_cols
         P._nonneg = getattr(A, '_nonneg', None)
+        P.adjacent_alike = True        # rows in order of length: adjacent row tasks are alike (fold_q20's tasks_per_wave)
         return P, perm.long()
 
     def csr_relabel_cols(self, A, col_map, sort=True):
@@ -1008,14 +1017,18 @@ class HipOps:
                    'pk_q20_decode_f64')
         return out
 
-    def fold_q20(self, A, image, K, out, rows=None, counters=None):
+    def fold_q20(self, A, image, K, out, rows=None, counters=None, tasks_per_wave=None):
         """out[:, :K] = A @ decode(image), out[:, K] = w = A @ D (the certified weight of the image's error),
         zeros up to out's width.  A: DeviceCSR with non-negative values; rows as in `spmm`.
-        counters (int32 device tensor): zeroed by the fold-in's fix-up launch (`fold_q20_zero`)."""
+        counters (int32 device tensor): zeroed by the fold-in's fix-up launch (`fold_q20_zero`).
+        tasks_per_wave: adjacent row tasks per wave (`pk_fold_q20_sliced`); by default `fold_tasks_per_wave`: more than 1 only
+        for a matrix marked `adjacent_alike` (the image `by_activity` builds) and a launch long enough."""
         img, tab = image
         Kx = out.shape[1]
         assert out.dtype == torch.float64 and out.stride(1) == 1 and Kx >= K + 1 and img.shape[0] == A.shape[1]
         t0, n_tasks, l0, n_long = (0, A.n_tasks, 0, A.n_long) if rows is None else A.task_range(int(rows[0]), int(rows[1]))
+        if tasks_per_wave is None:
+            tasks_per_wave = self.fold_tasks_per_wave(A, n_tasks)
         p = A.plan
         meta = None
         if self.timers is not None:
@@ -1024,13 +1037,30 @@ class HipOps:
                 _ptr(p['task_slot'], t0), n_long, _ptr(p['long_row'], l0), _ptr(p['long_slot_begin'], l0),
                 _ptr(p['long_slot_end'], l0), _ptr(A.indices), _ptr(A.values), A.val_kind, _ptr(img), _ptr(tab),
                 int(A.shape[1]), int(K), int(Kx), _ptr(out), out.stride(0), _ptr(A.partial(Kx)))
+        if counters is not None:
+            assert counters.dtype == torch.int32 and counters.is_contiguous() and counters.numel() >= 1
         with self._timed('fold_q20', meta):
-            if counters is None:
+            if tasks_per_wave != 1:
+                zero = (None, 0) if counters is None else (_ptr(counters), int(counters.numel()))
+                _lib.check(self.lib.pk_fold_q20_sliced(*args, *zero, int(tasks_per_wave)), 'pk_fold_q20_sliced')
+            elif counters is None:
                 _lib.check(self.lib.pk_fold_q20(*args), 'pk_fold_q20')
             else:
-                assert counters.dtype == torch.int32 and counters.is_contiguous() and counters.numel() >= 1
                 _lib.check(self.lib.pk_fold_q20_zero(*args, _ptr(counters), int(counters.numel())), 'pk_fold_q20_zero')
         return out
+
+    def fold_tasks_per_wave(self, A, n_tasks):
+        """what `fold_q20` asks pk_fold_q20_sliced for: FOLD_TASKS_PER_WAVE on a matrix marked `adjacent_alike`, halved until
+        the launch still has FOLD_SLICED_MIN_WAVES waves per SIMD (T tasks per wave are T times fewer waves: a launch that
+        does not fill the device keeps one task per wave); 1 for every other matrix"""
+        if not getattr(A, 'adjacent_alike', False):
+            return 1
+        if getattr(self, '_simds', None) is None:
+            self._simds = 4 * torch.cuda.get_device_properties(self.device).multi_processor_count
+        T = FOLD_TASKS_PER_WAVE
+        while T > 1 and n_tasks < T * FOLD_SLICED_MIN_WAVES * self._simds:
+            T //= 2
+        return T
 
     def fold_q20_zero(self, A, image, K, out, n_counters, rows=None):
         """`fold_q20` + `zero_counters(n_counters)` in the launches of the fold-in alone: returns the int32 [n] counters, zero
