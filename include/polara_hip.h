@@ -1275,6 +1275,44 @@ int pk_ialspp_predict_f64(void *stream, int64_t n_rows, int64_t n_cols, int32_t 
                           double *E_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Logistic matrix factorisation (csrc/lmf.hip; polara_amd/lmf.py): Johnson (2014) in the shape the `implicit` package trains it
+ * — rank k plus a bias on either side, per-parameter AdaGrad, sampled negatives —, fp64.  Blocks carry K = k + 2 columns: the user
+ * block [factors | bias | 1], the item block [factors | 1 | bias], so that their product are the logits (and the scores).
+ * One half-step fixes Y [n_cols x K] and moves, for a CSR of confidences C [n_rows x n_cols] (fp64 values, int64 row pointers,
+ * int32 column ids), every row u of X [n_rows x K] with n > 0 stored entries (confidences c_q in storage order), together with
+ * its AdaGrad state A [n_rows x K] (zeros at build start, kept over the epochs):
+ *   negatives:  m = min(n_cols, n * neg_prop);  neg_ptr = the exclusive prefix sum of m over the rows (int64 [n_rows + 1]);
+ *     h = mix64(seed * 2^32 + round)  (mix64 = the splitmix64 output function, the key of the BPR stream above);
+ *     negative t = 0 .. m - 1 is column ((mix64(h + neg_ptr[u] + t) >> 32) * n_cols) >> 32  (64-bit) — uniform over ALL
+ *     columns, with replacement, the row's own entries included (the sampled term estimates the sum over all items);
+ *   the sample list q = 0 .. n + m - 1: the positives in storage order, then the negatives in draw order; y_q its row of Y;
+ *   in IEEE fp64 without contraction, every product and sum rounded on its own, sqrt and division correctly rounded:
+ *     s_q  = (..((x_0 * y_q0) + x_1 * y_q1) + ..) + x_{K-1} * y_q,K-1           (x = the row as it was before the step)
+ *     g_q  = c_q * sigm(s_q) for a positive,  -sigm(-s_q) for a negative         (sigm(x) = 1 / (1 + exp(x)): the BPR sequence)
+ *     D_c  = chain_0 + chain_1 + .. + chain_{PK_LMF_CHAINS - 1}  (left to right),  chain_j = 0 + sum over q = j mod PK_LMF_CHAINS,
+ *            ascending, of g_q * y_qc  (left to right)
+ *     d_c  = D_c - reg * x_c;   a_c = A[u][c] + d_c * d_c;   A[u][c] <- a_c;   X[u][c] <- x_c + (lr / sqrt(1e-6 + a_c)) * d_c
+ *   for every column c but pinned_col (the constant 1: K - 1 of the user block, K - 2 of the item block; -1: none), which is
+ *   touched neither in X nor in A.  An empty row is not touched at all.  No row is refused: a NaN propagates.
+ * One workgroup per row, taken in the order row_order_dev lists them (a permutation of 0 .. n_rows - 1, longest rows first;
+ * NULL: ascending); the order of every summation depends on the row alone: equal inputs give equal bits, whatever the row order.
+ * No atomics; no sample array exists.  Column ids outside 0 .. n_cols - 1 read a row of zeros.  pk_lmf_max_rank() = 126 (K <= 128).
+ * pk_lmf_draw_negatives: out_dev[neg_ptr[u] + t] = negative t of row u, through the half-step's own draw function (int32
+ * [neg_ptr[n_rows]]); a row whose neg_ptr does not span min(n_cols, n * neg_prop) is skipped.  pk_lmf_chains() = PK_LMF_CHAINS. */
+#ifndef PK_LMF_CHAINS
+#define PK_LMF_CHAINS 4
+#endif
+int32_t pk_lmf_max_rank(void);
+int32_t pk_lmf_chains(void);
+int pk_lmf_half_step_f64(void *stream, int64_t n_rows, int64_t n_cols, int32_t K, const int64_t *indptr_dev,
+                         const int32_t *indices_dev, const double *conf_dev, const int32_t *row_order_dev,
+                         const int64_t *neg_ptr_dev, uint32_t seed, uint32_t round, int32_t pinned_col, int32_t neg_prop,
+                         const double *Y_dev, int64_t ldy, double learning_rate, double regularization, double *X_dev,
+                         int64_t ldx, double *A_dev, int64_t lda);
+int pk_lmf_draw_negatives(void *stream, int64_t n_rows, int64_t n_cols, const int64_t *indptr_dev,
+                          const int64_t *neg_ptr_dev, int32_t neg_prop, uint32_t seed, uint32_t round, int32_t *out_dev);
+
+/* ------------------------------------------------------------------------------------------
  * K5.  Sparse tensor-times-matrix (CoFFee / HOOI).
  * Replaces numba `dttm_seq` / `dttm_par` (lib/sparse.py:203-234) called from `ttm3d_seq`
  * (lib/tensor.py:7-19):  res[i0, j, k] += val * u[i1, j] * v[i2, k].

@@ -9,6 +9,7 @@
     from polara_amd import ImplicitALS                              # iALS / WRMF: alternating least squares, exact per-row solves
     from polara_amd import ImplicitALSPP                            # iALS++: block-subspace steps of the same objective, ranks to 2048
     from polara_amd import ImplicitBPR                              # BPR-MF: pairwise ranking by a blocked triplet sweep
+    from polara_amd import ImplicitLMF                              # logistic MF: per-row AdaGrad half-steps, negatives drawn in-kernel
     from polara_amd import LightFMWrapper, LightFMItemColdStart     # LightFM (WARP, item features), standard and item cold start
     from polara_amd import EASEModel                                # EASE: closed-form item weights on a device SPD inverse
     from polara_amd import SLIMModel                                # SLIM: sparse item weights by device coordinate descent
@@ -107,6 +108,7 @@ _EXPORTS = {
     'ImplicitALS': 'ials',
     'ImplicitALSPP': 'ialspp',
     'ImplicitBPR': 'bpr',
+    'ImplicitLMF': 'lmf',
     'LightFMWrapper': 'warp', 'LightFMItemColdStart': 'warp',
     'TuriFactorizationRecommender': 'fm', 'TuriFactorizationItemColdStart': 'fm',
     'EASEModel': 'ease',

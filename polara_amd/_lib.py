@@ -228,6 +228,11 @@ PROTOTYPES = {
     'pk_ialspp_block_step_f64': (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp, _i64,
                                            _vp, _i64, _vp, _vp, _vp]),
     'pk_ialspp_predict_f64': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    'pk_lmf_max_rank': (_i32, []),
+    'pk_lmf_chains': (_i32, []),
+    'pk_lmf_half_step_f64': (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _i32, _i32, _vp, _i64, _f64,
+                                       _f64, _vp, _i64, _vp, _i64]),
+    'pk_lmf_draw_negatives': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, C.c_uint32, C.c_uint32, _vp]),
     'pk_clamp_min_f64': (C.c_int, [_vp, _i64, _i32, _vp, _i64, _f64]),
     'pk_ctx_create': (C.c_int, [_i32, C.POINTER(_vp)]),
     'pk_ctx_destroy': (None, [_vp]),

@@ -100,6 +100,7 @@ hipError_t pk_tu_load_fm();
 hipError_t pk_tu_load_foldq();
 hipError_t pk_tu_load_ingest();
 hipError_t pk_tu_load_lce();
+hipError_t pk_tu_load_lmf();
 hipError_t pk_tu_load_knn();
 hipError_t pk_tu_load_kpmf();
 hipError_t pk_tu_load_pmf();
@@ -117,7 +118,7 @@ hipError_t pk_tu_load_uknn();
 hipError_t pk_tu_load_warp();
 
 extern "C" int pk_warm_up(void) {
-    hipError_t (*const loaders[])() = {pk_tu_load_bpr, pk_tu_load_context, pk_tu_load_dense, pk_tu_load_driver, pk_tu_load_eigh, pk_tu_load_eigh_top, pk_tu_load_evalmetrics, pk_tu_load_fm, pk_tu_load_foldq, pk_tu_load_hybrid, pk_tu_load_i2i, pk_tu_load_ials, pk_tu_load_ialspp, pk_tu_load_ingest, pk_tu_load_knn, pk_tu_load_kpmf, pk_tu_load_lce, pk_tu_load_pmf, pk_tu_load_rescore, pk_tu_load_sampled, pk_tu_load_score, pk_tu_load_simagg, pk_tu_load_slim, pk_tu_load_spgemm, pk_tu_load_split, pk_tu_load_spmm, pk_tu_load_ttm, pk_tu_load_uknn, pk_tu_load_warp};
+    hipError_t (*const loaders[])() = {pk_tu_load_bpr, pk_tu_load_context, pk_tu_load_dense, pk_tu_load_driver, pk_tu_load_eigh, pk_tu_load_eigh_top, pk_tu_load_evalmetrics, pk_tu_load_fm, pk_tu_load_foldq, pk_tu_load_hybrid, pk_tu_load_i2i, pk_tu_load_ials, pk_tu_load_ialspp, pk_tu_load_ingest, pk_tu_load_knn, pk_tu_load_kpmf, pk_tu_load_lce, pk_tu_load_lmf, pk_tu_load_pmf, pk_tu_load_rescore, pk_tu_load_sampled, pk_tu_load_score, pk_tu_load_simagg, pk_tu_load_slim, pk_tu_load_spgemm, pk_tu_load_split, pk_tu_load_spmm, pk_tu_load_ttm, pk_tu_load_uknn, pk_tu_load_warp};
     for (auto f : loaders) {
         const hipError_t e = f();
         if (e != hipSuccess) {

@@ -3116,6 +3116,80 @@ class HipOps:
             reg += float(lam * torch.trace(Gm).item()) if lam_rows is None else float((lam_rows * (M * M).sum(dim=1)).sum().item())
         return float((self.to_host(GX) * self.to_host(GY)).sum() + sparse + reg)
 
+    # ---- Logistic matrix factorisation (csrc/lmf.hip) --------------------------------------------------------------------
+    def lmf_max_rank(self):
+        return int(self.lib.pk_lmf_max_rank())
+
+    def lmf_plan(self, Cm, neg_prop):
+        """What a half-step over the rows of the DeviceCSR of confidences `Cm` [n_rows x n_cols] needs beside the matrix, made
+        once and kept on the matrix (as `Cm.T` is): a dict with row_order (int32 [n_rows]: longest rows first, the iALS order),
+        neg_ptr (int64 [n_rows + 1]: the exclusive prefix sum of m = min(n_cols, n * neg_prop) over the rows), negatives (their
+        total: the negatives of one half-step), neg_prop, matrix, shape."""
+        neg_prop = int(neg_prop)
+        if neg_prop < 1 or neg_prop >= 2 ** 31:
+            raise ValueError('LMF: neg_prop %d < 1' % neg_prop)
+        plans = Cm.__dict__.setdefault('_lmf_plans', {})
+        plan = plans.get(neg_prop)
+        if plan is None:
+            n_rows, n_cols = (int(x) for x in Cm.shape)
+            with self._timed('lmf_plan', (n_rows, n_cols, int(Cm.indices.numel()), neg_prop)):
+                lengths = Cm.indptr[1:n_rows + 1] - Cm.indptr[:n_rows]
+                neg_ptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=self.device)
+                neg_ptr[1:] = torch.cumsum(torch.clamp(lengths * neg_prop, max=n_cols), 0)
+                plan = plans[neg_prop] = dict(row_order=self._ials_row_order(Cm), neg_ptr=neg_ptr, negatives=int(neg_ptr[-1].item()),
+                                              neg_prop=neg_prop, matrix=Cm, shape=(n_rows, n_cols))
+        return plan
+
+    @staticmethod
+    def _lmf_stream(seed, round):
+        seed, round = int(seed), int(round)
+        if not (0 <= seed < 2 ** 32 and 0 <= round < 2 ** 32):
+            raise ValueError('LMF: seed %d and round %d must fit 32 unsigned bits' % (seed, round))
+        return seed, round
+
+    def lmf_half_step(self, plan, Y, X, A, lr, reg, seed, round, pinned, row_order=None):
+        """One half-step of logistic matrix factorisation (pk_lmf_half_step_f64; the arithmetic is spelled out in
+        include/polara_hip.h), IN PLACE on X [n_rows x K] and on its AdaGrad state A [n_rows x K] against the fixed block Y
+        [n_cols x K], K = rank + 2: every non-empty row of the plan's matrix takes one full-batch AdaGrad step on its positives
+        and on min(n_cols, n * neg_prop) negatives drawn inside the kernel from the stream (seed, round).  pinned: the column of
+        X that holds the constant 1 (touched neither in X nor in A; -1: none).  Views with a leading dimension are fine.
+        row_order: int32 device permutation of the rows (None: the plan's) — never a bit of the result.  Returns X."""
+        Cm = plan['matrix']
+        n_rows, n_cols = plan['shape']
+        K = int(Y.shape[1])
+        if K < 3 or K - 2 > self.lmf_max_rank():
+            raise ValueError('LMF: rank %d outside 1..%d' % (K - 2, self.lmf_max_rank()))
+        for M, n in ((X, n_rows), (A, n_rows), (Y, n_cols)):
+            if M.dtype != torch.float64 or M.dim() != 2 or tuple(M.shape) != (n, K) or M.stride(1) != 1 or M.stride(0) < K:
+                raise ValueError('LMF half-step: a block of shape %s, strides %s for [%d x %d] fp64 rows'
+                                 % (tuple(M.shape), M.stride(), n, K))
+        pinned = int(pinned)
+        if pinned < -1 or pinned >= K:
+            raise ValueError('LMF half-step: pinned column %d outside -1..%d' % (pinned, K - 1))
+        seed, round = self._lmf_stream(seed, round)
+        order = plan['row_order'] if row_order is None else row_order
+        if order.dtype != torch.int32 or order.numel() != n_rows or not order.is_contiguous():
+            raise ValueError('LMF half-step: row_order must be a contiguous int32 permutation of the %d rows' % n_rows)
+        conf = Cm.values if Cm.values.dtype == torch.float64 else Cm.values.to(torch.float64)
+        with self._timed('lmf_half_step', (n_rows, n_cols, int(Cm.indices.numel()), plan['negatives'], K)):
+            _lib.check(self.lib.pk_lmf_half_step_f64(self.stream(), n_rows, n_cols, K, _ptr(Cm.indptr), _ptr(Cm.indices), _ptr(conf),
+                                                     _ptr(order), _ptr(plan['neg_ptr']), seed, round, pinned, plan['neg_prop'],
+                                                     _ptr(Y), Y.stride(0), float(lr), float(reg), _ptr(X), X.stride(0), _ptr(A),
+                                                     A.stride(0)), 'pk_lmf_half_step_f64')
+        return X
+
+    def lmf_draw_negatives(self, plan, seed, round):
+        """int32 [plan['negatives']] (device): the negatives the half-step of (seed, round) draws, row after row in draw order
+        (pk_lmf_draw_negatives: the kernel's own draw function; the stream is spelled out in include/polara_hip.h)."""
+        Cm = plan['matrix']
+        n_rows, n_cols = plan['shape']
+        seed, round = self._lmf_stream(seed, round)
+        total = plan['negatives']
+        out = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)[:total]
+        _lib.check(self.lib.pk_lmf_draw_negatives(self.stream(), n_rows, n_cols, _ptr(Cm.indptr), _ptr(plan['neg_ptr']), plan['neg_prop'],
+                                                  seed, round, _ptr(out)), 'pk_lmf_draw_negatives')
+        return out
+
     def dense_scores(self, V, E):
         n_rows, K = E.shape
         n_items = V.shape[0]
